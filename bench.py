@@ -4,12 +4,18 @@
 Workload (BASELINE.json configs[1]): batch of 4096 independent condensed QPs per GPU, curvilinear kinematic
 bicycle, N=40 (nV=81, nC=240), fp64, generic mode of SURVEY 8(d): the dense (H,g,A,lb,ub,lbA,ubA) tensors are
 resident in HBM when the timed region starts; one step = one batched solve (+ the RCCL gather of x when N>1).
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 N > 1: one rank per GPU over RCCL.  Started under torch.distributed.run (RANK / WORLD_SIZE in the environment) this
 process is one rank; started plainly it spawns the N ranks itself (a child `python -m torch.distributed.run ... bench.py`
 -- before anything here touches the GPU) and relays rank 0's line.  Rank 0 prints ONE JSON line.
-cpu_baseline = the CPU oracle timed on the host cores (a reported baseline).  --dry-run exercises the launch, sharding,
-gather and reporting path without a GPU (gloo, zeros instead of solves; used by tests/test_abi_cpu.py)."""
+A plain run sets up, warms up, times the K steps and reports the headline with what the timed steps themselves give (kernel
+times, iteration / exit-flag histograms, roofline from the archived counters).  --full adds the measurements that need work of
+their own after the timed steps: the fused mode (rate and phase times), the KKT re-check of the returned points, and
+cpu_baseline = the CPU oracle timed on the host cores (a reported baseline; --no-cpu-baseline leaves it out).
+--dump-outputs DIR writes what the last timed step returned (x, fval, exitflag, iter, kkt, polished) as DIR/<name>.npy in
+float64; the inputs depend only on the arguments, so two builds can be compared output for output.
+--dry-run exercises the launch, sharding, gather and reporting path without a GPU (gloo, zeros instead of solves; used by
+tests/test_abi_cpu.py)."""
 import argparse
 import ctypes as C
 import json
@@ -23,6 +29,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X fp64 matrix peak (the microarch guide lists no fp64 row)
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: larger outputs are written as a fixed, seeded sample of instances
 
 
 def main():
@@ -33,9 +40,13 @@ def main():
     ap.add_argument("--batch", type=int, default=4096, help="instances per GPU (weak scaling)")
     ap.add_argument("--horizon", type=int, default=40)
     ap.add_argument("--model", default="kinematic", choices=["kinematic", "dynamic"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also the fused mode, the KKT re-check and the CPU baseline (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float64)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: launch / shard / gather / report path only (CPU, gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # self-start: one child launcher, N ranks; this parent never initialises the GPU
@@ -140,49 +151,59 @@ def main():
     if world > 1:   # per-rank solved counts from the gathered block itself (exit flag 0), as every rank sees them
         _, _, fl_all, _ = shard.ResultGather.unpack(out["all"], nV)
         solved_per_rank = [int((fl_all[r * Bl:(r + 1) * Bl] == 0).sum().item()) for r in range(world)]
-    # fused mode of SURVEY 8(d) (x0, x_ref, x_lin, u_lin -> u_opt, x_opt: construction + solve + post-solve), timed
-    # separately after the headline loop; reported in `config`, never as `value`
-    fx0, fxr, fxl, ful = up(x0), up(xr), up(xl), up(ul)
-    stepper.step(fx0, fxr, fxl, ful); torch.cuda.synchronize(dev)
-    tf0 = time.perf_counter()
-    for _ in range(max(2, min(args.steps, 5))):
-        fo = stepper.step(fx0, fxr, fxl, ful)
-    torch.cuda.synchronize(dev)
-    t_fused = time.perf_counter() - tf0
-    fused_rate = float((fo["exitflag"] == 0).sum().item()) * max(2, min(args.steps, 5)) / t_fused
-    # the fused step's four phases by HIP events on the launch stream (one more step, outside every timed region)
-    L.fsaempc_qp_set_timing(1)
-    stepper.step(fx0, fxr, fxl, ful)
-    ph = [C.c_double(0) for _ in range(4)]
-    fused_phases = None
-    if L.fsaempc_ltv_get_timing(*[C.byref(p_) for p_ in ph]) == 0:
-        fused_phases = dict(zip(("build", "prep", "solve", "post"), (round(p_.value, 4) for p_ in ph)))
-    L.fsaempc_qp_set_timing(0)
-    if os.environ.get("FSAEMPC_BENCH_DEBUG"):
-        print("fused: %.2f ms per step, solved %d" % (1e3 * t_fused / max(2, min(args.steps, 5)), int((fo["exitflag"] == 0).sum().item())), file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from the last timed step: the whole gathered batch when N > 1
+        if world > 1:
+            gx, gf, gfl, git = shard.ResultGather.unpack(out["all"], nV)
+            dumped = dict(x=gx, fval=gf, exitflag=gfl, iter=git)
+        else:
+            dumped = {k: out[k] for k in ("x", "fval", "exitflag", "iter", "kkt", "polished")}
+        dump_outputs(args.dump_outputs, {k: t.cpu().numpy() for k, t in dumped.items()})
     mean_it = float(iters.mean())
-    # SURVEY 8(d) extras, rank 0's shard, outside the timed region: iteration / status histograms and the worst relative
-    # KKT residual of the returned (x, lambda), evaluated with torch on the device (plumbing, not the product path)
+    # iteration / status histograms of the last timed step (rank 0's shard)
     it_hist = {int(k_): int(c_) for k_, c_ in zip(*np.unique(iters, return_counts=True))}
     fl_hist = {int(k_): int(c_) for k_, c_ in zip(*np.unique(flags, return_counts=True))}
-    chk = fm.qp_solve_batch_device(*qp_args, workspace=ws, want_lambda=True)
-    torch.cuda.synchronize(dev)
-    Hm, gv, Am, lbv, ubv, lbAv, ubAv = qp_args
-    xs, lam = chk["x"], chk["lam"]
-    AT = Am.transpose(1, 2)                                   # (B, nC, nV): A is stored column-major nC x nV per instance
-    Hx = torch.bmm(Hm, xs.unsqueeze(2)).squeeze(2)
-    Ax = torch.bmm(AT, xs.unsqueeze(2)).squeeze(2)
-    r_d = Hx + gv - lam[:, :nV] - torch.bmm(Am, lam[:, nV:].unsqueeze(2)).squeeze(2)
-    sc_d = torch.clamp(torch.maximum(gv.abs().amax(1), Hx.abs().amax(1)), min=1.0)
-    v = torch.cat([xs, Ax], 1); lo_ = torch.cat([lbv, lbAv], 1); hi_ = torch.cat([ubv, ubAv], 1)
-    fin_lo, fin_hi = lo_ > -1e9, hi_ < 1e9
-    viol = torch.maximum(torch.where(fin_lo, lo_ - v, torch.zeros_like(v)), torch.where(fin_hi, v - hi_, torch.zeros_like(v))).clamp(min=0)
-    sc_p = torch.clamp(v.abs().amax(1), min=1.0)
-    fv = chk["fval"].abs().clamp(min=1.0)
-    comp = torch.where(lam > 0, lam * torch.where(fin_lo, v - lo_, torch.zeros_like(v)), -lam * torch.where(fin_hi, hi_ - v, torch.zeros_like(v))).abs()
-    kkt = torch.stack([r_d.abs().amax(1) / sc_d, viol.amax(1) / sc_p, comp.amax(1) / fv], 1)
-    okm = chk["exitflag"] == 0
-    kkt_max = [float(t) for t in kkt[okm].amax(0).cpu()] if bool(okm.any()) else [float("nan")] * 3
+    fused_rate, fused_phases, kkt_max = None, None, [None] * 3
+    if args.full:
+        # fused mode of SURVEY 8(d) (x0, x_ref, x_lin, u_lin -> u_opt, x_opt: construction + solve + post-solve), timed
+        # separately after the headline loop; reported in `config`, never as `value`
+        fx0, fxr, fxl, ful = up(x0), up(xr), up(xl), up(ul)
+        stepper.step(fx0, fxr, fxl, ful); torch.cuda.synchronize(dev)
+        tf0 = time.perf_counter()
+        for _ in range(max(2, min(args.steps, 5))):
+            fo = stepper.step(fx0, fxr, fxl, ful)
+        torch.cuda.synchronize(dev)
+        t_fused = time.perf_counter() - tf0
+        fused_rate = float((fo["exitflag"] == 0).sum().item()) * max(2, min(args.steps, 5)) / t_fused
+        # the fused step's four phases by HIP events on the launch stream (one more step, outside every timed region)
+        L.fsaempc_qp_set_timing(1)
+        stepper.step(fx0, fxr, fxl, ful)
+        ph = [C.c_double(0) for _ in range(4)]
+        if L.fsaempc_ltv_get_timing(*[C.byref(p_) for p_ in ph]) == 0:
+            fused_phases = dict(zip(("build", "prep", "solve", "post"), (round(p_.value, 4) for p_ in ph)))
+        L.fsaempc_qp_set_timing(0)
+        if os.environ.get("FSAEMPC_BENCH_DEBUG"):
+            print("fused: %.2f ms per step, solved %d" % (1e3 * t_fused / max(2, min(args.steps, 5)), int((fo["exitflag"] == 0).sum().item())), file=sys.stderr)
+        # SURVEY 8(d) extra, rank 0's shard, outside the timed region: the worst relative KKT residual of the returned
+        # (x, lambda), evaluated with torch on the device (plumbing, not the product path)
+        chk = fm.qp_solve_batch_device(*qp_args, workspace=ws, want_lambda=True)
+        torch.cuda.synchronize(dev)
+        Hm, gv, Am, lbv, ubv, lbAv, ubAv = qp_args
+        xs, lam = chk["x"], chk["lam"]
+        AT = Am.transpose(1, 2)                                   # (B, nC, nV): A is stored column-major nC x nV per instance
+        Hx = torch.bmm(Hm, xs.unsqueeze(2)).squeeze(2)
+        Ax = torch.bmm(AT, xs.unsqueeze(2)).squeeze(2)
+        r_d = Hx + gv - lam[:, :nV] - torch.bmm(Am, lam[:, nV:].unsqueeze(2)).squeeze(2)
+        sc_d = torch.clamp(torch.maximum(gv.abs().amax(1), Hx.abs().amax(1)), min=1.0)
+        v = torch.cat([xs, Ax], 1); lo_ = torch.cat([lbv, lbAv], 1); hi_ = torch.cat([ubv, ubAv], 1)
+        fin_lo, fin_hi = lo_ > -1e9, hi_ < 1e9
+        viol = torch.maximum(torch.where(fin_lo, lo_ - v, torch.zeros_like(v)), torch.where(fin_hi, v - hi_, torch.zeros_like(v))).clamp(min=0)
+        sc_p = torch.clamp(v.abs().amax(1), min=1.0)
+        fv = chk["fval"].abs().clamp(min=1.0)
+        comp = torch.where(lam > 0, lam * torch.where(fin_lo, v - lo_, torch.zeros_like(v)), -lam * torch.where(fin_hi, hi_ - v, torch.zeros_like(v))).abs()
+        kkt = torch.stack([r_d.abs().amax(1) / sc_d, viol.amax(1) / sc_p, comp.amax(1) / fv], 1)
+        okm = chk["exitflag"] == 0
+        kkt_max = [float(t) for t in kkt[okm].amax(0).cpu()] if bool(okm.any()) else [float("nan")] * 3
     value = solved_total * args.steps / t_job                  # an instance counts only if its exit flag is 0
     flops_iter = 2.0 * nC * nV * nV + nV ** 3 / 3.0 + 4.0 * nC * nV + 2.0 * nV * nV
     flops_launch = flops_iter * mean_it * Bl
@@ -238,8 +259,8 @@ def main():
     if res["roofline"]["traffic"] is not None:
         res["roofline"]["traffic_unit"] = "bytes per launch (L2-miss side; Infinity-Cache hits are counted, so an upper bound on HBM bytes)"
 
-    res["cpu_baseline"] = None    # timed on rank 0 at N=1 only
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    res["cpu_baseline"] = None    # timed on rank 0 at N=1 only, with --full
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle as orc
         otr = orc.Track.load(os.path.join(ROOT, "fsae-mpc_amd", "tracks", "fsg2019.json"))
         avail = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
@@ -265,6 +286,23 @@ def main():
         print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(d, arrays):
+    """arrays: name -> per-instance array (first axis = instance), written as d/<name>.npy in float64 (exit flags and iteration
+    counts are exact there).  Above DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of instances is written from every array,
+    with its row ids as sample_rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in arrays.items()}
+    B = len(next(iter(arrays.values())))
+    per_row = sum(a.nbytes for a in arrays.values()) // max(1, B)
+    budget = DUMP_LIMIT_BYTES - 4096 * (len(arrays) + 1)     # room for the .npy headers
+    if per_row * B > budget:
+        rows = np.sort(np.random.default_rng(20190).choice(B, budget // (per_row + 8), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def dry_run(args, rank, world):

@@ -11,17 +11,17 @@ cd $R
 what=${1:-both}
 one() {   # tag, kernel substring, bench arguments...
   tag=$1; kern=$2; shift 2
-  python bench.py --steps 10 --warmup 2 "$@" > $O/bench_line_$tag.json 2> $O/bench_err_$tag.log
+  python bench.py --full --steps 10 --warmup 2 "$@" > $O/bench_line_$tag.json 2> $O/bench_err_$tag.log
   echo "bench $tag done"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktrace_$tag -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" > $O/bench_under_rocprof_$tag.json 2> $O/rocprof_err_$tag.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktrace_$tag -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline "$@" > $O/bench_under_rocprof_$tag.json 2> $O/rocprof_err_$tag.log
   echo "ktrace $tag done"
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_$tag -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> $O/pmc1_err_$tag.log
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_$tag -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> $O/pmc1_err_$tag.log
   echo "pmc fetch $tag done"
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_$tag -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> $O/pmc2_err_$tag.log
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_$tag -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> $O/pmc2_err_$tag.log
   echo "pmc write $tag done"
-  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma_$tag -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> $O/pmc3_err_$tag.log
+  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma_$tag -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> $O/pmc3_err_$tag.log
   echo "pmc mfma $tag done"
-  rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --output-format csv -d $O/pmc_wait_$tag -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> $O/pmc4_err_$tag.log
+  rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --output-format csv -d $O/pmc_wait_$tag -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> $O/pmc4_err_$tag.log
   echo "pmc wait $tag done"
   python tools/pmc_traffic.py $O/pmc_fetch_$tag $O/pmc_write_$tag $O/pmc_traffic_$tag.json $kern
   python tools/pmc_mfma.py $O/pmc_mfma_$tag $O/pmc_mfma_$tag.json $kern $O/pmc_wait_$tag

@@ -2,7 +2,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/meas_r3b; mkdir -p $O
 timeout -k 10 600 python tools/warm_start_ab.py 1024 60 > $O/warm_start_ab.json 2> $O/ws_err.log; echo "warm start rc=$?"
 for sb in 0 2; do FSAEMPC_SLACK_BORDER=$sb python bench.py --model kinematic --horizon 20 --batch 4096 --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_line_kinN20_B4096_policy$sb.json 2>> $O/bench_err.log; echo "kin20 policy $sb rc=$?"; done
-python bench.py --model kinematic --horizon 20 --batch 4096 --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_line_kinN20_B4096.json 2>> $O/bench_err.log
+python bench.py --full --model kinematic --horizon 20 --batch 4096 --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_line_kinN20_B4096.json 2>> $O/bench_err.log
 for sb in 0 1; do FSAEMPC_SLACK_BORDER=$sb python bench.py --model dynamic --horizon 60 --batch 4096 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_line_dynN60_B4096_policy$sb.json 2>> $O/bench_err.log; echo "dyn60 policy $sb rc=$?"; done
 timeout -k 10 500 python tools/cl_failures_check.py --model kinematic --cars 2048 --steps 200 --keep 24 --save $O/cl_fail_kin.npz > $O/cl_fail_kin.json 2> $O/clf_kin_err.log; echo "cl fail kin rc=$?"
 timeout -k 10 500 python tools/cl_failures_check.py --model dynamic --cars 2048 --steps 100 --keep 40 --save $O/cl_fail_dyn.npz > $O/cl_fail_dyn.json 2> $O/clf_dyn_err.log; echo "cl fail dyn rc=$?"
