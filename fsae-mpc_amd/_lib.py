@@ -16,6 +16,8 @@ EXPORTS = [
     "fsaempc_obtain_reference_batch_device", "fsaempc_reference_live_batch_device",
     "fsaempc_cl_pre_batch_device", "fsaempc_cl_plant_batch_device", "fsaempc_cl_accept_batch_device",
     "fsaempc_track_from_csv", "fsaempc_track_from_points", "fsaempc_track_free", "fsaempc_track_save", "fsaempc_track_load", "fsaempc_track_last_error",
+    "fsaempc_nlp_build_qp_batch_device", "fsaempc_sqp_default_opts", "fsaempc_sqp_workspace_bytes", "fsaempc_sqp_batch_device",
+    "fsaempc_sqp_get_timing",
 ]
 
 
@@ -38,6 +40,15 @@ class Spline(C.Structure):
 
 class LtvDesc(C.Structure):
     _fields_ = [("model", C.c_int), ("N", C.c_int), ("batch", C.c_int), ("dt", C.c_double), ("integrator", C.c_int)]
+
+
+class SqpOpts(C.Structure):
+    _fields_ = [("max_sweeps", C.c_int), ("trials", C.c_int), ("tol_step", C.c_double), ("tol_feas", C.c_double), ("armijo", C.c_double),
+                ("rho0", C.c_double), ("warm_start", C.c_int)]
+
+
+class SqpAux(C.Structure):
+    _fields_ = [("lambda_", C.c_void_p), ("qp_iter", C.c_void_p), ("step_norm", C.c_void_p), ("hard_viol", C.c_void_p), ("merit", C.c_void_p)]
 
 
 class TrackTable(C.Structure):
@@ -65,6 +76,7 @@ def lib():
         L.fsaempc_last_error.restype = C.c_char_p
         L.fsaempc_qp_workspace_bytes.restype = C.c_longlong
         L.fsaempc_ltv_workspace_bytes.restype = C.c_longlong
+        L.fsaempc_sqp_workspace_bytes.restype = C.c_longlong
         vp, ll = C.c_void_p, C.c_longlong
         L.fsaempc_qp_solve_batch_device.argtypes = [C.POINTER(QpDesc)] + [vp] * 7 + [C.POINTER(QpOpts)] + [vp] * 5 + [vp, ll, vp]
         L.fsaempc_qp_solve_batch_device_aux.argtypes = [C.POINTER(QpDesc)] + [vp] * 7 + [C.POINTER(QpOpts)] + [vp] * 5 + [C.POINTER(QpAux), vp, ll, vp]
@@ -72,6 +84,12 @@ def lib():
         L.fsaempc_ltv_build_qp_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline)] + [vp] * 4 + [vp] * 7 + [vp] * 3 + [vp]
         L.fsaempc_ltv_step_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline)] + [vp] * 4 + [C.POINTER(QpOpts)] + [vp] * 6 + [vp, ll, vp]
         L.fsaempc_ltv_step_batch_device_aux.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline)] + [vp] * 4 + [C.POINTER(QpOpts)] + [vp] * 6 + [C.POINTER(QpAux), vp, ll, vp]
+        L.fsaempc_nlp_build_qp_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline)] + [vp] * 3 + [vp] * 7 + [vp] * 3 + [vp]
+        L.fsaempc_sqp_default_opts.argtypes = [C.POINTER(SqpOpts)]
+        L.fsaempc_sqp_workspace_bytes.argtypes = [C.POINTER(LtvDesc)]
+        L.fsaempc_sqp_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline)] + [vp] * 3 + [C.POINTER(QpOpts), C.POINTER(SqpOpts)] + \
+            [vp] * 6 + [C.POINTER(SqpAux), vp, ll, vp]
+        L.fsaempc_sqp_get_timing.argtypes = [C.POINTER(C.c_double)] * 4
         L.fsaempc_obtain_reference_batch_device.argtypes = [vp, C.c_double, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, vp, vp]
         L.fsaempc_reference_live_batch_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, vp]
         L.fsaempc_cl_pre_batch_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(Spline), vp, vp, C.c_int, vp, vp, vp, vp]
@@ -91,6 +109,16 @@ def lib():
 def check(rc, what):
     if rc != 0:
         raise FsaempcError("%s failed (%d): %s" % (what, rc, lib().fsaempc_last_error().decode()))
+
+
+def sqp_default_opts(**kw):
+    o = SqpOpts()
+    lib().fsaempc_sqp_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError("unknown SQP option %r" % k)
+        setattr(o, k, v)
+    return o
 
 
 def default_opts(**kw):

@@ -15,6 +15,7 @@
 #include "ltv_build.h"
 #include "reference.h"
 #include "plant.h"
+#include "sqp.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -24,6 +25,8 @@ thread_local char g_err[512] = "";
 std::atomic<double*> g_dump{nullptr}; std::atomic<int> g_dump_stage{0};
 std::atomic<bool> g_timing{false}; hipEvent_t g_ev[3] = {nullptr, nullptr, nullptr};
 hipEvent_t g_evf[2] = {nullptr, nullptr};   // fused step: before the construction kernel, after the post-solve kernel
+hipEvent_t g_evs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // SQP sweep: compaction+gather | build | solve | line search
+double g_sqp_ms[4] = {0, 0, 0, 0};   // summed over the sweeps of the last SQP call: compaction + gather, build, solve, line search
 
 // roctx ranges around the launches of every phase (rocprofv3 --marker-trace shows them next to the kernel trace).  The roctx library is
 // looked up at run time: without it (or with FSAEMPC_ROCTX=0) the ranges are no-ops and the library has no dependency on it.
@@ -341,22 +344,42 @@ static int ltv_check(const fsaempc_ltv_desc* d, const fsaempc_spline* sp) {
   return 0;
 }
 
+static int ltv_integ(const fsaempc_ltv_desc* d) {
+  return d->integrator >= 0 ? d->integrator : (d->model == FSAEMPC_MODEL_KINEMATIC ? FSAEMPC_INT_RK2 : FSAEMPC_INT_RK4);   // ltvmpc_*.m:38
+}
+
+static int build_qp(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
+                    const double* u_lin, double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                    double* pred, double* Bt, double* qconst, void* stream, bool exact) {
+  if (desc->batch == 0) return 0;
+  LtvParams P; memset(&P, 0, sizeof(P));
+  P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.dt = desc->dt;
+  P.integ = ltv_integ(desc);
+  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP;
+  P.x0 = x0; P.x_ref = x_ref; P.x_lin = x_lin; P.u_lin = u_lin;
+  P.H = H; P.g = g; P.A = A; P.lb = lb; P.ub = ub; P.lbA = lbA; P.ubA = ubA; P.pred = pred; P.Bt = Bt; P.qconst = qconst;
+  hipError_t e = ltv_build_launch(P, desc->batch, (hipStream_t)stream, exact);
+  if (e != hipSuccess) return hipfail(e, "ltv_build_launch");
+  return 0;
+}
+
 int fsaempc_ltv_build_qp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
                                       const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
                                       double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
                                       double* pred, double* Bt, double* qconst, void* stream) {
   int rc = ltv_check(desc, sp); if (rc) return rc;
   if (!x0 || !x_ref || !x_lin || !u_lin || !H || !g || !A || !lb || !ub || !lbA || !ubA || !Bt) return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
-  if (desc->batch == 0) return 0;
-  LtvParams P; memset(&P, 0, sizeof(P));
-  P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.dt = desc->dt;
-  P.integ = desc->integrator >= 0 ? desc->integrator : (desc->model == FSAEMPC_MODEL_KINEMATIC ? FSAEMPC_INT_RK2 : FSAEMPC_INT_RK4);   // ltvmpc_*.m:38
-  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP;
-  P.x0 = x0; P.x_ref = x_ref; P.x_lin = x_lin; P.u_lin = u_lin;
-  P.H = H; P.g = g; P.A = A; P.lb = lb; P.ub = ub; P.lbA = lbA; P.ubA = ubA; P.pred = pred; P.Bt = Bt; P.qconst = qconst;
-  hipError_t e = ltv_build_launch(P, desc->batch, (hipStream_t)stream);
-  if (e != hipSuccess) return hipfail(e, "ltv_build_launch");
-  return 0;
+  return build_qp(desc, sp, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream, false);
+}
+
+int fsaempc_nlp_build_qp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                                      const double* x0, const double* x_ref, const double* u_lin,
+                                      double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                      double* pred, double* Bt, double* qconst, void* stream) {
+  int rc = ltv_check(desc, sp); if (rc) return rc;
+  if (ltv_build_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N, 256, true) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
+  if (!x0 || !x_ref || !u_lin || !H || !g || !A || !lb || !ub || !lbA || !ubA || !Bt) return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
+  return build_qp(desc, sp, x0, x_ref, nullptr, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream, true);
 }
 
 struct LtvCarve { size_t H, g, A, lb, ub, lbA, ubA, pred, Bt, qc, z, qpws, total; };
@@ -417,6 +440,114 @@ int fsaempc_ltv_step_batch_device_aux(const fsaempc_ltv_desc* desc, const fsaemp
                         u_opt, x_opt, slack, fval, (hipStream_t)stream); }
   if (e != hipSuccess) return hipfail(e, "ltv_post_launch");
   if (timing) { e = hipEventRecord(g_evf[1], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
+  return 0;
+}
+
+/* ---- batched SQP of the nonlinear MPC step ---- */
+void fsaempc_sqp_default_opts(fsaempc_sqp_opts* o) {
+  if (!o) return;
+  o->max_sweeps = 20; o->trials = 8; o->tol_step = 1e-6; o->tol_feas = 1e-6; o->armijo = 1e-4; o->rho0 = 1.0; o->warm_start = 1;
+}
+
+struct SqpCarve { size_t idx, cnt, gx0, gxr, gu, xinit, H, g, A, lb, ub, lbA, ubA, pred, Bt, qc, z, qf, qflag, qit, lam, rho, J, viol, vmax, qpws, total; };
+static void sqp_carve(const fsaempc_ltv_desc* d, SqpCarve* c) {
+  const size_t B = d->batch > 0 ? d->batch : 1, nx = fsaempc_ltv_nx(d->model), N = d->N;
+  const size_t nV = fsaempc_ltv_nV(d->model, d->N), nC = fsaempc_ltv_nC(d->model, d->N), R = nx * N;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = align64(off + bytes); return o; };
+  const size_t D = sizeof(double), I = sizeof(int);
+  c->idx = take(B * I); c->cnt = take(I);
+  c->gx0 = take(B * nx * D); c->gxr = take(B * R * D); c->gu = take(B * 2 * N * D); c->xinit = take(B * nV * D);
+  c->H = take(B * nV * nV * D); c->g = take(B * nV * D); c->A = take(B * nC * nV * D); c->lb = take(B * nV * D); c->ub = take(B * nV * D);
+  c->lbA = take(B * nC * D); c->ubA = take(B * nC * D); c->pred = take(B * R * D); c->Bt = take(B * R * nV * D); c->qc = take(B * D);
+  c->z = take(B * nV * D); c->qf = take(B * D); c->qflag = take(B * I); c->qit = take(B * I); c->lam = take(B * (nV + nC) * D);
+  c->rho = take(B * D); c->J = take(B * D); c->viol = take(B * D); c->vmax = take(B * D);
+  off = (off + 255) & ~(size_t)255;
+  c->qpws = off;
+  fsaempc_qp_desc q{(int)nV, (int)nC, (int)B, 0};
+  long long w = fsaempc_qp_workspace_bytes(&q);
+  c->total = off + (w > 0 ? (size_t)w : 0);
+}
+
+long long fsaempc_sqp_workspace_bytes(const fsaempc_ltv_desc* desc) {
+  if (!desc || desc->N <= 0 || desc->batch < 0) return FSAEMPC_ERR_ARG;
+  if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return FSAEMPC_ERR_DIM;
+  SqpCarve c; sqp_carve(desc, &c);
+  return (long long)c.total;
+}
+
+int fsaempc_sqp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                             const double* x0, const double* x_ref, const double* u_init,
+                             const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
+                             double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
+                             const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
+  int rc = ltv_check(desc, sp); if (rc) return rc;
+  if (!x0 || !x_ref || !u_init || !u_opt || !x_opt || !slack || !fval || !status || !sweeps || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
+  if (ltv_build_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N, 256, true) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
+  fsaempc_sqp_opts o; if (sqp_opts) o = *sqp_opts; else fsaempc_sqp_default_opts(&o);
+  if (o.max_sweeps < 1 || o.trials < 1 || o.trials > 64 || !(o.tol_step >= 0) || !(o.tol_feas >= 0) || !(o.armijo >= 0) || !(o.rho0 >= 0))
+    return fail(FSAEMPC_ERR_ARG, "bad SQP options (max_sweeps >= 1, 1 <= trials <= 64, tolerances / armijo / rho0 >= 0)");
+  if (desc->batch == 0) return 0;
+  SqpCarve c; sqp_carve(desc, &c);
+  if ((long long)c.total > workspace_bytes) return fail(FSAEMPC_ERR_WORKSPACE, "workspace too small");
+  char* w = (char*)workspace;
+  auto D = [&](size_t off) { return (double*)(w + off); };
+  auto Iw = [&](size_t off) { return (int*)(w + off); };
+  hipStream_t st = (hipStream_t)stream;
+  const int nx = fsaempc_ltv_nx(desc->model), N = desc->N, nV = fsaempc_ltv_nV(desc->model, N), nC = fsaempc_ltv_nC(desc->model, N);
+  SqpParams P; memset(&P, 0, sizeof(P));
+  P.nx = nx; P.N = N; P.integ = ltv_integ(desc); P.B = desc->batch; P.dt = desc->dt;
+  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP;
+  P.x0 = x0; P.x_ref = x_ref; P.u = u_opt; P.x = x_opt; P.s = slack; P.fval = fval; P.status = status; P.sweeps = sweeps;
+  P.rho = D(c.rho); P.J = D(c.J); P.viol = D(c.viol); P.vmax = D(c.vmax);
+  if (aux) { P.lambda_out = aux->lambda; P.qp_iter = aux->qp_iter; P.step_norm = aux->step_norm; P.hard_viol = aux->hard_viol; P.merit = aux->merit; }
+  P.max_sweeps = o.max_sweeps; P.trials = o.trials; P.tol_step = o.tol_step; P.tol_feas = o.tol_feas; P.armijo = o.armijo; P.rho0 = o.rho0;
+  Range whole("fsaempc.sqp");
+  const bool timing = g_timing.load();
+  for (double& v : g_sqp_ms) v = 0;
+  hipError_t e = sqp_init_launch(P, u_init, st);
+  if (e != hipSuccess) return hipfail(e, "sqp_init_launch");
+  for (int sweep = 0; sweep < o.max_sweeps; ++sweep) {
+    if (timing) { e = hipEventRecord(g_evs[0], st); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
+    int cnt = 0;
+    { Range r("fsaempc.sqp.compact");
+      e = sqp_compact_launch(status, desc->batch, Iw(c.idx), Iw(c.cnt), st);
+      if (e == hipSuccess) e = hipMemcpyAsync(&cnt, Iw(c.cnt), sizeof(int), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st); }   // the one read of the sweep
+    if (e != hipSuccess) return hipfail(e, "sqp compaction");
+    if (cnt == 0) break;
+    double* xinit = o.warm_start ? D(c.xinit) : nullptr;
+    e = sqp_gather_launch(P, Iw(c.idx), cnt, D(c.gx0), D(c.gxr), D(c.gu), xinit, nV, st);
+    if (e != hipSuccess) return hipfail(e, "sqp_gather_launch");
+    if (timing) { e = hipEventRecord(g_evs[1], st); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
+    fsaempc_ltv_desc sub = *desc; sub.batch = cnt;
+    { Range r("fsaempc.sqp.build");
+      rc = build_qp(&sub, sp, D(c.gx0), D(c.gxr), nullptr, D(c.gu), D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA),
+                    D(c.pred), D(c.Bt), D(c.qc), stream, true); }
+    if (rc) return rc;
+    if (timing) { e = hipEventRecord(g_evs[2], st); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
+    fsaempc_qp_desc q{nV, nC, cnt, 0};
+    fsaempc_qp_aux qa{nullptr, nullptr, xinit, nullptr};
+    rc = fsaempc_qp_solve_batch_device_aux(&q, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA), qp_opts, D(c.z), D(c.qf),
+                                           Iw(c.qflag), Iw(c.qit), D(c.lam), &qa, w + c.qpws, (long long)(c.total - c.qpws), stream);
+    if (rc) return rc;
+    if (timing) { e = hipEventRecord(g_evs[3], st); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
+    { Range r("fsaempc.sqp.linesearch");
+      e = sqp_linesearch_launch(P, Iw(c.idx), cnt, sweep, D(c.z), D(c.qf), D(c.qc), Iw(c.qflag), Iw(c.qit), D(c.lam), st); }
+    if (e != hipSuccess) return hipfail(e, "sqp_linesearch_launch");
+    if (timing) {
+      e = hipEventRecord(g_evs[4], st); if (e == hipSuccess) e = hipEventSynchronize(g_evs[4]);
+      if (e != hipSuccess) return hipfail(e, "hipEventRecord");
+      for (int k = 0; k < 4; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, g_evs[k], g_evs[k + 1]) == hipSuccess) g_sqp_ms[k] += ms; }
+    }
+  }
+  return 0;
+}
+
+int fsaempc_sqp_get_timing(double* build_ms, double* solve_ms, double* linesearch_ms, double* compact_ms) {
+  if (!build_ms || !solve_ms || !linesearch_ms || !compact_ms) return fail(FSAEMPC_ERR_ARG, "null argument");
+  *compact_ms = g_sqp_ms[0]; *build_ms = g_sqp_ms[1]; *solve_ms = g_sqp_ms[2]; *linesearch_ms = g_sqp_ms[3];
   return 0;
 }
 
@@ -487,6 +618,7 @@ int fsaempc_qp_set_timing(int enable) {
   if (enable && !g_ev[0]) {
     for (int i = 0; i < 3; ++i) { hipError_t e = hipEventCreate(&g_ev[i]); if (e != hipSuccess) return hipfail(e, "hipEventCreate"); }
     for (int i = 0; i < 2; ++i) { hipError_t e = hipEventCreate(&g_evf[i]); if (e != hipSuccess) return hipfail(e, "hipEventCreate"); }
+    for (int i = 0; i < 5; ++i) { hipError_t e = hipEventCreate(&g_evs[i]); if (e != hipSuccess) return hipfail(e, "hipEventCreate"); }
   }
   g_timing.store(enable != 0);
   return 0;

@@ -12,7 +12,8 @@ struct LtvParams {
   double *pred, *Bt, *qconst;   // Bt is required (internal operand); pred/qconst optional
 };
 
-hipError_t ltv_build_launch(const LtvParams& P, int batch, hipStream_t st);
+// exact = false: the LTV build of the reference; true: the exact build of the NLP at u_lin (x_lin is not read)
+hipError_t ltv_build_launch(const LtvParams& P, int batch, hipStream_t st, bool exact = false);
 hipError_t ltv_post_launch(int nx, int N, int ns, int batch, const double* z, const double* pred, const double* Bt,
                            const double* qconst, double* u_opt, double* x_opt, double* slack, double* fval, hipStream_t st);
-size_t ltv_build_lds_bytes(int nx, int N, int threads);
+size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact = false);

@@ -15,54 +15,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "ltv_build.h"
+#include "nlp_model.h"
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
-typedef double v4d __attribute__((ext_vector_type(4)));
-constexpr double LR = 0.6183, LF = 0.8672;
-constexpr double VM = 280, VI = 200, GRAV = 9.81;
-constexpr double PB = 12.56, PC = 1.38, PD = 1.60, PE = -0.58;
-
-struct Spl { int M; double dl; const double* xP; const double* yP; };
-
-DEVINL void seg_lookup(int M, double dl, double t, int& seg, double& tau) {
-  const double per = dl * (double)M;
-  double r = t - floor(t / per) * per;  // MATLAB mod()
-  if (r < 0) r += per;
-  if (r >= per) r -= per;
-  int i = 0;
-  if (r >= 0 && r < per) i = (int)floor(r / dl);   // a non-finite arc length (a car whose state blew up) must not index the table
-  if (i >= M) i = M - 1;
-  if (i < 0) i = 0;
-  seg = i; tau = r / dl - (double)i;
-}
-DEVINL double kappa(const Spl& sp, double s) {
-  int i; double u;
-  seg_lookup(sp.M, sp.dl, s, i, u);
-  const int M = sp.M;
-  const double x0 = sp.xP[i], x1 = sp.xP[i + M], x2 = sp.xP[i + 2 * M], x3 = sp.xP[i + 3 * M];
-  const double y0 = sp.yP[i], y1 = sp.yP[i + M], y2 = sp.yP[i + 2 * M], y3 = sp.yP[i + 3 * M];
-  const double b0 = -3 * (1 - u) * (1 - u), b1 = 3 * (3 * u * u - 4 * u + 1), b2 = 3 * (2 * u - 3 * u * u), b3 = 3 * u * u;
-  const double c0 = 6 * (1 - u), c1 = 6 * (3 * u - 2), c2 = 6 * (1 - 3 * u), c3 = 6 * u;
-  const double Xd = (b0 * x0 + b1 * x1 + b2 * x2 + b3 * x3) / sp.dl, Yd = (b0 * y0 + b1 * y1 + b2 * y2 + b3 * y3) / sp.dl;
-  const double Xdd = (c0 * x0 + c1 * x1 + c2 * x2 + c3 * x3) / (sp.dl * sp.dl), Ydd = (c0 * y0 + c1 * y1 + c2 * y2 + c3 * y3) / (sp.dl * sp.dl);
-  return (Xd * Ydd - Xdd * Yd) / pow(Xd * Xd + Yd * Yd, 1.5);
-}
-
-// ---- kinematic model (f_curv_kin.m:13-29, A_curv_kin.m:15-55) ----
-DEVINL void f_kin(const double* x, const double* u, const Spl& sp, double* f) {
-  const double lr_ratio = LR / (LR + LF);
-  const double k = kappa(sp, x[0]);
-  const double beta = atan(lr_ratio * tan(x[4]));
-  const double s_mb = sin(x[2] + beta), c_mb = cos(x[2] + beta);
-  const double denom_nk = 1.0 / (1.0 - x[1] * k);
-  f[0] = x[3] * c_mb * denom_nk;
-  f[1] = x[3] * s_mb;
-  f[2] = x[3] * sin(beta) / LR - x[3] * c_mb * denom_nk * k;
-  f[3] = u[0];
-  f[4] = u[1];
-}
 DEVINL void A_kin(const double* x, const Spl& sp, double* A) {  // 5x5 column-major
   const double lr_ratio = LR / (LR + LF);
   const double k = kappa(sp, x[0]);
@@ -83,26 +39,6 @@ DEVINL void A_kin(const double* x, const Spl& sp, double* A) {  // 5x5 column-ma
   A[2 + 4 * 5] = x[3] * cos(beta) * beta_d / LR - s_delta * k;
 }
 
-// ---- dynamic model (f_curv_dyn.m:13-62, A_curv_dyn.m:15-106) ----
-DEVINL void f_dyn(const double* x, const double* u, const Spl& sp, double* f) {
-  const double n = x[1], mu = x[2], x_d = x[3], y_d = x[4], th_d = x[5], delta = x[6];
-  const double Fx = u[0] * VM;
-  const double x_d_hat = x_d + 5 * exp(-x_d / 5);
-  const double k = kappa(sp, x[0]);
-  const double denom_nk = 1.0 / (1.0 - n * k);
-  const double alpha_f = delta - atan((y_d + LF * th_d) / x_d_hat);
-  const double alpha_r = -atan((y_d - LR * th_d) / x_d_hat);
-  const double Fzf = VM * GRAV * LR / (LR + LF), Fzr = VM * GRAV * LF / (LR + LF);
-  const double Fcf = Fzf * PD * sin(PC * atan(PB * alpha_f - PE * (PB * alpha_f - atan(PB * alpha_f))));
-  const double Fcr = Fzr * PD * sin(PC * atan(PB * alpha_r - PE * (PB * alpha_r - atan(PB * alpha_r))));
-  f[0] = (x_d * cos(mu) - y_d * sin(mu)) * denom_nk;
-  f[1] = x_d * sin(mu) + y_d * cos(mu);
-  f[2] = th_d - (x_d * cos(mu) - y_d * sin(mu)) * denom_nk * k;
-  f[3] = (Fx - Fcf * sin(delta) + VM * y_d * th_d) / VM;
-  f[4] = (Fcr + Fcf * cos(delta) - VM * x_d * th_d) / VM;
-  f[5] = (LF * Fcf * cos(delta) - LR * Fcr) / VI;
-  f[6] = u[1];
-}
 // byp = {Fcr, Fcr_d, vr, denom_vr2, x_d_hat, x_d_hat_d, vf, denom_vf2}; A may be null
 DEVINL void A_dyn(const double* x, const Spl& sp, double* A, double* byp) {
   const double n = x[1], mu = x[2], x_d = x[3], y_d = x[4], th_d = x[5], delta = x[6];
@@ -154,9 +90,6 @@ template <int NX> DEVINL void mmul(const double* A, const double* B, double* C, 
       for (int p = 0; p < NX; ++p) s += A[i + p * NX] * B[p + j * NX];
       C[i + j * NX] = s;
     }
-}
-template <int NX> DEVINL void model_f(const double* x, const double* u, const Spl& sp, double* f) {
-  if (NX == 5) f_kin(x, u, sp, f); else f_dyn(x, u, sp, f);
 }
 template <int NX> DEVINL void model_A(const double* x, const Spl& sp, double* A) {
   if (NX == 5) A_kin(x, sp, A); else A_dyn(x, sp, A, nullptr);
@@ -239,8 +172,26 @@ template <int NX> DEVINL void linearise_step(const double* xi, const double* ui,
   for (int j = 0; j < NX * 2; ++j) Bd[j] = Bi[j] * dt;
 }
 
+// Exact linearisation of one step of the NLP's rollout: Ad = dPsi/dx, Bd = dPsi/du at (xi, ui), one dual-number pass of psi_step per
+// column (true df/dx including kappa'(s), classical RK4 stage derivatives).
+template <int NX> DEVINL void linearise_exact(const double* xi, const double* ui, const Spl& sp, double dt, int integ, double* Ad, double* Bd) {
+  for (int c = 0; c < NX + 2; ++c) {
+    Dl xd[NX], ud[2], xn[NX];
+    for (int j = 0; j < NX; ++j) xd[j] = Dl(xi[j], j == c ? 1.0 : 0.0);
+    for (int j = 0; j < 2; ++j) ud[j] = Dl(ui[j], NX + j == c ? 1.0 : 0.0);
+    psi_step<NX>(xd, ud, sp, dt, integ, xn);
+    double* col = c < NX ? Ad + c * NX : Bd + (c - NX) * NX;
+    for (int r = 0; r < NX; ++r) col[r] = xn[r].d;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
-template <int NX> __global__ __launch_bounds__(256) void ltv_build_kernel(LtvParams P) {
+// EXACT = false: the LTV build of the reference (quirks C-1, C-3, C-4/C-5, C-8 kept; bitwise pinned by the parity tests).
+// EXACT = true: the QP of the NLP of DESIGN.md "Nonlinear MPC: batched SQP" at u = u_lin: x_lin is not read, the states are the
+// rollout x_k = Psi(x_{k-1}, u_k) (x_0 = x0), step k is linearised exactly at (x_{k-1}, u_k), Phi(i,i) = Bd_i, every constraint row
+// is linearised at the rollout state it constrains, and pred receives the rollout (the affine offset of the QP, rollout - Phi u_lin,
+// stays internal).
+template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_kernel(LtvParams P) {
   constexpr int NN = NX * NX, NS = (NX == 5) ? 1 : 4, RPK = (NX == 5) ? 6 : 20;  // rows per step
   const int b = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
   const int N = P.N, R = NX * N, nV = 2 * N + NS, nC = RPK * N;
@@ -267,15 +218,37 @@ template <int NX> __global__ __launch_bounds__(256) void ltv_build_kernel(LtvPar
   double* red = cc + (size_t)N * CW;     // reduction scratch (nth)
   double* ell = red + nth;               // 24: dac[12], dal[12] of the inscribed 12-gon (dynamic_tyre_linearise_constraints.m:33-39)
   double* colst = ell + 24;              // one column of Bt (R doubles) per wavefront: stage of step 4c
+  double* xs = colst + (size_t)(nth >> 6) * R;   // EXACT: rollout x_0 .. x_N ((N + 1) * NX)
 
   if (tid < 12) {
     const int j = tid;
     const double th0 = 2 * M_PI * (double)j / 12, th1 = (j + 1 == 12) ? 2 * M_PI : 2 * M_PI * (double)(j + 1) / 12;
     ell[j] = 9.163 * sin(th1) - 9.163 * sin(th0); ell[12 + j] = 10.0 * cos(th1) - 10.0 * cos(th0);
   }
+  if constexpr (EXACT) {
+    if (tid == 0) {
+      for (int j = 0; j < NX; ++j) xs[j] = x0[j];
+      for (int k = 0; k < N; ++k) psi_step<NX>(xs + (size_t)k * NX, u_lin + (size_t)k * 2, sp, dt, P.integ, xs + (size_t)(k + 1) * NX);
+    }
+    __syncthreads();
+  }
   // ---- 1. linearise every step (one thread per step) ----
-  for (int k = tid; k < N; k += nth)
-    linearise_step<NX>(x_lin + (size_t)k * NX, u_lin + (size_t)k * 2, sp, dt, P.integ, Ad + (size_t)k * NN, Bd + (size_t)k * NX * 2, dd + (size_t)k * NX);
+  for (int k = tid; k < N; k += nth) {
+    if constexpr (EXACT) {
+      const double* xi = xs + (size_t)k * NX;
+      const double* ui = u_lin + (size_t)k * 2;
+      double* a = Ad + (size_t)k * NN; double* bd = Bd + (size_t)k * NX * 2; double* d = dd + (size_t)k * NX;
+      linearise_exact<NX>(xi, ui, sp, dt, P.integ, a, bd);
+      for (int r = 0; r < NX; ++r) {     // dd_k = x_k - Ad_k x_{k-1} - Bd_k u_k: the recursion of step 2 reproduces the rollout at u_lin
+        double v = xi[NX + r];
+        for (int c = 0; c < NX; ++c) v -= a[r + c * NX] * xi[c];
+        for (int c = 0; c < 2; ++c) v -= bd[r + c * NX] * ui[c];
+        d[r] = v;
+      }
+    } else {
+      linearise_step<NX>(x_lin + (size_t)k * NX, u_lin + (size_t)k * 2, sp, dt, P.integ, Ad + (size_t)k * NN, Bd + (size_t)k * NX * 2, dd + (size_t)k * NX);
+    }
+  }
   // zero Bt while the linearisation runs
   for (size_t i = tid; i < (size_t)R * nV; i += nth) Bt[i] = 0.0;
   __syncthreads();
@@ -298,7 +271,8 @@ template <int NX> __global__ __launch_bounds__(256) void ltv_build_kernel(LtvPar
   for (int w = tid; w < 2 * N; w += nth) {
     const int i = w >> 1, col = w & 1;
     double cur[NX], nxt[NX];
-    for (int r = 0; r < NX; ++r) cur[r] = Bd[r + col * NX];
+    const double* bdi = EXACT ? Bd + (size_t)i * NX * 2 : Bd;
+    for (int r = 0; r < NX; ++r) cur[r] = bdi[r + col * NX];
     double* dst = Bt + (size_t)w * R;
     for (int r = 0; r < NX; ++r) dst[i * NX + r] = cur[r];
     for (int j = i + 1; j < N; ++j) {
@@ -313,7 +287,7 @@ template <int NX> __global__ __launch_bounds__(256) void ltv_build_kernel(LtvPar
   }
   // ---- 4a. per-step constraint coefficients ----
   for (int k = tid; k < N; k += nth) {
-    const double* xl = x_lin + (size_t)k * NX;
+    const double* xl = EXACT ? xs + (size_t)(k + 1) * NX : x_lin + (size_t)k * NX;   // (default: pairing quirk C-8)
     double* ck = cc + (size_t)k * CW;
     if (NX == 5) {
       // kinematic_tyre_linearise_constraints.m:18-32 ; g = v^2 delta/(lr+lf)
@@ -347,7 +321,7 @@ template <int NX> __global__ __launch_bounds__(256) void ltv_build_kernel(LtvPar
     lbA[N + k] = -0.4 - cd;       ubA[N + k] = 0.4 - cd;
     lbA[2 * N + k] = -0.75 - cn;  ubA[2 * N + k] = 1e10;    // *_state_constraints.m:38-39
     lbA[3 * N + k] = -1e10;       ubA[3 * N + k] = 0.75 - cn;
-    const double* xl = x_lin + (size_t)k * NX;
+    const double* xl = EXACT ? xs + (size_t)(k + 1) * NX : x_lin + (size_t)k * NX;
     const double* ck = cc + (size_t)k * CW;
     if (NX == 5) {
       const double cst = ck[2] + ck[0] * (aff[k * NX + 3] - xl[3]) + ck[1] * (aff[k * NX + 4] - xl[4]);
@@ -497,7 +471,7 @@ template <int NX> __global__ __launch_bounds__(256) void ltv_build_kernel(LtvPar
     double s = 0; for (int i = 0; i < nth; ++i) s += red[i];
     if (P.qconst) P.qconst[b] = s;
   }
-  if (P.pred) for (int i = tid; i < R; i += nth) P.pred[(size_t)b * R + i] = aff[i];
+  if (P.pred) for (int i = tid; i < R; i += nth) P.pred[(size_t)b * R + i] = EXACT ? xs[NX + i] : aff[i];
 }
 
 // post-solve: x_opt = aff + Bt z ; u_opt = z(1:2N) ; slack ; fval += const   (ltvmpc_*.m:57-60)
@@ -519,25 +493,25 @@ __global__ void ltv_post_kernel(int nx, int N, int ns, const double* z, const do
 
 }  // namespace
 
-size_t ltv_build_lds_bytes(int nx, int N, int threads) {
+size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact) {
   const int CW = (nx == 5) ? 3 : 16;
   return ((size_t)N * nx * nx + (size_t)N * nx * 2 + (size_t)N * nx + (size_t)nx * N + (size_t)N * CW + threads + 24 +
-          (size_t)(threads / 64) * nx * N) * sizeof(double);   // last term: the per-wavefront column stage of step 4c
+          (size_t)(threads / 64) * nx * N +    // the per-wavefront column stage of step 4c
+          (exact ? (size_t)(N + 1) * nx : 0)) * sizeof(double);   // the rollout of the NLP build
 }
 
-hipError_t ltv_build_launch(const LtvParams& P, int batch, hipStream_t st) {
+template <int NX, bool EXACT> static hipError_t launch_build(const LtvParams& P, int batch, hipStream_t st) {
   const int threads = 256;
-  const size_t lds = ltv_build_lds_bytes(P.nx, P.N, threads);
-  if (P.nx == 5) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ltv_build_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ltv_build_kernel<5>, dim3(batch), dim3(threads), lds, st, P);
-  } else {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ltv_build_kernel<7>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ltv_build_kernel<7>, dim3(batch), dim3(threads), lds, st, P);
-  }
+  const size_t lds = ltv_build_lds_bytes(NX, P.N, threads, EXACT);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ltv_build_kernel<NX, EXACT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((ltv_build_kernel<NX, EXACT>), dim3(batch), dim3(threads), lds, st, P);
   return hipGetLastError();
+}
+
+hipError_t ltv_build_launch(const LtvParams& P, int batch, hipStream_t st, bool exact) {
+  if (exact) return P.nx == 5 ? launch_build<5, true>(P, batch, st) : launch_build<7, true>(P, batch, st);
+  return P.nx == 5 ? launch_build<5, false>(P, batch, st) : launch_build<7, false>(P, batch, st);
 }
 
 hipError_t ltv_post_launch(int nx, int N, int ns, int batch, const double* z, const double* pred, const double* Bt, const double* qconst,

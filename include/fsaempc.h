@@ -215,6 +215,67 @@ int fsaempc_ltv_step_batch_device_aux(const fsaempc_ltv_desc* desc, const fsaemp
                                       const fsaempc_qp_aux* aux,
                                       void* workspace, long long workspace_bytes, void* stream);
 
+/*
+ * Exact-linearisation build of the nonlinear MPC step (the NLP of DESIGN.md "Nonlinear MPC: batched SQP") at the inputs u_lin:
+ * the states are the rollout x_k = Psi(x_{k-1}, u_k) of the integrator of desc->integrator (x_0 = x0; RK4 is the classical
+ * one), step k is linearised exactly at (x_{k-1}, u_k) (Phi(i,i) = Bd_i, true df/dx including the curvature derivative of the
+ * track table, true RK4 stage derivatives), and every constraint row is linearised at the rollout state it constrains.
+ * Same outputs as fsaempc_ltv_build_qp_batch_device, with one difference: pred receives the rollout x_1..x_N itself.  The QP's
+ * variables are still u (not a step), so its affine state offset is pred - Bt(:, 1:2N) u_lin (g = 2 Bt' Qbar (that offset - x_ref)).
+ * The reference quirks the LTV build keeps are not applied here.
+ */
+int fsaempc_nlp_build_qp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                                      const double* x0, const double* x_ref, const double* u_lin,
+                                      double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                      double* pred, double* Bt, double* qconst, void* stream);
+
+/* ---- batched SQP of the nonlinear MPC step --------------------------------------
+ * Gauss-Newton SQP with exact linearisation: each sweep builds the exact QP at the current inputs, solves it, and takes the
+ * largest step 2^-i (i < trials) that satisfies Armijo on the l1 merit J + rho * |hard violation|_1 (slacks reset to the least
+ * value their soft rows need at each trial point); rho >= 1.1 |lambda of the hard rows|_inf.  Instances leave the batch when
+ * they are done; each sweep works on a dense sub-batch of the ones still running. */
+typedef struct {
+  int max_sweeps;    /* sweep limit (default 20) */
+  int trials;        /* step lengths 2^0 .. 2^-(trials-1) tried at once, 1..64 (default 8) */
+  double tol_step;   /* converged: |u_QP - u|_inf <= tol_step (1 + |u|_inf) ... (default 1e-6) */
+  double tol_feas;   /* ... and max hard violation <= tol_feas (default 1e-6) */
+  double armijo;     /* eta of phi(a) <= phi(0) - eta a pred (default 1e-4) */
+  double rho0;       /* initial penalty (default 1) */
+  int warm_start;    /* 1 (default): the QP of each sweep starts at (u, s) of the current iterate (fsaempc_qp_aux.x_init) */
+} fsaempc_sqp_opts;
+
+void fsaempc_sqp_default_opts(fsaempc_sqp_opts* o);
+
+/* Optional per-instance outputs of fsaempc_sqp_batch_device (device arrays over the whole batch; each may be NULL). */
+typedef struct {
+  double* lambda;     /* nV + nC: multipliers of the instance's last QP (layout of fsaempc_qp_solve_batch_device) */
+  int* qp_iter;       /* interior-point iterations summed over the instance's QPs */
+  double* step_norm;  /* |u_QP - u|_inf of the last sweep */
+  double* hard_viol;  /* max hard-row violation of the returned point */
+  double* merit;      /* max_sweeps: merit after each sweep (NaN for sweeps not run) */
+} fsaempc_sqp_aux;
+
+/* Bytes of device workspace fsaempc_sqp_batch_device needs (QP tensors of the whole batch + solver workspace + SQP state). */
+long long fsaempc_sqp_workspace_bytes(const fsaempc_ltv_desc* desc);
+
+/*
+ * Solves the nonlinear MPC step of `batch` instances from u_init (2N per instance; x0 nx, x_ref nx*N as for the LTV step).
+ * Outputs per instance: u_opt 2N, x_opt nx*N (the rollout of u_opt), slack ns, fval (NLP objective incl. the constant),
+ * status, sweeps (QPs solved).  status: 0 converged, 1 sweep limit, 2 no step accepted, -1 / -2 the QP of the last sweep failed
+ * with that flag (every other failing flag is reported as -1); for every status but 0 the outputs are the last accepted iterate.
+ * Instances never influence each other.  qp_opts / sqp_opts may be NULL (defaults).  The call blocks once per sweep (it reads
+ * the number of instances still running); all other work is queued on `stream`.
+ */
+int fsaempc_sqp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                             const double* x0, const double* x_ref, const double* u_init,
+                             const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
+                             double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
+                             const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream);
+
+/* Phase times of the last fsaempc_sqp_batch_device call, summed over its sweeps, by HIP events (switch: fsaempc_qp_set_timing;
+ * with it on, the call also synchronises after every sweep).  compact = compaction + gather. */
+int fsaempc_sqp_get_timing(double* build_ms, double* solve_ms, double* linesearch_ms, double* compact_ms);
+
 /* ---- reference trajectories ---------------------------------------------------------------- */
 
 /*
