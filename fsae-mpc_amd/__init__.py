@@ -7,6 +7,8 @@ from .closed_loop import ClosedLoop, monte_carlo, monte_carlo_carts
 from .ltvmpc import LtvBatch, dims, ltvmpc_dynamic_curvilinear, ltvmpc_kinetmatic_curvilinear
 from .qpoases import qp_solve_batch_device, qpOASES, qpOASES_sequence
 from .sqp import SqpBatch, sqp_timing
+from .sensitivity import (LtvStepFunction, QpFunction, feedback_gain, ltv_step_affine_maps, ltv_step_diff, ltv_step_lambda,
+                          ltv_step_vjp, qp_vjp)
 from .reference import obtain_reference, obtain_reference_batch_device, reference_live_batch_device
 from .synthetic import DYNAMIC, KINEMATIC, instances, reference_live
 from .tracks import Track
@@ -14,4 +16,5 @@ from .tracks import Track
 __all__ = ["FsaempcError", "default_opts", "lib", "LtvBatch", "dims", "ltvmpc_dynamic_curvilinear",
            "ltvmpc_kinetmatic_curvilinear", "qp_solve_batch_device", "qpOASES", "qpOASES_sequence", "DYNAMIC", "KINEMATIC",
            "instances", "reference_live", "Track", "obtain_reference", "obtain_reference_batch_device",
-           "reference_live_batch_device", "ClosedLoop", "monte_carlo", "monte_carlo_carts", "SqpBatch", "sqp_timing"]
+           "reference_live_batch_device", "ClosedLoop", "monte_carlo", "monte_carlo_carts", "SqpBatch", "sqp_timing", "QpFunction", "qp_vjp",
+           "LtvStepFunction", "feedback_gain", "ltv_step_affine_maps", "ltv_step_diff", "ltv_step_lambda", "ltv_step_vjp"]

@@ -17,7 +17,9 @@ EXPORTS = [
     "fsaempc_cl_pre_batch_device", "fsaempc_cl_plant_batch_device", "fsaempc_cl_accept_batch_device",
     "fsaempc_track_from_csv", "fsaempc_track_from_points", "fsaempc_track_free", "fsaempc_track_save", "fsaempc_track_load", "fsaempc_track_last_error",
     "fsaempc_nlp_build_qp_batch_device", "fsaempc_sqp_default_opts", "fsaempc_sqp_workspace_bytes", "fsaempc_sqp_batch_device",
-    "fsaempc_sqp_get_timing",
+    "fsaempc_sqp_get_timing", "fsaempc_qp_vjp_workspace_bytes", "fsaempc_qp_vjp_batch_device",
+    "fsaempc_ltv_affine_maps_batch_device", "fsaempc_ltv_step_batch_device_lambda", "fsaempc_ltv_step_vjp_workspace_bytes",
+    "fsaempc_ltv_step_vjp_batch_device",
 ]
 
 
@@ -32,6 +34,16 @@ class QpAux(C.Structure):
 
 class QpDesc(C.Structure):
     _fields_ = [("nV", C.c_int), ("nC", C.c_int), ("batch", C.c_int), ("shared_HA", C.c_int)]
+
+
+class QpVjpIO(C.Structure):
+    _fields_ = [("xbar", C.c_void_p), ("fbar", C.c_void_p), ("gbar", C.c_void_p), ("lbbar", C.c_void_p), ("ubbar", C.c_void_p),
+                ("lbAbar", C.c_void_p), ("ubAbar", C.c_void_p), ("Hbar", C.c_void_p), ("Abar", C.c_void_p)]
+
+
+class LtvVjpIO(C.Structure):
+    _fields_ = [("ubar", C.c_void_p), ("xbar", C.c_void_p), ("sbar", C.c_void_p), ("fbar", C.c_void_p), ("x0bar", C.c_void_p),
+                ("xrefbar", C.c_void_p)]
 
 
 class Spline(C.Structure):
@@ -77,9 +89,19 @@ def lib():
         L.fsaempc_qp_workspace_bytes.restype = C.c_longlong
         L.fsaempc_ltv_workspace_bytes.restype = C.c_longlong
         L.fsaempc_sqp_workspace_bytes.restype = C.c_longlong
+        L.fsaempc_qp_vjp_workspace_bytes.restype = C.c_longlong
+        L.fsaempc_ltv_step_vjp_workspace_bytes.restype = C.c_longlong
         vp, ll = C.c_void_p, C.c_longlong
         L.fsaempc_qp_solve_batch_device.argtypes = [C.POINTER(QpDesc)] + [vp] * 7 + [C.POINTER(QpOpts)] + [vp] * 5 + [vp, ll, vp]
         L.fsaempc_qp_solve_batch_device_aux.argtypes = [C.POINTER(QpDesc)] + [vp] * 7 + [C.POINTER(QpOpts)] + [vp] * 5 + [C.POINTER(QpAux), vp, ll, vp]
+        L.fsaempc_qp_vjp_workspace_bytes.argtypes = [C.POINTER(QpDesc)]
+        L.fsaempc_qp_vjp_batch_device.argtypes = [C.POINTER(QpDesc), C.c_int] + [vp] * 7 + [vp] * 4 + [C.POINTER(QpOpts), C.POINTER(QpVjpIO), vp, vp, ll, vp]
+        L.fsaempc_ltv_affine_maps_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline)] + [vp] * 5
+        L.fsaempc_ltv_step_batch_device_lambda.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline)] + [vp] * 4 + [C.POINTER(QpOpts)] + [vp] * 7 + \
+            [C.POINTER(QpAux), vp, ll, vp]
+        L.fsaempc_ltv_step_vjp_workspace_bytes.argtypes = [C.POINTER(LtvDesc), C.c_int]
+        L.fsaempc_ltv_step_vjp_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.c_int] + [vp] * 4 + [vp] * 5 + \
+            [C.POINTER(QpOpts), C.POINTER(LtvVjpIO), vp, vp, ll, vp]
         L.fsaempc_qp_solve_batch.argtypes = [C.POINTER(QpDesc)] + [vp] * 7 + [C.POINTER(QpOpts)] + [vp] * 5
         L.fsaempc_ltv_build_qp_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline)] + [vp] * 4 + [vp] * 7 + [vp] * 3 + [vp]
         L.fsaempc_ltv_step_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline)] + [vp] * 4 + [C.POINTER(QpOpts)] + [vp] * 6 + [vp, ll, vp]

@@ -16,6 +16,7 @@
 #include "reference.h"
 #include "plant.h"
 #include "sqp.h"
+#include "qp_sens.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -112,6 +113,47 @@ int fsaempc_qp_solve_batch_device_aux(const fsaempc_qp_desc* desc, const double*
     e = qp_launch(P, desc->batch, (hipStream_t)stream, timing ? g_ev[1] : nullptr); }
   if (e != hipSuccess) return hipfail(e, "qp_launch");
   if (timing) { e = hipEventRecord(g_ev[2], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
+  return 0;
+}
+
+// ---- VJP of the batched QP solve (qp_sens.hip) ----
+static int qp_vjp_plan(const fsaempc_qp_desc* desc, int k, QpsParams* P) {
+  if (!desc || desc->nV <= 0 || desc->nC < 0 || desc->batch < 0 || k < 1) return fail(FSAEMPC_ERR_ARG, "bad dimensions (nV > 0, nC >= 0, batch >= 0, k >= 1)");
+  if (desc->nV > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
+  memset(P, 0, sizeof(*P));
+  P->n = desc->nV; P->m = desc->nC; P->B = desc->batch; P->k = k; P->shared_HA = desc->shared_HA ? 1 : 0;
+  qps_plan(P);
+  if (P->lds_bytes > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "problem exceeds the 160 KiB LDS budget of the VJP kernel");
+  return 0;
+}
+long long fsaempc_qp_vjp_workspace_bytes(const fsaempc_qp_desc* desc) {
+  QpsParams P;
+  const int rc = qp_vjp_plan(desc, 1, &P);
+  return rc ? rc : (long long)qps_plan(&P);
+}
+int fsaempc_qp_vjp_batch_device(const fsaempc_qp_desc* desc, int k, const double* H, const double* g, const double* A,
+                                const double* lb, const double* ub, const double* lbA, const double* ubA,
+                                const double* x, const double* lambda, const int* exitflag, const int* polished,
+                                const fsaempc_qp_opts* opts, const fsaempc_qp_vjp_io* io, int* status,
+                                void* workspace, long long workspace_bytes, void* stream) {
+  QpsParams P;
+  int rc = qp_vjp_plan(desc, k, &P); if (rc) return rc;
+  if (!H || !g || !lb || !ub || !x || !lambda || !exitflag || !io || !io->xbar || !io->gbar || !status || !workspace)
+    return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (desc->nC > 0 && (!A || !lbA || !ubA)) return fail(FSAEMPC_ERR_ARG, "nC > 0 needs A, lbA, ubA");
+  if (desc->shared_HA && (io->Hbar || io->Abar)) return fail(FSAEMPC_ERR_ARG, "Hbar / Abar are per instance: not available with shared_HA");
+  if (desc->batch == 0) return 0;
+  if ((long long)qps_plan(&P) > workspace_bytes) return fail(FSAEMPC_ERR_WORKSPACE, "workspace too small");
+  fsaempc_qp_opts o; if (opts) o = *opts; else fsaempc_qp_default_opts(&o);
+  P.inf_bound = o.inf_bound; P.tol = o.tol;
+  P.H = H; P.g = g; P.A = A; P.lb = lb; P.ub = ub; P.lbA = lbA; P.ubA = ubA;
+  P.x = x; P.lam = lambda; P.exitflag = exitflag; P.polished = polished;
+  P.xbar = io->xbar; P.fbar = io->fbar; P.gbar = io->gbar; P.lbbar = io->lbbar; P.ubbar = io->ubbar; P.lbAbar = io->lbAbar; P.ubAbar = io->ubAbar;
+  P.Hbar = io->Hbar; P.Abar = io->Abar; P.status = status; P.ws = (double*)workspace;
+  hipError_t e;
+  { Range r("fsaempc.qp.vjp");
+    e = qps_launch(P, (hipStream_t)stream); }
+  if (e != hipSuccess) return hipfail(e, "qps_launch");
   return 0;
 }
 
@@ -411,10 +453,29 @@ int fsaempc_ltv_step_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_sp
   return fsaempc_ltv_step_batch_device_aux(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, nullptr, workspace, workspace_bytes, stream);
 }
 
+static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
+                    const double* u_lin, const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream);
+
 int fsaempc_ltv_step_batch_device_aux(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
                                       const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
                                       const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
                                       int* exitflag, int* iter, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
+  return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, nullptr, aux, workspace, workspace_bytes, stream);
+}
+
+int fsaempc_ltv_step_batch_device_lambda(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                                         const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                         const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                         int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                         void* workspace, long long workspace_bytes, void* stream) {
+  if (!lambda) return fail(FSAEMPC_ERR_ARG, "null argument (lambda)");
+  return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream);
+}
+
+static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
+                    const double* u_lin, const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
   int rc = ltv_check(desc, sp); if (rc) return rc;
   if (!x0 || !x_ref || !x_lin || !u_lin || !u_opt || !x_opt || !slack || !fval || !exitflag || !iter || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
@@ -432,7 +493,7 @@ int fsaempc_ltv_step_batch_device_aux(const fsaempc_ltv_desc* desc, const fsaemp
   if (rc) return rc;
   fsaempc_qp_desc q{fsaempc_ltv_nV(desc->model, desc->N), fsaempc_ltv_nC(desc->model, desc->N), desc->batch, 0};
   rc = fsaempc_qp_solve_batch_device_aux(&q, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA), opts, D(c.z), fval, exitflag, iter,
-                                         nullptr, aux, w + c.qpws, (long long)(c.total - c.qpws), stream);
+                                         lambda, aux, w + c.qpws, (long long)(c.total - c.qpws), stream);
   if (rc) return rc;
   hipError_t e;
   { Range r("fsaempc.ltv.post");
@@ -440,6 +501,84 @@ int fsaempc_ltv_step_batch_device_aux(const fsaempc_ltv_desc* desc, const fsaemp
                         u_opt, x_opt, slack, fval, (hipStream_t)stream); }
   if (e != hipSuccess) return hipfail(e, "ltv_post_launch");
   if (timing) { e = hipEventRecord(g_evf[1], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
+  return 0;
+}
+
+/* ---- sensitivities of the LTV-MPC step ---- */
+int fsaempc_ltv_affine_maps_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x_lin, const double* u_lin,
+                                         double* Abar, double* Crow, void* stream) {
+  int rc = ltv_check(desc, sp); if (rc) return rc;
+  if (!x_lin || !u_lin || !Abar || !Crow) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (ltv_affine_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
+  if (desc->batch == 0) return 0;
+  LtvParams P; memset(&P, 0, sizeof(P));
+  P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.dt = desc->dt; P.integ = ltv_integ(desc);
+  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP; P.x_lin = x_lin; P.u_lin = u_lin;
+  hipError_t e = ltv_affine_launch(P, desc->batch, Abar, Crow, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "ltv_affine_launch");
+  return 0;
+}
+
+struct LtvVjpCarve { LtvCarve f; size_t zbar, fb, gbar, lbAbar, ubAbar, Abar, Crow, vjpws, total; };
+static void ltv_vjp_carve(const fsaempc_ltv_desc* d, int k, LtvVjpCarve* c) {
+  ltv_carve(d, &c->f);
+  const size_t B = d->batch > 0 ? d->batch : 1, nx = fsaempc_ltv_nx(d->model), N = d->N, K = k > 0 ? k : 1;
+  const size_t nV = fsaempc_ltv_nV(d->model, d->N), nC = fsaempc_ltv_nC(d->model, d->N), R = nx * N;
+  size_t off = c->f.qpws;   // the forward's QP tensors stay; the solver's workspace is not needed here
+  auto take = [&](size_t cnt) { size_t o = off; off = align64(off + cnt * sizeof(double)); return o; };
+  c->zbar = take(B * K * nV); c->fb = take(B * K); c->gbar = take(B * K * nV); c->lbAbar = take(B * K * nC); c->ubAbar = take(B * K * nC);
+  c->Abar = take(B * R * nx); c->Crow = take(B * nC * nx);
+  off = (off + 255) & ~(size_t)255;
+  c->vjpws = off;
+  fsaempc_qp_desc q{(int)nV, (int)nC, (int)B, 0};
+  long long w = fsaempc_qp_vjp_workspace_bytes(&q);
+  c->total = off + (w > 0 ? (size_t)w : 0);
+}
+
+long long fsaempc_ltv_step_vjp_workspace_bytes(const fsaempc_ltv_desc* desc, int k) {
+  if (!desc || desc->N <= 0 || desc->batch < 0 || k < 1) return FSAEMPC_ERR_ARG;
+  if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return FSAEMPC_ERR_DIM;
+  LtvVjpCarve c; ltv_vjp_carve(desc, k, &c);
+  return (long long)c.total;
+}
+
+int fsaempc_ltv_step_vjp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, int k,
+                                      const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                      const double* u_opt, const double* slack, const double* lambda, const int* exitflag, const int* polished,
+                                      const fsaempc_qp_opts* opts, const fsaempc_ltv_vjp_io* io, int* status,
+                                      void* workspace, long long workspace_bytes, void* stream) {
+  int rc = ltv_check(desc, sp); if (rc) return rc;
+  if (k < 1) return fail(FSAEMPC_ERR_ARG, "k >= 1 cotangent columns");
+  if (!x0 || !x_ref || !x_lin || !u_lin || !u_opt || !slack || !lambda || !exitflag || !io || !io->x0bar || !status || !workspace)
+    return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
+  if (ltv_affine_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
+  if (desc->batch == 0) return 0;
+  LtvVjpCarve c; ltv_vjp_carve(desc, k, &c);
+  if ((long long)c.total > workspace_bytes) return fail(FSAEMPC_ERR_WORKSPACE, "workspace too small");
+  char* w = (char*)workspace;
+  auto D = [&](size_t off) { return (double*)(w + off); };
+  const int nx = fsaempc_ltv_nx(desc->model), N = desc->N, ns = ltv_ns(desc->model);
+  const int nV = fsaempc_ltv_nV(desc->model, N), nC = fsaempc_ltv_nC(desc->model, N), B = desc->batch;
+  hipStream_t st = (hipStream_t)stream;
+  Range whole("fsaempc.ltv.step_vjp");
+  // the QP of the step (the build is deterministic: the same QP the forward solved) and the affine maps
+  rc = build_qp(desc, sp, x0, x_ref, x_lin, u_lin, D(c.f.H), D(c.f.g), D(c.f.A), D(c.f.lb), D(c.f.ub), D(c.f.lbA), D(c.f.ubA),
+                D(c.f.pred), D(c.f.Bt), D(c.f.qc), stream, false);
+  if (rc) return rc;
+  rc = fsaempc_ltv_affine_maps_batch_device(desc, sp, x_lin, u_lin, D(c.Abar), D(c.Crow), stream);
+  if (rc) return rc;
+  hipError_t e = ltv_vjp_pre_launch(nx, N, ns, B, k, D(c.f.Bt), u_opt, slack, io->ubar, io->xbar, io->sbar, D(c.f.z), D(c.zbar), st);
+  if (e != hipSuccess) return hipfail(e, "ltv_vjp_pre_launch");
+  if (io->fbar) { e = hipMemcpyAsync(D(c.fb), io->fbar, sizeof(double) * (size_t)B * k, hipMemcpyDeviceToDevice, st); if (e != hipSuccess) return hipfail(e, "hipMemcpyAsync"); }
+  fsaempc_qp_desc q{nV, nC, B, 0};
+  fsaempc_qp_vjp_io qio{D(c.zbar), io->fbar ? D(c.fb) : nullptr, D(c.gbar), nullptr, nullptr, D(c.lbAbar), D(c.ubAbar), nullptr, nullptr};
+  rc = fsaempc_qp_vjp_batch_device(&q, k, D(c.f.H), D(c.f.g), D(c.f.A), D(c.f.lb), D(c.f.ub), D(c.f.lbA), D(c.f.ubA), D(c.f.z), lambda,
+                                   exitflag, polished, opts, &qio, status, w + c.vjpws, (long long)(c.total - c.vjpws), stream);
+  if (rc) return rc;
+  e = ltv_vjp_chain_launch(nx, N, B, k, D(c.f.Bt), D(c.f.pred), x_ref, D(c.Abar), D(c.Crow), D(c.gbar), D(c.lbAbar), D(c.ubAbar),
+                           io->xbar, io->fbar, status, io->x0bar, io->xrefbar, st);
+  if (e != hipSuccess) return hipfail(e, "ltv_vjp_chain_launch");
   return 0;
 }
 

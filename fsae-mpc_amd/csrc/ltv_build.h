@@ -17,3 +17,14 @@ hipError_t ltv_build_launch(const LtvParams& P, int batch, hipStream_t st, bool 
 hipError_t ltv_post_launch(int nx, int N, int ns, int batch, const double* z, const double* pred, const double* Bt,
                            const double* qconst, double* u_opt, double* x_opt, double* slack, double* fval, hipStream_t st);
 size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact = false);
+
+// sensitivities: the affine maps of the build in x0 / x_ref (Abar R x nx, Crow nC x nx per instance, column-major),
+// the cotangent of the QP variables of a step (z = [u_opt; slack], zbar = [ubar; sbar] + Bt' xbar, kc columns) and the chain from the
+// QP cotangents (gbar, lbAbar, ubAbar) to x0bar (kc x nx) / xrefbar (kc x R); status < 0 gives zeros
+size_t ltv_affine_lds_bytes(int nx, int N);
+hipError_t ltv_affine_launch(const LtvParams& P, int batch, double* Abar, double* Crow, hipStream_t st);
+hipError_t ltv_vjp_pre_launch(int nx, int N, int ns, int batch, int kc, const double* Bt, const double* u_opt, const double* slack,
+                              const double* ubar, const double* xbar, const double* sbar, double* z, double* zbar, hipStream_t st);
+hipError_t ltv_vjp_chain_launch(int nx, int N, int batch, int kc, const double* Bt, const double* pred, const double* x_ref,
+                                const double* Abar, const double* Crow, const double* gbar, const double* lbAbar, const double* ubAbar,
+                                const double* xbar, const double* fbar, const int* status, double* x0bar, double* xrefbar, hipStream_t st);

@@ -191,6 +191,30 @@ template <int NX> DEVINL void linearise_exact(const double* xi, const double* ui
 // rollout x_k = Psi(x_{k-1}, u_k) (x_0 = x0), step k is linearised exactly at (x_{k-1}, u_k), Phi(i,i) = Bd_i, every constraint row
 // is linearised at the rollout state it constrains, and pred receives the rollout (the affine offset of the QP, rollout - Phi u_lin,
 // stays internal).
+constexpr double QW[3] = {5, 250, 2000};   // state weights of the cost (ltvmpc_*.m:32); the terminal step carries 10 QW (:33)
+
+// Step 4a of the build: the coefficients of step k's linearised constraint rows, at the state xl they are linearised at
+// (kinematic: 3 values; dynamic: 16).  Shared by the build and by the affine maps of the sensitivities (ltv_affine_kernel).
+template <int NX> DEVINL void step_coef(const double* xl, const Spl& sp, double* ck) {
+  if (NX == 5) {
+    // kinematic_tyre_linearise_constraints.m:18-32 ; g = v^2 delta/(lr+lf)
+    ck[0] = 2 * xl[3] * xl[4] / (LF + LR);
+    ck[1] = xl[3] * xl[3] / (LF + LR);
+    ck[2] = xl[3] * xl[3] * xl[4] / (LR + LF);  // g0
+  } else {
+    double byp[8];
+    A_dyn(xl, sp, nullptr, byp);
+    const double Fcr = byp[0], Fcr_d = byp[1], vr = byp[2], dvr2 = byp[3], xh = byp[4], xhd = byp[5], vf = byp[6], dvf2 = byp[7];
+    // dynamic_slip_linearise_constraints.m:26-30 : rows (alpha_r, alpha_f) coefficients on states 4..7
+    ck[0] = dvr2 * vr * xhd / xh; ck[1] = -dvr2 / xh; ck[2] = dvr2 * LR / xh; ck[3] = 0.0;
+    ck[4] = dvf2 * vf * xhd / xh; ck[5] = -dvf2 / xh; ck[6] = -dvf2 * LF / xh; ck[7] = 1.0;
+    ck[8] = -atan(vr); ck[9] = xl[6] - atan(vf);
+    // dynamic_tyre_linearise_constraints.m:41-49 : C_j = dal_j * ck[10..12] on states 4..6
+    ck[10] = -Fcr_d * dvr2 * vr * xhd / xh / 280; ck[11] = Fcr_d * dvr2 / xh / 280; ck[12] = -Fcr_d * dvr2 * LR / xh / 280;
+    ck[13] = Fcr; ck[14] = 0; ck[15] = 0;
+  }
+}
+
 template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_kernel(LtvParams P) {
   constexpr int NN = NX * NX, NS = (NX == 5) ? 1 : 4, RPK = (NX == 5) ? 6 : 20;  // rows per step
   const int b = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
@@ -288,24 +312,7 @@ template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_k
   // ---- 4a. per-step constraint coefficients ----
   for (int k = tid; k < N; k += nth) {
     const double* xl = EXACT ? xs + (size_t)(k + 1) * NX : x_lin + (size_t)k * NX;   // (default: pairing quirk C-8)
-    double* ck = cc + (size_t)k * CW;
-    if (NX == 5) {
-      // kinematic_tyre_linearise_constraints.m:18-32 ; g = v^2 delta/(lr+lf)
-      ck[0] = 2 * xl[3] * xl[4] / (LF + LR);
-      ck[1] = xl[3] * xl[3] / (LF + LR);
-      ck[2] = xl[3] * xl[3] * xl[4] / (LR + LF);  // g0
-    } else {
-      double byp[8];
-      A_dyn(xl, sp, nullptr, byp);
-      const double Fcr = byp[0], Fcr_d = byp[1], vr = byp[2], dvr2 = byp[3], xh = byp[4], xhd = byp[5], vf = byp[6], dvf2 = byp[7];
-      // dynamic_slip_linearise_constraints.m:26-30 : rows (alpha_r, alpha_f) coefficients on states 4..7
-      ck[0] = dvr2 * vr * xhd / xh; ck[1] = -dvr2 / xh; ck[2] = dvr2 * LR / xh; ck[3] = 0.0;
-      ck[4] = dvf2 * vf * xhd / xh; ck[5] = -dvf2 / xh; ck[6] = -dvf2 * LF / xh; ck[7] = 1.0;
-      ck[8] = -atan(vr); ck[9] = xl[6] - atan(vf);
-      // dynamic_tyre_linearise_constraints.m:41-49 : C_j = dal_j * ck[10..12] on states 4..6
-      ck[10] = -Fcr_d * dvr2 * vr * xhd / xh / 280; ck[11] = Fcr_d * dvr2 / xh / 280; ck[12] = -Fcr_d * dvr2 * LR / xh / 280;
-      ck[13] = Fcr; ck[14] = 0; ck[15] = 0;
-    }
+    step_coef<NX>(xl, sp, cc + (size_t)k * CW);
   }
   __syncthreads();
 
@@ -396,7 +403,7 @@ template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_k
   // entry as a scalar dot product with stride-NX loads: 3.5 of the 10.3 ms of a dynamic N = 60 batch, 0.95 of 2.26 ms on the
   // headline shape.)  Lane (c = l & 15, q = l >> 4): A operand = weight * Bt[row rho][16 I + c], B operand = Bt[row rho][16 J + c],
   // rho = 4 s + q over the weighted rows (k, r) = (rho / 3, rho % 3); result register p holds H[16 I + q + 4 p][16 J + c].
-  const double Qw[3] = {5, 250, 2000};   // ltvmpc_*.m:32 ; Q_terminal = 10 Q (:33)
+  const double Qw[3] = {QW[0], QW[1], QW[2]};   // ltvmpc_*.m:32 ; Q_terminal = 10 Q (:33)
   {
     const int lane = tid & 63, wv = tid >> 6, nwv = nth >> 6, c = lane & 15, q = lane >> 4;
     const int nU = 2 * N, Tu = (nU + 15) >> 4, npairs = Tu * (Tu + 1) / 2, ksteps = (3 * N + 3) >> 2;
@@ -491,6 +498,126 @@ __global__ void ltv_post_kernel(int nx, int N, int ns, const double* z, const do
   if (tid == 0) fval[b] += qconst[b];
 }
 
+// ---- sensitivities: the build is affine in x0 and x_ref once x_lin, u_lin are fixed ----
+// Row `row` of the constraint block belongs to step row_step(): its bounds move by -Crow_row . pred_k (rows 0..4N: a unit
+// coefficient on v, delta, n; the linearised rows: the coefficients of step 4a, as step 4b applies them).
+template <int NX> DEVINL int row_step(int row, int N) {
+  if (row < 4 * N) return row % N;
+  if (NX == 5) return (row - 4 * N) % N;
+  if (row < 8 * N) return ((row - 4 * N) % (2 * N)) >> 1;
+  return (row - 8 * N) / 12;
+}
+template <int NX> DEVINL void row_coef(int row, int N, const double* ck, double* crow) {   // ck: the 4a coefficients of the row's step
+  for (int j = 0; j < NX; ++j) crow[j] = 0.0;
+  if (row < 4 * N) { const int blk = row / N; crow[blk == 0 ? 3 : (blk == 1 ? NX - 1 : 1)] = 1.0; return; }
+  if (NX == 5) { crow[3] = ck[0]; crow[4] = ck[1]; return; }
+  if (row < 8 * N) { const int q = ((row - 4 * N) % (2 * N)) & 1; for (int j = 0; j < 4; ++j) crow[3 + j] = ck[4 * q + j]; return; }
+  const int j = (row - 8 * N) % 12;
+  const double th0 = 2 * M_PI * (double)j / 12, th1 = (j + 1 == 12) ? 2 * M_PI : 2 * M_PI * (double)(j + 1) / 12;
+  const double dal = 10.0 * cos(th1) - 10.0 * cos(th0);
+  for (int jj = 0; jj < 3; ++jj) crow[3 + jj] = dal * ck[10 + jj];
+}
+
+// Abar (R x NX, column-major): d pred / d x0 = Ad_k ... Ad_1; Crow (nC x NX, column-major).  One workgroup per instance; the
+// linearisation and the 4a coefficients are the build's own device functions at the same points.
+template <int NX> __global__ __launch_bounds__(256) void ltv_affine_kernel(LtvParams P, double* Abar, double* Crow) {
+  constexpr int NN = NX * NX, RPK = (NX == 5) ? 6 : 20, CW = (NX == 5) ? 3 : 16;
+  const int b = blockIdx.x, tid = threadIdx.x, nth = blockDim.x, N = P.N, R = NX * N, nC = RPK * N;
+  Spl sp{P.spM, P.spdl, P.xP, P.yP};
+  const double* x_lin = P.x_lin + (size_t)b * R;
+  const double* u_lin = P.u_lin + (size_t)b * 2 * N;
+  extern __shared__ double sm[];
+  double* Ad = sm; double* Bd = Ad + (size_t)N * NN; double* dd = Bd + (size_t)N * NX * 2; double* cc = dd + (size_t)N * NX;
+  for (int k = tid; k < N; k += nth) {
+    linearise_step<NX>(x_lin + (size_t)k * NX, u_lin + (size_t)k * 2, sp, P.dt, P.integ, Ad + (size_t)k * NN, Bd + (size_t)k * NX * 2, dd + (size_t)k * NX);
+    step_coef<NX>(x_lin + (size_t)k * NX, sp, cc + (size_t)k * CW);
+  }
+  __syncthreads();
+  double* Ab = Abar + (size_t)b * R * NX;
+  if (tid < NX) {   // column tid: e_tid pushed through the recursion aff_k = Ad_k aff_{k-1}
+    double cur[NX], nxt[NX];
+    for (int j = 0; j < NX; ++j) cur[j] = j == tid ? 1.0 : 0.0;
+    for (int k = 0; k < N; ++k) {
+      const double* a = Ad + (size_t)k * NN;
+      for (int r = 0; r < NX; ++r) { double v = 0.0; for (int c = 0; c < NX; ++c) v += a[r + c * NX] * cur[c]; nxt[r] = v; }
+      for (int r = 0; r < NX; ++r) { cur[r] = nxt[r]; Ab[(size_t)k * NX + r + (size_t)tid * R] = nxt[r]; }
+    }
+  }
+  double* Cr = Crow + (size_t)b * nC * NX;
+  for (int row = tid; row < nC; row += nth) {
+    double crow[NX];
+    row_coef<NX>(row, N, cc + (size_t)row_step<NX>(row, N) * CW, crow);
+    for (int j = 0; j < NX; ++j) Cr[row + (size_t)j * nC] = crow[j];
+  }
+}
+
+// Cotangent of the QP's variables from the step's: zbar = [ubar; sbar] + Bt' xbar (x_opt = pred + Bt z), one column per block.y;
+// z = [u_opt; slack] (the forward's QP solution).
+__global__ void ltv_vjp_pre_kernel(int nx, int N, int ns, int kc, const double* Bt, const double* u_opt, const double* slack,
+                                   const double* ubar, const double* xbar, const double* sbar, double* z, double* zbar) {
+  const int b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, nth = blockDim.x;
+  const int R = nx * N, nV = 2 * N + ns;
+  const double* Btb = Bt + (size_t)b * R * nV;
+  const size_t col = (size_t)b * kc + c;
+  for (int i = tid; i < nV; i += nth) {
+    double s = 0.0;
+    if (i < 2 * N) s = ubar ? ubar[col * 2 * N + i] : 0.0;
+    else s = sbar ? sbar[col * ns + i - 2 * N] : 0.0;
+    if (xbar) for (int e = 0; e < R; ++e) s += Btb[e + (size_t)i * R] * xbar[col * R + e];
+    zbar[col * nV + i] = s;
+    if (c == 0) z[(size_t)b * nV + i] = i < 2 * N ? u_opt[(size_t)b * 2 * N + i] : slack[(size_t)b * ns + i - 2 * N];
+  }
+}
+
+// The transposed affine maps: pred receives xbar (x_opt), 2 Qbar Bt gbar (g = 2 Bt' Qbar (pred - x_ref)), -Crow'(lbAbar + ubAbar)
+// (row shifts) and 2 fbar Qbar (pred - x_ref) (qconst); x_ref receives minus the g and qconst parts; x0bar = Abar' predbar.
+// Instances whose QP VJP failed (status < 0) get zeros.  One workgroup per (instance, column).
+template <int NX> __global__ __launch_bounds__(256) void ltv_vjp_chain_kernel(int N, int kc, const double* Bt, const double* pred,
+    const double* x_ref, const double* Abar, const double* Crow, const double* gbar, const double* lbAbar, const double* ubAbar,
+    const double* xbar, const double* fbar, const int* status, double* x0bar, double* xrefbar) {
+  constexpr int NS = (NX == 5) ? 1 : 4, RPK = (NX == 5) ? 6 : 20;
+  const int b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, nth = blockDim.x;
+  const int R = NX * N, nV = 2 * N + NS, nC = RPK * N;
+  const size_t col = (size_t)b * kc + c;
+  const bool ok = status[b] >= 0;
+  extern __shared__ double pb[];   // R: cotangent of pred
+  const double* Btb = Bt + (size_t)b * R * nV;
+  const double* gb = gbar + col * nV;
+  const double fb = fbar ? fbar[col] : 0.0;
+  for (int e = tid; e < R; e += nth) {
+    const int k = e / NX, r = e - k * NX;
+    double p = xbar ? xbar[col * R + e] : 0.0, xr = 0.0;
+    if (r < 3) {
+      double G = 0.0;
+      for (int i = 0; i < 2 * N; ++i) G += Btb[e + (size_t)i * R] * gb[i];
+      const double w = ((k == N - 1) ? 10.0 : 1.0) * QW[r];
+      const double d = pred[(size_t)b * R + e] - x_ref[(size_t)b * R + e];
+      const double t = 2.0 * w * G + 2.0 * fb * w * d;
+      p += t; xr = -t;
+    }
+    pb[e] = p;
+    if (xrefbar) xrefbar[col * R + e] = ok ? xr : 0.0;
+  }
+  __syncthreads();
+  // rows of each step, in a fixed order per state: deterministic sums
+  for (int e = tid; e < R; e += nth) {
+    const int k = e / NX, j = e - k * NX;
+    double s = 0.0;
+    for (int row = 0; row < nC; ++row) {
+      if (row_step<NX>(row, N) != k) continue;
+      const double cr = Crow[(size_t)b * nC * NX + row + (size_t)j * nC];
+      if (cr != 0.0) s += cr * (lbAbar[col * nC + row] + ubAbar[col * nC + row]);
+    }
+    pb[e] -= s;
+  }
+  __syncthreads();
+  if (tid < NX) {
+    double s = 0.0;
+    for (int e = 0; e < R; ++e) s += Abar[(size_t)b * R * NX + e + (size_t)tid * R] * pb[e];
+    x0bar[col * NX + tid] = ok ? s : 0.0;
+  }
+}
+
 }  // namespace
 
 size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact) {
@@ -517,5 +644,35 @@ hipError_t ltv_build_launch(const LtvParams& P, int batch, hipStream_t st, bool 
 hipError_t ltv_post_launch(int nx, int N, int ns, int batch, const double* z, const double* pred, const double* Bt, const double* qconst,
                            double* u_opt, double* x_opt, double* slack, double* fval, hipStream_t st) {
   hipLaunchKernelGGL(ltv_post_kernel, dim3(batch), dim3(256), 0, st, nx, N, ns, z, pred, Bt, qconst, u_opt, x_opt, slack, fval);
+  return hipGetLastError();
+}
+
+size_t ltv_affine_lds_bytes(int nx, int N) {
+  const int CW = (nx == 5) ? 3 : 16;
+  return ((size_t)N * nx * nx + (size_t)N * nx * 2 + (size_t)N * nx + (size_t)N * CW) * sizeof(double);
+}
+
+hipError_t ltv_affine_launch(const LtvParams& P, int batch, double* Abar, double* Crow, hipStream_t st) {
+  const size_t lds = ltv_affine_lds_bytes(P.nx, P.N);
+  const void* f = P.nx == 5 ? reinterpret_cast<const void*>(&ltv_affine_kernel<5>) : reinterpret_cast<const void*>(&ltv_affine_kernel<7>);
+  hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  if (P.nx == 5) hipLaunchKernelGGL(ltv_affine_kernel<5>, dim3(batch), dim3(256), lds, st, P, Abar, Crow);
+  else hipLaunchKernelGGL(ltv_affine_kernel<7>, dim3(batch), dim3(256), lds, st, P, Abar, Crow);
+  return hipGetLastError();
+}
+
+hipError_t ltv_vjp_pre_launch(int nx, int N, int ns, int batch, int kc, const double* Bt, const double* u_opt, const double* slack,
+                              const double* ubar, const double* xbar, const double* sbar, double* z, double* zbar, hipStream_t st) {
+  hipLaunchKernelGGL(ltv_vjp_pre_kernel, dim3(batch, kc), dim3(256), 0, st, nx, N, ns, kc, Bt, u_opt, slack, ubar, xbar, sbar, z, zbar);
+  return hipGetLastError();
+}
+
+hipError_t ltv_vjp_chain_launch(int nx, int N, int batch, int kc, const double* Bt, const double* pred, const double* x_ref,
+                                const double* Abar, const double* Crow, const double* gbar, const double* lbAbar, const double* ubAbar,
+                                const double* xbar, const double* fbar, const int* status, double* x0bar, double* xrefbar, hipStream_t st) {
+  const size_t lds = (size_t)nx * N * sizeof(double);
+  if (nx == 5) hipLaunchKernelGGL(ltv_vjp_chain_kernel<5>, dim3(batch, kc), dim3(256), lds, st, N, kc, Bt, pred, x_ref, Abar, Crow, gbar, lbAbar, ubAbar, xbar, fbar, status, x0bar, xrefbar);
+  else hipLaunchKernelGGL(ltv_vjp_chain_kernel<7>, dim3(batch, kc), dim3(256), lds, st, N, kc, Bt, pred, x_ref, Abar, Crow, gbar, lbAbar, ubAbar, xbar, fbar, status, x0bar, xrefbar);
   return hipGetLastError();
 }

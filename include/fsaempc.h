@@ -152,6 +152,51 @@ int fsaempc_seq_equality(int handle, int nV, int nC, const double* g, const doub
                          double* x, double* lambda, int* workingSetB, int* workingSetC);        /* 'e' */
 int fsaempc_seq_cleanup(int handle);                                                         /* 'c' */
 
+/* ---- sensitivities: vector-Jacobian product of the batched QP solve ---------------------------
+ * The reference's route to sensitivities is qpOASES_sequence('e', ...) (optimizers/matlab/qpOASES/qpOASES_sequence.m:64): the
+ * equality QP of the current working set solved for new right-hand sides (fsaempc_seq_equality above, one QP on a handle).  This is
+ * its batched, on-device counterpart in reverse mode.  For a QP solved by fsaempc_qp_solve_batch_device(_aux) with lambda and
+ * polished, the working set is the solver's refinement rule (a side is in it iff its multiplier has the side's sign and exceeds the
+ * side's slack).  With A^ = the working rows plus unit rows of the active bounds, each cotangent column xbar (and fbar) solves
+ *     H w + A^' mu = xbar + fbar (H x + g),   A^ w = 0
+ * and gives gbar = -w + fbar x, bbar = mu on the active side of each working-set constraint (0 elsewhere),
+ * Hbar = -(w x' + x w')/2 + fbar x x'/2, Abar row r = lambda_r w' - mu_r x' for working rows (0 otherwise).
+ * Per-instance status: 0 vertex (polished > 0), solved, every working-set multiplier above tol (1 + |lambda|_inf); 1 as 0 with a
+ * weakly active side kept (one-sided derivative); 2 the forward returned the interior-point iterate (polished <= 0), working set
+ * of the rule used anyway; -1 system singular / not solved to a relative KKT residual of 1e-12 (zeros); -2 forward exit flag != 0
+ * (zeros).  Results depend only on the instance's own data. */
+#define FSAEMPC_VJP_OK 0
+#define FSAEMPC_VJP_WEAK 1
+#define FSAEMPC_VJP_INTERIOR 2
+#define FSAEMPC_VJP_SINGULAR (-1)
+#define FSAEMPC_VJP_FORWARD_FAILED (-2)
+
+/* Cotangents in and out (device arrays, instance-major; column c of instance b starts at (b k + c) * <size>). */
+typedef struct {
+  const double* xbar;  /* IN  k * nV per instance (required) */
+  const double* fbar;  /* IN  k per instance (NULL = 0) */
+  double* gbar;        /* OUT k * nV (required) */
+  double* lbbar;       /* OUT k * nV (NULL = not wanted) */
+  double* ubbar;       /* OUT k * nV */
+  double* lbAbar;      /* OUT k * nC */
+  double* ubAbar;      /* OUT k * nC */
+  double* Hbar;        /* OUT k * nV * nV, column-major (not with shared_HA) */
+  double* Abar;        /* OUT k * nC * nV, column-major nC x nV as A (not with shared_HA) */
+} fsaempc_qp_vjp_io;
+
+/* Bytes of device workspace fsaempc_qp_vjp_batch_device needs for `desc` (at most 512 instances are in flight). */
+long long fsaempc_qp_vjp_workspace_bytes(const fsaempc_qp_desc* desc);
+
+/* x, lambda (nV + nC), exitflag, polished (may be NULL: every instance counts as unrefined, status 2) are the outputs of the forward
+ * solve of the same data; opts (may be NULL) supplies inf_bound and the weak-multiplier tolerance tol.  k >= 1 columns.  Asking for
+ * Hbar or Abar with desc->shared_HA returns FSAEMPC_ERR_ARG.  status: batch ints.  Asynchronous on `stream`. */
+int fsaempc_qp_vjp_batch_device(const fsaempc_qp_desc* desc, int k,
+                                const double* H, const double* g, const double* A,
+                                const double* lb, const double* ub, const double* lbA, const double* ubA,
+                                const double* x, const double* lambda, const int* exitflag, const int* polished,
+                                const fsaempc_qp_opts* opts, const fsaempc_qp_vjp_io* io, int* status,
+                                void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- LTV-MPC step (QP construction + solve + post-solve) ---------------------------------- */
 
 /* Track spline table: the `kappa` closure of main.m:18 as data.  xP,yP: M x 4 column-major. */
@@ -213,6 +258,46 @@ int fsaempc_ltv_step_batch_device_aux(const fsaempc_ltv_desc* desc, const fsaemp
                                       const fsaempc_qp_opts* opts,
                                       double* u_opt, double* x_opt, double* slack, double* fval, int* exitflag, int* iter,
                                       const fsaempc_qp_aux* aux,
+                                      void* workspace, long long workspace_bytes, void* stream);
+
+/* ---- sensitivities of the LTV-MPC step (the step's counterpart of qpOASES_sequence('e'), qpOASES_sequence.m:64) ----
+ * With x_lin, u_lin fixed the build depends on x0 and x_ref only through pred = Abar x0 + d_bar, g_u = 2 Phi' Qbar (pred - x_ref),
+ * row shifts of lbA / ubA that are affine in the predicted state of the row's own step, and qconst; H, A, lb, ub do not move.
+ * fsaempc_ltv_affine_maps_batch_device writes, per instance, Abar (nx N x nx, column-major: d pred / d x0) and Crow (nC x nx,
+ * column-major): lbA_r and ubA_r move by -Crow_r . pred_k, k the step of row r (rows 0..4N: k = r mod N; kinematic rows 4N..6N:
+ * (r - 4N) mod N; dynamic slip rows 4N..8N: ((r - 4N) mod 2N) / 2; dynamic tyre rows: (r - 8N) / 12).  Same linearisation and step
+ * coefficients as the build. */
+int fsaempc_ltv_affine_maps_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x_lin, const double* u_lin,
+                                         double* Abar, double* Crow, void* stream);
+
+/* The fused step that also returns the multipliers of its QP (lambda: nV + nC per instance, layout of fsaempc_qp_solve_batch_device):
+ * the forward of fsaempc_ltv_step_vjp_batch_device.  Same outputs and workspace as fsaempc_ltv_step_batch_device_aux. */
+int fsaempc_ltv_step_batch_device_lambda(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                                         const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                         const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                         int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                         void* workspace, long long workspace_bytes, void* stream);
+
+/* Cotangents of the step (device arrays; column c of instance b at (b k + c) * <size>). */
+typedef struct {
+  const double* ubar;  /* IN  k * 2N   cotangent of u_opt (NULL = 0) */
+  const double* xbar;  /* IN  k * nx N cotangent of x_opt (NULL = 0) */
+  const double* sbar;  /* IN  k * ns   cotangent of slack (NULL = 0) */
+  const double* fbar;  /* IN  k        cotangent of fval  (NULL = 0) */
+  double* x0bar;       /* OUT k * nx   (required) */
+  double* xrefbar;     /* OUT k * nx N (NULL = not wanted) */
+} fsaempc_ltv_vjp_io;
+
+long long fsaempc_ltv_step_vjp_workspace_bytes(const fsaempc_ltv_desc* desc, int k);
+
+/* VJP of the step in x0 and x_ref (x_lin, u_lin fixed).  u_opt, slack, lambda, exitflag, polished (may be NULL) are the outputs of
+ * fsaempc_ltv_step_batch_device_lambda (with fsaempc_qp_aux.polished) on the same inputs.  The QP is rebuilt by the build kernel,
+ * its VJP is fsaempc_qp_vjp_batch_device, and a chain kernel applies the transposed affine maps.  status: the QP VJP's status
+ * (FSAEMPC_VJP_*); a negative status gives zeros.  k >= 1 columns; asynchronous on `stream`. */
+int fsaempc_ltv_step_vjp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, int k,
+                                      const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                      const double* u_opt, const double* slack, const double* lambda, const int* exitflag, const int* polished,
+                                      const fsaempc_qp_opts* opts, const fsaempc_ltv_vjp_io* io, int* status,
                                       void* workspace, long long workspace_bytes, void* stream);
 
 /*
