@@ -13,7 +13,7 @@ all: $(LIBDIR)/libfsaempc.so oracle o1 dbg
 CC_CHECKED := HIPCC=$(HIPCC) tools/hipcc_checked.sh
 CHECKDEPS := tools/hipcc_checked.sh tools/check_isa_exec_prologue.py
 
-$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/qp_solver.h $(CSRC)/qp_sens.h $(CSRC)/ltv_build.h $(CSRC)/nlp_model.h $(CSRC)/sqp.h $(CSRC)/reference.h $(CSRC)/plant.h include/fsaempc.h $(CHECKDEPS)
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/qp_solver.h $(CSRC)/qp_sens.h $(CSRC)/ltv_build.h $(CSRC)/nlp_model.h $(CSRC)/mpc_params.h $(CSRC)/sqp.h $(CSRC)/reference.h $(CSRC)/plant.h include/fsaempc.h $(CHECKDEPS)
 	@mkdir -p $(LIBDIR)
 	$(CC_CHECKED) $@ $< $(HIPFLAGS)
 

@@ -2,7 +2,7 @@
 solve) as hand-written gfx950 HIP kernels behind a C ABI (include/fsaempc.h, lib/libfsaempc.so).  This
 package is the host-side mirror of the reference's interfaces for that path; it contains no CPU compute path."""
 from . import _lib
-from ._lib import FsaempcError, default_opts, lib
+from ._lib import NPAR, PARAM_INDEX, FsaempcError, default_opts, default_params, lib
 from .closed_loop import ClosedLoop, monte_carlo, monte_carlo_carts
 from .ltvmpc import LtvBatch, dims, ltvmpc_dynamic_curvilinear, ltvmpc_kinetmatic_curvilinear
 from .qpoases import qp_solve_batch_device, qpOASES, qpOASES_sequence
@@ -10,11 +10,11 @@ from .sqp import SqpBatch, sqp_timing
 from .sensitivity import (LtvStepFunction, QpFunction, feedback_gain, ltv_step_affine_maps, ltv_step_diff, ltv_step_lambda,
                           ltv_step_vjp, qp_vjp)
 from .reference import obtain_reference, obtain_reference_batch_device, reference_live_batch_device
-from .synthetic import DYNAMIC, KINEMATIC, instances, reference_live
+from .synthetic import DYNAMIC, KINEMATIC, instances, param_draws, reference_live
 from .tracks import Track
 
 __all__ = ["FsaempcError", "default_opts", "lib", "LtvBatch", "dims", "ltvmpc_dynamic_curvilinear",
            "ltvmpc_kinetmatic_curvilinear", "qp_solve_batch_device", "qpOASES", "qpOASES_sequence", "DYNAMIC", "KINEMATIC",
            "instances", "reference_live", "Track", "obtain_reference", "obtain_reference_batch_device",
            "reference_live_batch_device", "ClosedLoop", "monte_carlo", "monte_carlo_carts", "SqpBatch", "sqp_timing", "QpFunction", "qp_vjp",
-           "LtvStepFunction", "feedback_gain", "ltv_step_affine_maps", "ltv_step_diff", "ltv_step_lambda", "ltv_step_vjp"]
+           "LtvStepFunction", "feedback_gain", "ltv_step_affine_maps", "ltv_step_diff", "ltv_step_lambda", "ltv_step_vjp", "NPAR", "PARAM_INDEX", "default_params", "param_draws"]

@@ -20,7 +20,16 @@ EXPORTS = [
     "fsaempc_sqp_get_timing", "fsaempc_qp_vjp_workspace_bytes", "fsaempc_qp_vjp_batch_device",
     "fsaempc_ltv_affine_maps_batch_device", "fsaempc_ltv_step_batch_device_lambda", "fsaempc_ltv_step_vjp_workspace_bytes",
     "fsaempc_ltv_step_vjp_batch_device",
+    "fsaempc_ltv_default_params", "fsaempc_ltv_build_qp_batch_device_p", "fsaempc_ltv_step_batch_device_p",
+    "fsaempc_nlp_build_qp_batch_device_p", "fsaempc_sqp_batch_device_p", "fsaempc_cl_plant_batch_device_p",
 ]
+
+# fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
+NPAR = 32
+PARAM_INDEX = {name: i for i, name in enumerate(
+    ["M", "IZ", "LF", "LR", "GRAV", "PB", "PC", "PD", "PE", "Q_S", "Q_N", "Q_MU", "Q_TERMINAL", "R_ACC", "R_STEER",
+     "R_SOFT0", "R_SOFT1", "R_SOFT2", "R_SOFT3", "U_ACC_MAX", "U_STEER_MAX", "DELTA_MAX", "N_MAX", "V_MIN", "ALAT_MAX", "SLIP_MAX",
+     "ELL_LONG", "ELL_LAT", "PID_KP_V", "PID_MAX_F", "PID_KP_D", "PID_MAX_DRATE"])}
 
 
 class QpOpts(C.Structure):
@@ -52,6 +61,10 @@ class Spline(C.Structure):
 
 class LtvDesc(C.Structure):
     _fields_ = [("model", C.c_int), ("N", C.c_int), ("batch", C.c_int), ("dt", C.c_double), ("integrator", C.c_int)]
+
+
+class LtvParams(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("per_instance", C.c_int)]
 
 
 class SqpOpts(C.Structure):
@@ -117,6 +130,14 @@ def lib():
         L.fsaempc_cl_pre_batch_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(Spline), vp, vp, C.c_int, vp, vp, vp, vp]
         L.fsaempc_cl_plant_batch_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp, vp]
         L.fsaempc_cl_accept_batch_device.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.fsaempc_ltv_default_params.argtypes = [C.c_int, C.POINTER(C.c_double)]
+        L.fsaempc_ltv_build_qp_batch_device_p.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams)] + [vp] * 4 + [vp] * 7 + [vp] * 3 + [vp]
+        L.fsaempc_ltv_step_batch_device_p.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams)] + [vp] * 4 + [C.POINTER(QpOpts)] + \
+            [vp] * 7 + [C.POINTER(QpAux), vp, ll, vp]
+        L.fsaempc_nlp_build_qp_batch_device_p.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams)] + [vp] * 3 + [vp] * 7 + [vp] * 3 + [vp]
+        L.fsaempc_sqp_batch_device_p.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams)] + [vp] * 3 + \
+            [C.POINTER(QpOpts), C.POINTER(SqpOpts)] + [vp] * 6 + [C.POINTER(SqpAux), vp, ll, vp]
+        L.fsaempc_cl_plant_batch_device_p.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(LtvParams), vp, vp, vp, vp, vp, vp, vp]
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p
         L.fsaempc_track_from_csv.argtypes = [C.c_char_p, C.c_int, C.POINTER(TrackTable)]
@@ -131,6 +152,32 @@ def lib():
 def check(rc, what):
     if rc != 0:
         raise FsaempcError("%s failed (%d): %s" % (what, rc, lib().fsaempc_last_error().decode()))
+
+
+def default_params(model):
+    """The FSAEMPC_NPAR defaults of `model` (fsaempc_ltv_default_params; a host function: no GPU needed) as a (32,) numpy array."""
+    import numpy as np
+    out = np.zeros(NPAR, dtype=np.float64)
+    check(lib().fsaempc_ltv_default_params(int(model), out.ctypes.data_as(C.POINTER(C.c_double))), "fsaempc_ltv_default_params")
+    return out
+
+
+class ParamBlock:
+    """Device copy of a parameter block, (32,) shared by the batch or (batch, 32) per instance (numpy or a device tensor), and the
+    fsaempc_ltv_params that points at it."""
+
+    def __init__(self, params, batch, device):
+        import numpy as np
+        import torch
+        t = params if isinstance(params, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(params, dtype=np.float64)))
+        if tuple(t.shape) not in ((NPAR,), (batch, NPAR)):
+            raise ValueError("params must be (%d,) or (batch = %d, %d), got %s" % (NPAR, batch, NPAR, tuple(t.shape)))
+        self.tensor = t.to(device=device, dtype=torch.float64).contiguous()
+        self.per_instance = 1 if t.dim() == 2 else 0
+        self.c = LtvParams(C.c_void_p(self.tensor.data_ptr()), self.per_instance)
+
+    def ref(self):
+        return C.byref(self.c)
 
 
 def sqp_default_opts(**kw):

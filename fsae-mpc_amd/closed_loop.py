@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import Spline, check, lib
+from ._lib import ParamBlock, Spline, check, lib
 from .ltvmpc import LtvBatch, dims
 
 
@@ -14,7 +14,10 @@ class ClosedLoop:
     back; like the reference (main.m:122-126, 163-175) a car keeps driving after an abnormal solver exit -- on its last good
     plan -- and the exit flags are only tallied.  Cars that completed the lap (s >= L) or left the track keep their state."""
 
-    def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True):
+    def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
+                 params=None, plant_params=None):
+        """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
+        None = the same as params (both None: the reference's constants compiled into the kernels)."""
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -23,7 +26,10 @@ class ClosedLoop:
         cart0 = np.ascontiguousarray(np.asarray(cart0, dtype=np.float64).reshape(-1, 7))
         self.B = cart0.shape[0]
         self.track = track
-        self.mpc = LtvBatch(model, N, dt, track, self.B, device=device, options=options, integrator=integrator)
+        self.mpc = LtvBatch(model, N, dt, track, self.B, device=device, options=options, integrator=integrator, params=params)
+        if plant_params is None:
+            plant_params = params
+        self.plant_params = ParamBlock(plant_params, self.B, self.device) if plant_params is not None else None
         self.cart = torch.from_numpy(cart0).to(self.device)
         self.pid = torch.zeros((self.B, 4), dtype=torch.float64, device=self.device)
         self.finished = torch.zeros(self.B, dtype=torch.int32, device=self.device)
@@ -63,8 +69,12 @@ class ClosedLoop:
 
     def plant(self, exitflag, stream=None):
         P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        rc = lib().fsaempc_cl_plant_batch_device(self.model, self.N, C.c_double(self.dt), self.B, P(self.cart), P(self.pid), P(self.x_opt),
-                                                 P(self.finished), P(exitflag), P(self.u_last), self._stream(stream))
+        if self.plant_params is not None:
+            rc = lib().fsaempc_cl_plant_batch_device_p(self.model, self.N, C.c_double(self.dt), self.B, self.plant_params.ref(), P(self.cart), P(self.pid),
+                                                       P(self.x_opt), P(self.finished), P(exitflag), P(self.u_last), self._stream(stream))
+        else:
+            rc = lib().fsaempc_cl_plant_batch_device(self.model, self.N, C.c_double(self.dt), self.B, P(self.cart), P(self.pid), P(self.x_opt),
+                                                     P(self.finished), P(exitflag), P(self.u_last), self._stream(stream))
         check(rc, "fsaempc_cl_plant_batch_device")
 
     def step(self, stream=None):
@@ -109,13 +119,15 @@ def monte_carlo_carts(track, B, seed):
     return cart, s
 
 
-def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True):
+def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
+                plant_params=None):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
     import torch
     cart0, s_init = monte_carlo_carts(track, B, seed)
-    cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint)
+    cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
+                    params=params, plant_params=plant_params)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

@@ -390,9 +390,32 @@ static int ltv_integ(const fsaempc_ltv_desc* d) {
   return d->integrator >= 0 ? d->integrator : (d->model == FSAEMPC_MODEL_KINEMATIC ? FSAEMPC_INT_RK2 : FSAEMPC_INT_RK4);   // ltvmpc_*.m:38
 }
 
+/* ---- parameter blocks ---- */
+int fsaempc_ltv_default_params(int model, double* out) {
+  if (!out) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  const bool dyn = model == FSAEMPC_MODEL_DYNAMIC;
+  out[FSAEMPC_P_M] = 280; out[FSAEMPC_P_IZ] = 200; out[FSAEMPC_P_LF] = 0.8672; out[FSAEMPC_P_LR] = 0.6183; out[FSAEMPC_P_GRAV] = 9.81;
+  out[FSAEMPC_P_PB] = 12.56; out[FSAEMPC_P_PC] = 1.38; out[FSAEMPC_P_PD] = 1.60; out[FSAEMPC_P_PE] = -0.58;
+  out[FSAEMPC_P_Q_S] = 5; out[FSAEMPC_P_Q_N] = 250; out[FSAEMPC_P_Q_MU] = 2000; out[FSAEMPC_P_Q_TERMINAL] = 10;
+  out[FSAEMPC_P_R_ACC] = 10; out[FSAEMPC_P_R_STEER] = 10;
+  out[FSAEMPC_P_R_SOFT0] = 1e8; out[FSAEMPC_P_R_SOFT1] = dyn ? 1e6 : 0; out[FSAEMPC_P_R_SOFT2] = dyn ? 1e6 : 0; out[FSAEMPC_P_R_SOFT3] = dyn ? 1e4 : 0;
+  out[FSAEMPC_P_U_ACC_MAX] = 10; out[FSAEMPC_P_U_STEER_MAX] = 0.4; out[FSAEMPC_P_DELTA_MAX] = 0.4; out[FSAEMPC_P_N_MAX] = 0.75;
+  out[FSAEMPC_P_V_MIN] = 0; out[FSAEMPC_P_ALAT_MAX] = 5; out[FSAEMPC_P_SLIP_MAX] = 0.1; out[FSAEMPC_P_ELL_LONG] = 10.0; out[FSAEMPC_P_ELL_LAT] = 9.163;
+  out[FSAEMPC_P_PID_KP_V] = 16000; out[FSAEMPC_P_PID_MAX_F] = 2800; out[FSAEMPC_P_PID_KP_D] = 80; out[FSAEMPC_P_PID_MAX_DRATE] = 0.8;
+  return 0;
+}
+// a NULL block (or NULL values) selects the kernels with the constants compiled in
+static const double* par_values(const fsaempc_ltv_params* par) { return par ? par->values : nullptr; }
+static int par_stride(const fsaempc_ltv_params* par) { return par && par->per_instance ? FSAEMPC_NPAR : 0; }
+
+// par_idx (with par): the batch instance behind each instance of this (sub-)batch, for the per-instance blocks
 static int build_qp(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
                     const double* u_lin, double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
-                    double* pred, double* Bt, double* qconst, void* stream, bool exact) {
+                    double* pred, double* Bt, double* qconst, void* stream, bool exact, const fsaempc_ltv_params* par = nullptr,
+                    const int* par_idx = nullptr) {
+  if (par_values(par) && ltv_build_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N, 256, exact, true) > 160 * 1024)
+    return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
   if (desc->batch == 0) return 0;
   LtvParams P; memset(&P, 0, sizeof(P));
   P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.dt = desc->dt;
@@ -400,28 +423,41 @@ static int build_qp(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, cons
   P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP;
   P.x0 = x0; P.x_ref = x_ref; P.x_lin = x_lin; P.u_lin = u_lin;
   P.H = H; P.g = g; P.A = A; P.lb = lb; P.ub = ub; P.lbA = lbA; P.ubA = ubA; P.pred = pred; P.Bt = Bt; P.qconst = qconst;
-  hipError_t e = ltv_build_launch(P, desc->batch, (hipStream_t)stream, exact);
+  hipError_t e = par_values(par) ? ltv_build_par_launch(P, par_values(par), par_stride(par), par_idx, desc->batch, (hipStream_t)stream, exact)
+                                 : ltv_build_launch(P, desc->batch, (hipStream_t)stream, exact);
   if (e != hipSuccess) return hipfail(e, "ltv_build_launch");
   return 0;
 }
 
+int fsaempc_ltv_build_qp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream) {
+  int rc = ltv_check(desc, sp); if (rc) return rc;
+  if (!x0 || !x_ref || !x_lin || !u_lin || !H || !g || !A || !lb || !ub || !lbA || !ubA || !Bt) return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
+  return build_qp(desc, sp, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream, false, par);
+}
 int fsaempc_ltv_build_qp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
                                       const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
                                       double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
                                       double* pred, double* Bt, double* qconst, void* stream) {
-  int rc = ltv_check(desc, sp); if (rc) return rc;
-  if (!x0 || !x_ref || !x_lin || !u_lin || !H || !g || !A || !lb || !ub || !lbA || !ubA || !Bt) return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
-  return build_qp(desc, sp, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream, false);
+  return fsaempc_ltv_build_qp_batch_device_p(desc, sp, nullptr, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
 }
 
+int fsaempc_nlp_build_qp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const double* x0, const double* x_ref, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream) {
+  int rc = ltv_check(desc, sp); if (rc) return rc;
+  if (ltv_build_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N, 256, true) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
+  if (!x0 || !x_ref || !u_lin || !H || !g || !A || !lb || !ub || !lbA || !ubA || !Bt) return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
+  return build_qp(desc, sp, x0, x_ref, nullptr, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream, true, par);
+}
 int fsaempc_nlp_build_qp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
                                       const double* x0, const double* x_ref, const double* u_lin,
                                       double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
                                       double* pred, double* Bt, double* qconst, void* stream) {
-  int rc = ltv_check(desc, sp); if (rc) return rc;
-  if (ltv_build_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N, 256, true) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
-  if (!x0 || !x_ref || !u_lin || !H || !g || !A || !lb || !ub || !lbA || !ubA || !Bt) return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
-  return build_qp(desc, sp, x0, x_ref, nullptr, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream, true);
+  return fsaempc_nlp_build_qp_batch_device_p(desc, sp, nullptr, x0, x_ref, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
 }
 
 struct LtvCarve { size_t H, g, A, lb, ub, lbA, ubA, pred, Bt, qc, z, qpws, total; };
@@ -455,7 +491,16 @@ int fsaempc_ltv_step_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_sp
 
 static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
                     const double* u_lin, const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream);
+                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream,
+                    const fsaempc_ltv_params* par = nullptr);
+
+int fsaempc_ltv_step_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                    void* workspace, long long workspace_bytes, void* stream) {
+  return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream, par);
+}
 
 int fsaempc_ltv_step_batch_device_aux(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
                                       const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
@@ -475,7 +520,8 @@ int fsaempc_ltv_step_batch_device_lambda(const fsaempc_ltv_desc* desc, const fsa
 
 static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
                     const double* u_lin, const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
+                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream,
+                    const fsaempc_ltv_params* par) {
   int rc = ltv_check(desc, sp); if (rc) return rc;
   if (!x0 || !x_ref || !x_lin || !u_lin || !u_opt || !x_opt || !slack || !fval || !exitflag || !iter || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
@@ -488,8 +534,8 @@ static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, cons
   const bool timing = g_timing.load();
   if (timing) { hipError_t e = hipEventRecord(g_evf[0], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
   { Range r("fsaempc.ltv.build");
-    rc = fsaempc_ltv_build_qp_batch_device(desc, sp, x0, x_ref, x_lin, u_lin, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA),
-                                           D(c.pred), D(c.Bt), D(c.qc), stream); }
+    rc = fsaempc_ltv_build_qp_batch_device_p(desc, sp, par, x0, x_ref, x_lin, u_lin, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA),
+                                             D(c.pred), D(c.Bt), D(c.qc), stream); }
   if (rc) return rc;
   fsaempc_qp_desc q{fsaempc_ltv_nV(desc->model, desc->N), fsaempc_ltv_nC(desc->model, desc->N), desc->batch, 0};
   rc = fsaempc_qp_solve_batch_device_aux(&q, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA), opts, D(c.z), fval, exitflag, iter,
@@ -620,6 +666,16 @@ int fsaempc_sqp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline*
                              const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
                              double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
                              const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
+  return fsaempc_sqp_batch_device_p(desc, sp, nullptr, x0, x_ref, u_init, qp_opts, sqp_opts, u_opt, x_opt, slack, fval, status, sweeps, aux,
+                                    workspace, workspace_bytes, stream);
+}
+
+// (build, initial rollout and line search all read the block: instance i of a compacted sub-batch finds its own through the index list)
+int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                               const double* x0, const double* x_ref, const double* u_init,
+                               const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
+                               double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
+                               const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
   int rc = ltv_check(desc, sp); if (rc) return rc;
   if (!x0 || !x_ref || !u_init || !u_opt || !x_opt || !slack || !fval || !status || !sweeps || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
@@ -645,7 +701,7 @@ int fsaempc_sqp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline*
   Range whole("fsaempc.sqp");
   const bool timing = g_timing.load();
   for (double& v : g_sqp_ms) v = 0;
-  hipError_t e = sqp_init_launch(P, u_init, st);
+  hipError_t e = sqp_init_launch(P, u_init, st, par_values(par), par_stride(par));
   if (e != hipSuccess) return hipfail(e, "sqp_init_launch");
   for (int sweep = 0; sweep < o.max_sweeps; ++sweep) {
     if (timing) { e = hipEventRecord(g_evs[0], st); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
@@ -663,7 +719,7 @@ int fsaempc_sqp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline*
     fsaempc_ltv_desc sub = *desc; sub.batch = cnt;
     { Range r("fsaempc.sqp.build");
       rc = build_qp(&sub, sp, D(c.gx0), D(c.gxr), nullptr, D(c.gu), D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA),
-                    D(c.pred), D(c.Bt), D(c.qc), stream, true); }
+                    D(c.pred), D(c.Bt), D(c.qc), stream, true, par, Iw(c.idx)); }
     if (rc) return rc;
     if (timing) { e = hipEventRecord(g_evs[2], st); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
     fsaempc_qp_desc q{nV, nC, cnt, 0};
@@ -673,7 +729,8 @@ int fsaempc_sqp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline*
     if (rc) return rc;
     if (timing) { e = hipEventRecord(g_evs[3], st); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
     { Range r("fsaempc.sqp.linesearch");
-      e = sqp_linesearch_launch(P, Iw(c.idx), cnt, sweep, D(c.z), D(c.qf), D(c.qc), Iw(c.qflag), Iw(c.qit), D(c.lam), st); }
+      e = sqp_linesearch_launch(P, Iw(c.idx), cnt, sweep, D(c.z), D(c.qf), D(c.qc), Iw(c.qflag), Iw(c.qit), D(c.lam), st,
+                                par_values(par), par_stride(par)); }
     if (e != hipSuccess) return hipfail(e, "sqp_linesearch_launch");
     if (timing) {
       e = hipEventRecord(g_evs[4], st); if (e == hipSuccess) e = hipEventSynchronize(g_evs[4]);
@@ -722,12 +779,17 @@ int fsaempc_cl_pre_batch_device(int model, int N, double dt, double target_vel, 
 
 int fsaempc_cl_plant_batch_device(int model, int N, double dt, int batch, double* cart, double* pid, const double* x_opt,
                                   const int* finished, const int* exitflag, double* u_last, void* stream) {
+  return fsaempc_cl_plant_batch_device_p(model, N, dt, batch, nullptr, cart, pid, x_opt, finished, exitflag, u_last, stream);
+}
+
+int fsaempc_cl_plant_batch_device_p(int model, int N, double dt, int batch, const fsaempc_ltv_params* par, double* cart, double* pid,
+                                    const double* x_opt, const int* finished, const int* exitflag, double* u_last, void* stream) {
   if (!cart || !pid || !x_opt) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
   if (N <= 0 || batch < 0 || !(dt > 0)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
   ClPlantParams P; P.nx = fsaempc_ltv_nx(model); P.N = N; P.batch = batch; P.dt = dt; P.cart = cart; P.pid = pid; P.x_opt = x_opt;
   P.finished = finished; P.exitflag = exitflag; P.u_last = u_last;
-  hipError_t e = cl_plant_launch(P, (hipStream_t)stream);
+  hipError_t e = cl_plant_launch(P, (hipStream_t)stream, par_values(par), par_stride(par));
   if (e != hipSuccess) return hipfail(e, "cl_plant_launch");
   return 0;
 }

@@ -16,7 +16,11 @@ struct LtvParams {
 hipError_t ltv_build_launch(const LtvParams& P, int batch, hipStream_t st, bool exact = false);
 hipError_t ltv_post_launch(int nx, int N, int ns, int batch, const double* z, const double* pred, const double* Bt,
                            const double* qconst, double* u_opt, double* x_opt, double* slack, double* fval, hipStream_t st);
-size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact = false);
+size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact = false, bool par = false);
+// The same build with the constants read from parameter blocks (include/fsaempc.h, FSAEMPC_P_*): workgroup b reads
+// values + inst * stride (stride 0: one block for the batch), inst = idx ? idx[b] : b.
+hipError_t ltv_build_par_launch(const LtvParams& P, const double* values, int stride, const int* idx, int batch, hipStream_t st,
+                                bool exact = false);
 
 // sensitivities: the affine maps of the build in x0 / x_ref (Abar R x nx, Crow nC x nx per instance, column-major),
 // the cotangent of the QP variables of a step (z = [u_opt; slack], zbar = [ubar; sbar] + Bt' xbar, kc columns) and the chain from the

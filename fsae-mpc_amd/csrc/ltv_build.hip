@@ -19,8 +19,8 @@
 
 namespace {
 
-DEVINL void A_kin(const double* x, const Spl& sp, double* A) {  // 5x5 column-major
-  const double lr_ratio = LR / (LR + LF);
+template <class PAR> DEVINL void A_kin(const PAR p, const double* x, const Spl& sp, double* A) {  // 5x5 column-major
+  const double lr_ratio = p.LR_RATIO, LR = p.LR;
   const double k = kappa(sp, x[0]);
   const double td = tan(x[4]);
   const double beta = atan(lr_ratio * td);
@@ -40,14 +40,15 @@ DEVINL void A_kin(const double* x, const Spl& sp, double* A) {  // 5x5 column-ma
 }
 
 // byp = {Fcr, Fcr_d, vr, denom_vr2, x_d_hat, x_d_hat_d, vf, denom_vf2}; A may be null
-DEVINL void A_dyn(const double* x, const Spl& sp, double* A, double* byp) {
+template <class PAR> DEVINL void A_dyn(const PAR p, const double* x, const Spl& sp, double* A, double* byp) {
+  const double LF = p.LF, LR = p.LR, PB = p.PB, PC = p.PC, PD = p.PD, PE = p.PE;
   const double n = x[1], mu = x[2], x_d = x[3], y_d = x[4], th_d = x[5], delta = x[6];
-  const double m = VM, I = VI;
+  const double m = p.M, I = p.IZ;
   const double x_d_hat = x_d + 5 * exp(-x_d / 5);
   const double x_d_hat_d = 1 - exp(-x_d / 5);
   const double alpha_f = delta - atan((y_d + LF * th_d) / x_d_hat);
   const double alpha_r = -atan((y_d - LR * th_d) / x_d_hat);
-  const double Fzf = m * GRAV * LR / (LR + LF), Fzr = m * GRAV * LF / (LR + LF);
+  const double Fzf = p.FZF, Fzr = p.FZR;
   const double af_arg = PB * alpha_f - PE * (PB * alpha_f - atan(PB * alpha_f));
   const double ar_arg = PB * alpha_r - PE * (PB * alpha_r - atan(PB * alpha_r));
   const double Fcf = Fzf * PD * sin(PC * atan(af_arg));
@@ -91,15 +92,15 @@ template <int NX> DEVINL void mmul(const double* A, const double* B, double* C, 
       C[i + j * NX] = s;
     }
 }
-template <int NX> DEVINL void model_A(const double* x, const Spl& sp, double* A) {
-  if (NX == 5) A_kin(x, sp, A); else A_dyn(x, sp, A, nullptr);
+template <int NX, class PAR> DEVINL void model_A(const PAR p, const double* x, const Spl& sp, double* A) {
+  if (NX == 5) A_kin(p, x, sp, A); else A_dyn(p, x, sp, A, nullptr);
 }
 
 // Linearise step k about (xi, ui): writes Ad = I + dt*A, Bd = dt*B, dd = dt*d   (sequential_integration.m:16-18)
 // integ: 0 Euler (euler_*_curvilinear.m:24-30), 1 midpoint rule (rk2_*_curvilinear.m:25-50), 2 classical RK4
 // (rk4_*_curvilinear.m:25-59).  The reference drivers use rk2 for the kinematic and rk4 for the dynamic model
 // (ltvmpc_kinetmatic_curvilinear.m:38, ltvmpc_dynamic_curvilinear.m:38); the others are the alternates kept beside them.
-template <int NX> DEVINL void linearise_step(const double* xi, const double* ui, const Spl& sp, double dt, int integ,
+template <int NX, class PAR> DEVINL void linearise_step(const PAR p, const double* xi, const double* ui, const Spl& sp, double dt, int integ,
                                              double* Ad, double* Bd, double* dd) {
   constexpr int NN = NX * NX;
   double Bc[NX * 2];
@@ -107,16 +108,16 @@ template <int NX> DEVINL void linearise_step(const double* xi, const double* ui,
   Bc[3] = 1.0; Bc[(NX - 1) + NX] = 1.0;  // B_curv_kin.m:12-16 / B_curv_dyn.m:12-18
   double f[NX], Ai[NN], Bi[NX * 2];
   if (integ == 0) {
-    model_f<NX>(xi, ui, sp, f);
-    model_A<NX>(xi, sp, Ai);
+    model_f<NX>(p, xi, ui, sp, f);
+    model_A<NX>(p, xi, sp, Ai);
     for (int j = 0; j < NX * 2; ++j) Bi[j] = Bc[j];
   } else if (integ == 1) {
     double k1[NX], xs[NX], F1[NN], F2[NN], Tm[NN], TB[NX * 2];
-    model_f<NX>(xi, ui, sp, k1);
+    model_f<NX>(p, xi, ui, sp, k1);
     for (int j = 0; j < NX; ++j) xs[j] = xi[j] + k1[j] * dt / 2;
-    model_f<NX>(xs, ui, sp, f);
-    model_A<NX>(xi, sp, F1);
-    model_A<NX>(xs, sp, F2);
+    model_f<NX>(p, xs, ui, sp, f);
+    model_A<NX>(p, xi, sp, F1);
+    model_A<NX>(p, xs, sp, F2);
     for (int j = 0; j < NN; ++j) Tm[j] = F1[j] * dt / 2;
     for (int j = 0; j < NX; ++j) Tm[j + j * NX] += 1;
     mmul<NX>(F2, Tm, Ai, NX);
@@ -125,13 +126,13 @@ template <int NX> DEVINL void linearise_step(const double* xi, const double* ui,
   } else {
     double k1[NX], k2[NX], k3[NX], k4[NX], xs[NX];
     double F[NN], K[NN], Tm[NN], Ks[NN], U[NX * 2], Us[NX * 2], TB[NX * 2];
-    model_f<NX>(xi, ui, sp, k1);
-    model_A<NX>(xi, sp, K);                       // dkdx1
+    model_f<NX>(p, xi, ui, sp, k1);
+    model_A<NX>(p, xi, sp, K);                       // dkdx1
     for (int j = 0; j < NN; ++j) Ks[j] = K[j];
     for (int j = 0; j < NX * 2; ++j) { U[j] = Bc[j]; Us[j] = Bc[j]; }
     for (int j = 0; j < NX; ++j) xs[j] = xi[j] + k1[j] * dt / 2;
-    model_f<NX>(xs, ui, sp, k2);
-    model_A<NX>(xs, sp, F);
+    model_f<NX>(p, xs, ui, sp, k2);
+    model_A<NX>(p, xs, sp, F);
     for (int j = 0; j < NN; ++j) Tm[j] = K[j] * dt / 2;
     for (int j = 0; j < NX; ++j) Tm[j + j * NX] += 1;
     mmul<NX>(F, Tm, K, NX);                        // dkdx2
@@ -140,8 +141,8 @@ template <int NX> DEVINL void linearise_step(const double* xi, const double* ui,
     for (int j = 0; j < NN; ++j) Ks[j] += 2 * K[j];
     for (int j = 0; j < NX * 2; ++j) Us[j] += 2 * U[j];
     for (int j = 0; j < NX; ++j) xs[j] = xi[j] + k2[j] * dt / 2;
-    model_f<NX>(xs, ui, sp, k3);
-    model_A<NX>(xs, sp, F);
+    model_f<NX>(p, xs, ui, sp, k3);
+    model_A<NX>(p, xs, sp, F);
     for (int j = 0; j < NN; ++j) Tm[j] = K[j] * dt / 2;
     for (int j = 0; j < NX; ++j) Tm[j + j * NX] += 1;
     mmul<NX>(F, Tm, K, NX);                        // dkdx3
@@ -150,8 +151,8 @@ template <int NX> DEVINL void linearise_step(const double* xi, const double* ui,
     for (int j = 0; j < NN; ++j) Ks[j] += 2 * K[j];
     for (int j = 0; j < NX * 2; ++j) Us[j] += 2 * U[j];
     for (int j = 0; j < NX; ++j) xs[j] = xi[j] + k3[j] * dt;
-    model_f<NX>(xs, ui, sp, k4);
-    model_A<NX>(xs, sp, F);
+    model_f<NX>(p, xs, ui, sp, k4);
+    model_A<NX>(p, xs, sp, F);
     for (int j = 0; j < NN; ++j) Tm[j] = K[j] * dt;
     for (int j = 0; j < NX; ++j) Tm[j + j * NX] += 1;
     mmul<NX>(F, Tm, K, NX);                        // dkdx4
@@ -174,12 +175,12 @@ template <int NX> DEVINL void linearise_step(const double* xi, const double* ui,
 
 // Exact linearisation of one step of the NLP's rollout: Ad = dPsi/dx, Bd = dPsi/du at (xi, ui), one dual-number pass of psi_step per
 // column (true df/dx including kappa'(s), classical RK4 stage derivatives).
-template <int NX> DEVINL void linearise_exact(const double* xi, const double* ui, const Spl& sp, double dt, int integ, double* Ad, double* Bd) {
+template <int NX, class PAR> DEVINL void linearise_exact(const PAR p, const double* xi, const double* ui, const Spl& sp, double dt, int integ, double* Ad, double* Bd) {
   for (int c = 0; c < NX + 2; ++c) {
     Dl xd[NX], ud[2], xn[NX];
     for (int j = 0; j < NX; ++j) xd[j] = Dl(xi[j], j == c ? 1.0 : 0.0);
     for (int j = 0; j < 2; ++j) ud[j] = Dl(ui[j], NX + j == c ? 1.0 : 0.0);
-    psi_step<NX>(xd, ud, sp, dt, integ, xn);
+    psi_step<NX>(p, xd, ud, sp, dt, integ, xn);
     double* col = c < NX ? Ad + c * NX : Bd + (c - NX) * NX;
     for (int r = 0; r < NX; ++r) col[r] = xn[r].d;
   }
@@ -191,31 +192,37 @@ template <int NX> DEVINL void linearise_exact(const double* xi, const double* ui
 // rollout x_k = Psi(x_{k-1}, u_k) (x_0 = x0), step k is linearised exactly at (x_{k-1}, u_k), Phi(i,i) = Bd_i, every constraint row
 // is linearised at the rollout state it constrains, and pred receives the rollout (the affine offset of the QP, rollout - Phi u_lin,
 // stays internal).
-constexpr double QW[3] = {5, 250, 2000};   // state weights of the cost (ltvmpc_*.m:32); the terminal step carries 10 QW (:33)
+// state weights of the cost (ltvmpc_*.m:32) and the factor the terminal step carries (:33), as the unparameterised VJP chain reads them
+constexpr double QW[3] = {FixedPar::QW[0], FixedPar::QW[1], FixedPar::QW[2]};
+constexpr double QTERM = FixedPar::Q_TERMINAL;
 
 // Step 4a of the build: the coefficients of step k's linearised constraint rows, at the state xl they are linearised at
 // (kinematic: 3 values; dynamic: 16).  Shared by the build and by the affine maps of the sensitivities (ltv_affine_kernel).
-template <int NX> DEVINL void step_coef(const double* xl, const Spl& sp, double* ck) {
+template <int NX, class PAR> DEVINL void step_coef(const PAR p, const double* xl, const Spl& sp, double* ck) {
+  const double LF = p.LF, LR = p.LR;
   if (NX == 5) {
     // kinematic_tyre_linearise_constraints.m:18-32 ; g = v^2 delta/(lr+lf)
-    ck[0] = 2 * xl[3] * xl[4] / (LF + LR);
-    ck[1] = xl[3] * xl[3] / (LF + LR);
-    ck[2] = xl[3] * xl[3] * xl[4] / (LR + LF);  // g0
+    ck[0] = 2 * xl[3] * xl[4] / p.WB;
+    ck[1] = xl[3] * xl[3] / p.WB;
+    ck[2] = xl[3] * xl[3] * xl[4] / p.WB;  // g0
   } else {
     double byp[8];
-    A_dyn(xl, sp, nullptr, byp);
+    A_dyn(p, xl, sp, nullptr, byp);
     const double Fcr = byp[0], Fcr_d = byp[1], vr = byp[2], dvr2 = byp[3], xh = byp[4], xhd = byp[5], vf = byp[6], dvf2 = byp[7];
     // dynamic_slip_linearise_constraints.m:26-30 : rows (alpha_r, alpha_f) coefficients on states 4..7
     ck[0] = dvr2 * vr * xhd / xh; ck[1] = -dvr2 / xh; ck[2] = dvr2 * LR / xh; ck[3] = 0.0;
     ck[4] = dvf2 * vf * xhd / xh; ck[5] = -dvf2 / xh; ck[6] = -dvf2 * LF / xh; ck[7] = 1.0;
     ck[8] = -atan(vr); ck[9] = xl[6] - atan(vf);
     // dynamic_tyre_linearise_constraints.m:41-49 : C_j = dal_j * ck[10..12] on states 4..6
-    ck[10] = -Fcr_d * dvr2 * vr * xhd / xh / 280; ck[11] = Fcr_d * dvr2 / xh / 280; ck[12] = -Fcr_d * dvr2 * LR / xh / 280;
+    ck[10] = -Fcr_d * dvr2 * vr * xhd / xh / p.M; ck[11] = Fcr_d * dvr2 / xh / p.M; ck[12] = -Fcr_d * dvr2 * LR / xh / p.M;
     ck[13] = Fcr; ck[14] = 0; ck[15] = 0;
   }
 }
 
-template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_kernel(LtvParams P) {
+// PAR: the constants (mpc_params.h).  FixedPar: the shipped build, pa is empty.  RtPar: the constants of the instance's block, loaded
+// once through uniform addresses (pa.idx: the batch instance behind this workgroup, for sub-batches).
+template <int NX, bool EXACT, class PAR> __global__ __launch_bounds__(256) void ltv_build_kernel(LtvParams P, typename PAR::Args pa) {
+  const PAR p = par_get<PAR>(pa, blockIdx.x);
   constexpr int NN = NX * NX, NS = (NX == 5) ? 1 : 4, RPK = (NX == 5) ? 6 : 20;  // rows per step
   const int b = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
   const int N = P.N, R = NX * N, nV = 2 * N + NS, nC = RPK * N;
@@ -243,16 +250,18 @@ template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_k
   double* ell = red + nth;               // 24: dac[12], dal[12] of the inscribed 12-gon (dynamic_tyre_linearise_constraints.m:33-39)
   double* colst = ell + 24;              // one column of Bt (R doubles) per wavefront: stage of step 4c
   double* xs = colst + (size_t)(nth >> 6) * R;   // EXACT: rollout x_0 .. x_N ((N + 1) * NX)
+  double* ell0 = xs + (EXACT ? (size_t)(N + 1) * NX : 0);   // runtime constants only: 24 more, ac0[12], al0[12] of the same 12-gon
 
   if (tid < 12) {
     const int j = tid;
     const double th0 = 2 * M_PI * (double)j / 12, th1 = (j + 1 == 12) ? 2 * M_PI : 2 * M_PI * (double)(j + 1) / 12;
-    ell[j] = 9.163 * sin(th1) - 9.163 * sin(th0); ell[12 + j] = 10.0 * cos(th1) - 10.0 * cos(th0);
+    ell[j] = p.ELL_LAT * sin(th1) - p.ELL_LAT * sin(th0); ell[12 + j] = p.ELL_LONG * cos(th1) - p.ELL_LONG * cos(th0);
+    if constexpr (PAR::RT) { ell0[j] = p.ELL_LAT * sin(th0); ell0[12 + j] = p.ELL_LONG * cos(th0); }
   }
   if constexpr (EXACT) {
     if (tid == 0) {
       for (int j = 0; j < NX; ++j) xs[j] = x0[j];
-      for (int k = 0; k < N; ++k) psi_step<NX>(xs + (size_t)k * NX, u_lin + (size_t)k * 2, sp, dt, P.integ, xs + (size_t)(k + 1) * NX);
+      for (int k = 0; k < N; ++k) psi_step<NX>(p, xs + (size_t)k * NX, u_lin + (size_t)k * 2, sp, dt, P.integ, xs + (size_t)(k + 1) * NX);
     }
     __syncthreads();
   }
@@ -262,7 +271,7 @@ template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_k
       const double* xi = xs + (size_t)k * NX;
       const double* ui = u_lin + (size_t)k * 2;
       double* a = Ad + (size_t)k * NN; double* bd = Bd + (size_t)k * NX * 2; double* d = dd + (size_t)k * NX;
-      linearise_exact<NX>(xi, ui, sp, dt, P.integ, a, bd);
+      linearise_exact<NX>(p, xi, ui, sp, dt, P.integ, a, bd);
       for (int r = 0; r < NX; ++r) {     // dd_k = x_k - Ad_k x_{k-1} - Bd_k u_k: the recursion of step 2 reproduces the rollout at u_lin
         double v = xi[NX + r];
         for (int c = 0; c < NX; ++c) v -= a[r + c * NX] * xi[c];
@@ -270,7 +279,7 @@ template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_k
         d[r] = v;
       }
     } else {
-      linearise_step<NX>(x_lin + (size_t)k * NX, u_lin + (size_t)k * 2, sp, dt, P.integ, Ad + (size_t)k * NN, Bd + (size_t)k * NX * 2, dd + (size_t)k * NX);
+      linearise_step<NX>(p, x_lin + (size_t)k * NX, u_lin + (size_t)k * 2, sp, dt, P.integ, Ad + (size_t)k * NN, Bd + (size_t)k * NX * 2, dd + (size_t)k * NX);
     }
   }
   // zero Bt while the linearisation runs
@@ -312,41 +321,50 @@ template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_k
   // ---- 4a. per-step constraint coefficients ----
   for (int k = tid; k < N; k += nth) {
     const double* xl = EXACT ? xs + (size_t)(k + 1) * NX : x_lin + (size_t)k * NX;   // (default: pairing quirk C-8)
-    step_coef<NX>(xl, sp, cc + (size_t)k * CW);
+    step_coef<NX>(p, xl, sp, cc + (size_t)k * CW);
   }
   __syncthreads();
 
+  // (runtime constants: the linearisation above needs the vehicle entries, everything below the limits and the cost; the block is
+  //  read a second time here instead of holding all of it in SGPRs across the linearisation)
+  const PAR pl = par_get_again<PAR>(pa, blockIdx.x);
   // ---- 4b. variable bounds (ltvmpc_*.m:28-29) and constraint bounds ----
   for (int i = tid; i < nV; i += nth) {
-    if (i < 2 * N) { lb[i] = (i & 1) ? -0.4 : -10.0; ub[i] = (i & 1) ? 0.4 : 10.0; }
+    if (i < 2 * N) { lb[i] = (i & 1) ? -pl.U_STEER_MAX : -pl.U_ACC_MAX; ub[i] = (i & 1) ? pl.U_STEER_MAX : pl.U_ACC_MAX; }
     else { lb[i] = 0.0; ub[i] = INFINITY; }
   }
   const int vidx = 3, didx = NX - 1, nidx = 1, scol = 2 * N;
   for (int k = tid; k < N; k += nth) {
     const double cv = aff[k * NX + vidx], cd = aff[k * NX + didx], cn = aff[k * NX + nidx];
-    lbA[k] = 0 - cv;              ubA[k] = INFINITY;
-    lbA[N + k] = -0.4 - cd;       ubA[N + k] = 0.4 - cd;
-    lbA[2 * N + k] = -0.75 - cn;  ubA[2 * N + k] = 1e10;    // *_state_constraints.m:38-39
-    lbA[3 * N + k] = -1e10;       ubA[3 * N + k] = 0.75 - cn;
+    lbA[k] = pl.V_MIN - cv;              ubA[k] = INFINITY;
+    lbA[N + k] = -pl.DELTA_MAX - cd;     ubA[N + k] = pl.DELTA_MAX - cd;
+    lbA[2 * N + k] = -pl.N_MAX - cn;     ubA[2 * N + k] = 1e10;    // *_state_constraints.m:38-39
+    lbA[3 * N + k] = -1e10;             ubA[3 * N + k] = pl.N_MAX - cn;
     const double* xl = EXACT ? xs + (size_t)(k + 1) * NX : x_lin + (size_t)k * NX;
     const double* ck = cc + (size_t)k * CW;
     if (NX == 5) {
       const double cst = ck[2] + ck[0] * (aff[k * NX + 3] - xl[3]) + ck[1] * (aff[k * NX + 4] - xl[4]);
-      lbA[4 * N + k] = -5.0 - cst;  ubA[4 * N + k] = INFINITY;
-      lbA[5 * N + k] = -INFINITY;   ubA[5 * N + k] = 5.0 - cst;
+      lbA[4 * N + k] = -pl.ALAT_MAX - cst;  ubA[4 * N + k] = INFINITY;
+      lbA[5 * N + k] = -INFINITY;          ubA[5 * N + k] = pl.ALAT_MAX - cst;
     } else {
       const double* ul = u_lin + (size_t)k * 2;
       for (int q = 0; q < 2; ++q) {
         double cst = ck[8 + q];
         for (int j = 0; j < 4; ++j) cst += ck[4 * q + j] * (aff[k * NX + 3 + j] - xl[3 + j]);
-        lbA[4 * N + 2 * k + q] = -0.1 - cst; ubA[4 * N + 2 * k + q] = INFINITY;
-        lbA[6 * N + 2 * k + q] = -INFINITY;  ubA[6 * N + 2 * k + q] = 0.1 - cst;
+        lbA[4 * N + 2 * k + q] = -pl.SLIP_MAX - cst; ubA[4 * N + 2 * k + q] = INFINITY;
+        lbA[6 * N + 2 * k + q] = -INFINITY;         ubA[6 * N + 2 * k + q] = pl.SLIP_MAX - cst;
       }
       for (int j = 0; j < 12; ++j) {
-        const double th0 = 2 * M_PI * (double)j / 12, th1 = (j + 1 == 12) ? 2 * M_PI : 2 * M_PI * (double)(j + 1) / 12;
-        const double ac0 = 9.163 * sin(th0), ac1 = 9.163 * sin(th1), al0 = 10.0 * cos(th0), al1 = 10.0 * cos(th1);
-        const double dac = ac1 - ac0, dal = al1 - al0;
-        double cst = (ul[0] - al0) * dac - (ck[13] / 280 - ac0) * dal;
+        double ac0, al0, dac, dal;
+        if constexpr (PAR::RT) {   // the table of this instance's ellipse
+          ac0 = ell0[j]; al0 = ell0[12 + j]; dac = ell[j]; dal = ell[12 + j];
+        } else {                   // constants of the compiler
+          const double th0 = 2 * M_PI * (double)j / 12, th1 = (j + 1 == 12) ? 2 * M_PI : 2 * M_PI * (double)(j + 1) / 12;
+          const double ac1 = pl.ELL_LAT * sin(th1), al1 = pl.ELL_LONG * cos(th1);
+          ac0 = pl.ELL_LAT * sin(th0); al0 = pl.ELL_LONG * cos(th0);
+          dac = ac1 - ac0; dal = al1 - al0;
+        }
+        double cst = (ul[0] - al0) * dac - (ck[13] / pl.M - ac0) * dal;
         for (int jj = 0; jj < 3; ++jj) cst += dal * ck[10 + jj] * (aff[k * NX + 3 + jj] - xl[3 + jj]);
         cst -= dac * ul[0];
         lbA[8 * N + 12 * k + j] = -INFINITY; ubA[8 * N + 12 * k + j] = 0 - cst;
@@ -403,7 +421,7 @@ template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_k
   // entry as a scalar dot product with stride-NX loads: 3.5 of the 10.3 ms of a dynamic N = 60 batch, 0.95 of 2.26 ms on the
   // headline shape.)  Lane (c = l & 15, q = l >> 4): A operand = weight * Bt[row rho][16 I + c], B operand = Bt[row rho][16 J + c],
   // rho = 4 s + q over the weighted rows (k, r) = (rho / 3, rho % 3); result register p holds H[16 I + q + 4 p][16 J + c].
-  const double Qw[3] = {QW[0], QW[1], QW[2]};   // ltvmpc_*.m:32 ; Q_terminal = 10 Q (:33)
+  const double Qw[3] = {pl.QW[0], pl.QW[1], pl.QW[2]};   // ltvmpc_*.m:32 ; Q_terminal = 10 Q (:33)
   {
     const int lane = tid & 63, wv = tid >> 6, nwv = nth >> 6, c = lane & 15, q = lane >> 4;
     const int nU = 2 * N, Tu = (nU + 15) >> 4, npairs = Tu * (Tu + 1) / 2, ksteps = (3 * N + 3) >> 2;
@@ -425,7 +443,7 @@ template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_k
         for (int u = 0; u < UN; ++u) {
           const bool on = k < N;                                  // (rows beyond 3N: zero operands; the address stays inside Bt)
           const int off = (on ? k : 0) * NX + r;
-          const double wq = ((k == N - 1) ? 10.0 : 1.0) * (r == 0 ? Qw[0] : (r == 1 ? Qw[1] : Qw[2]));
+          const double wq = ((k == N - 1) ? pl.Q_TERMINAL : 1.0) * (r == 0 ? Qw[0] : (r == 1 ? Qw[1] : Qw[2]));
           const double a_ = pi_[off], b_ = pj_[off];
           av[u] = (on && oni) ? wq * a_ : 0.0;
           bv[u] = (on && onj) ? b_ : 0.0;
@@ -435,10 +453,10 @@ template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_k
         for (int u = 0; u < UN; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
       }
 #pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int i = 16 * I + q + 4 * p, j = cj;
+      for (int pp = 0; pp < 4; ++pp) {
+        const int i = 16 * I + q + 4 * pp, j = cj;
         if (i < nU && j < nU) {
-          const double v = 2.0 * (acc[p] + (i == j ? 10.0 : 0.0));   // R = [10,10] (ltvmpc_*.m:34)
+          const double v = 2.0 * (acc[pp] + (i == j ? ((i & 1) ? pl.R_STEER : pl.R_ACC) : 0.0));   // R = [10,10] (ltvmpc_*.m:34)
           H[(size_t)i + (size_t)j * nV] = v;
           H[(size_t)j + (size_t)i * nV] = v;
         }
@@ -457,18 +475,20 @@ template <int NX, bool EXACT> __global__ __launch_bounds__(256) void ltv_build_k
     if (i < 2 * N) {
       const double* ci = Bt + (size_t)i * R;
       for (int k = i >> 1; k < N; ++k) {
-        const double wq = (k == N - 1) ? 10.0 : 1.0;
+        const double wq = (k == N - 1) ? pl.Q_TERMINAL : 1.0;
         for (int r = 0; r < 3; ++r) s += ci[k * NX + r] * (wq * Qw[r]) * (aff[k * NX + r] - x_ref[k * NX + r]);
       }
       g[i] = 2 * s;
     } else {
       const int sidx = i - 2 * N;
-      g[i] = (NX == 5) ? 1e8 : (sidx == 0 ? 1e8 : (sidx == 3 ? 1e4 : 1e6));   // R_soft (ltvmpc_*.m:35)
+      g[i] = (NX == 5 || sidx == 0) ? pl.R_SOFT0 : (sidx == 3 ? pl.R_SOFT3 : (sidx == 1 ? pl.R_SOFT1 : pl.R_SOFT2));   // R_soft (ltvmpc_*.m:35)
     }
+    if constexpr (PAR::RT) { if (pl.bad) g[i] = NAN; }   // a block that cannot describe a car: the solve returns -1 for this instance
+
   }
   for (int e = tid; e < 3 * N; e += nth) {
     const int k = e / 3, r = e - 3 * k;
-    const double wq = (k == N - 1) ? 10.0 : 1.0;
+    const double wq = (k == N - 1) ? pl.Q_TERMINAL : 1.0;
     const double rr = aff[k * NX + r] - x_ref[k * NX + r];
     qc_local += rr * (wq * Qw[r]) * rr;
   }
@@ -514,7 +534,7 @@ template <int NX> DEVINL void row_coef(int row, int N, const double* ck, double*
   if (row < 8 * N) { const int q = ((row - 4 * N) % (2 * N)) & 1; for (int j = 0; j < 4; ++j) crow[3 + j] = ck[4 * q + j]; return; }
   const int j = (row - 8 * N) % 12;
   const double th0 = 2 * M_PI * (double)j / 12, th1 = (j + 1 == 12) ? 2 * M_PI : 2 * M_PI * (double)(j + 1) / 12;
-  const double dal = 10.0 * cos(th1) - 10.0 * cos(th0);
+  const double dal = FixedPar::ELL_LONG * cos(th1) - FixedPar::ELL_LONG * cos(th0);
   for (int jj = 0; jj < 3; ++jj) crow[3 + jj] = dal * ck[10 + jj];
 }
 
@@ -529,8 +549,8 @@ template <int NX> __global__ __launch_bounds__(256) void ltv_affine_kernel(LtvPa
   extern __shared__ double sm[];
   double* Ad = sm; double* Bd = Ad + (size_t)N * NN; double* dd = Bd + (size_t)N * NX * 2; double* cc = dd + (size_t)N * NX;
   for (int k = tid; k < N; k += nth) {
-    linearise_step<NX>(x_lin + (size_t)k * NX, u_lin + (size_t)k * 2, sp, P.dt, P.integ, Ad + (size_t)k * NN, Bd + (size_t)k * NX * 2, dd + (size_t)k * NX);
-    step_coef<NX>(x_lin + (size_t)k * NX, sp, cc + (size_t)k * CW);
+    linearise_step<NX>(FixedPar{}, x_lin + (size_t)k * NX, u_lin + (size_t)k * 2, sp, P.dt, P.integ, Ad + (size_t)k * NN, Bd + (size_t)k * NX * 2, dd + (size_t)k * NX);
+    step_coef<NX>(FixedPar{}, x_lin + (size_t)k * NX, sp, cc + (size_t)k * CW);
   }
   __syncthreads();
   double* Ab = Abar + (size_t)b * R * NX;
@@ -590,7 +610,7 @@ template <int NX> __global__ __launch_bounds__(256) void ltv_vjp_chain_kernel(in
     if (r < 3) {
       double G = 0.0;
       for (int i = 0; i < 2 * N; ++i) G += Btb[e + (size_t)i * R] * gb[i];
-      const double w = ((k == N - 1) ? 10.0 : 1.0) * QW[r];
+      const double w = ((k == N - 1) ? QTERM : 1.0) * QW[r];
       const double d = pred[(size_t)b * R + e] - x_ref[(size_t)b * R + e];
       const double t = 2.0 * w * G + 2.0 * fb * w * d;
       p += t; xr = -t;
@@ -620,20 +640,36 @@ template <int NX> __global__ __launch_bounds__(256) void ltv_vjp_chain_kernel(in
 
 }  // namespace
 
-size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact) {
+size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact, bool par) {
   const int CW = (nx == 5) ? 3 : 16;
   return ((size_t)N * nx * nx + (size_t)N * nx * 2 + (size_t)N * nx + (size_t)nx * N + (size_t)N * CW + threads + 24 +
           (size_t)(threads / 64) * nx * N +    // the per-wavefront column stage of step 4c
-          (exact ? (size_t)(N + 1) * nx : 0)) * sizeof(double);   // the rollout of the NLP build
+          (exact ? (size_t)(N + 1) * nx : 0) +                     // the rollout of the NLP build
+          (par ? 24 : 0)) * sizeof(double);                       // the second half of the ellipse table of a parameter block
 }
 
 template <int NX, bool EXACT> static hipError_t launch_build(const LtvParams& P, int batch, hipStream_t st) {
   const int threads = 256;
   const size_t lds = ltv_build_lds_bytes(NX, P.N, threads, EXACT);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ltv_build_kernel<NX, EXACT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ltv_build_kernel<NX, EXACT, FixedPar>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((ltv_build_kernel<NX, EXACT>), dim3(batch), dim3(threads), lds, st, P);
+  hipLaunchKernelGGL((ltv_build_kernel<NX, EXACT, FixedPar>), dim3(batch), dim3(threads), lds, st, P, NoParArgs{});
   return hipGetLastError();
+}
+
+template <int NX, bool EXACT> static hipError_t launch_build_par(const LtvParams& P, const ParArgs& pa, int batch, hipStream_t st) {
+  const int threads = 256;
+  const size_t lds = ltv_build_lds_bytes(NX, P.N, threads, EXACT, true);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ltv_build_kernel<NX, EXACT, RtPar>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((ltv_build_kernel<NX, EXACT, RtPar>), dim3(batch), dim3(threads), lds, st, P, pa);
+  return hipGetLastError();
+}
+
+hipError_t ltv_build_par_launch(const LtvParams& P, const double* values, int stride, const int* idx, int batch, hipStream_t st, bool exact) {
+  const ParArgs pa{values, stride, idx};
+  if (exact) return P.nx == 5 ? launch_build_par<5, true>(P, pa, batch, st) : launch_build_par<7, true>(P, pa, batch, st);
+  return P.nx == 5 ? launch_build_par<5, false>(P, pa, batch, st) : launch_build_par<7, false>(P, pa, batch, st);
 }
 
 hipError_t ltv_build_launch(const LtvParams& P, int batch, hipStream_t st, bool exact) {

@@ -5,14 +5,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include "mpc_params.h"
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
 typedef double v4d __attribute__((ext_vector_type(4)));
-constexpr double LR = 0.6183, LF = 0.8672;
-constexpr double VM = 280, VI = 200, GRAV = 9.81;
-constexpr double PB = 12.56, PC = 1.38, PD = 1.60, PE = -0.58;
 
 struct Spl { int M; double dl; const double* xP; const double* yP; };
 
@@ -75,8 +72,9 @@ template <class T> DEVINL T kappa(const Spl& sp, T s) {
 }
 
 // ---- kinematic model (f_curv_kin.m:13-29, A_curv_kin.m:15-55) ----
-template <class T> DEVINL void f_kin(const T* x, const T* u, const Spl& sp, T* f) {
-  const double lr_ratio = LR / (LR + LF);
+// (every model function takes the constants from a policy object p: mpc_params.h)
+template <class T, class PAR> DEVINL void f_kin(const PAR p, const T* x, const T* u, const Spl& sp, T* f) {
+  const double lr_ratio = p.LR_RATIO, LR = p.LR;
   const T k = kappa(sp, x[0]);
   const T beta = atan(lr_ratio * tan(x[4]));
   const T s_mb = sin(x[2] + beta), c_mb = cos(x[2] + beta);
@@ -88,7 +86,8 @@ template <class T> DEVINL void f_kin(const T* x, const T* u, const Spl& sp, T* f
   f[4] = u[1];
 }
 // ---- dynamic model (f_curv_dyn.m:13-62, A_curv_dyn.m:15-106) ----
-template <class T> DEVINL void f_dyn(const T* x, const T* u, const Spl& sp, T* f) {
+template <class T, class PAR> DEVINL void f_dyn(const PAR p, const T* x, const T* u, const Spl& sp, T* f) {
+  const double VM = p.M, VI = p.IZ, LF = p.LF, LR = p.LR, PB = p.PB, PC = p.PC, PD = p.PD, PE = p.PE;
   const T n = x[1], mu = x[2], x_d = x[3], y_d = x[4], th_d = x[5], delta = x[6];
   const T Fx = u[0] * VM;
   const T x_d_hat = x_d + 5 * exp(-x_d / 5);
@@ -96,7 +95,7 @@ template <class T> DEVINL void f_dyn(const T* x, const T* u, const Spl& sp, T* f
   const T denom_nk = 1.0 / (1.0 - n * k);
   const T alpha_f = delta - atan((y_d + LF * th_d) / x_d_hat);
   const T alpha_r = -atan((y_d - LR * th_d) / x_d_hat);
-  const double Fzf = VM * GRAV * LR / (LR + LF), Fzr = VM * GRAV * LF / (LR + LF);
+  const double Fzf = p.FZF, Fzr = p.FZR;
   const T Fcf = Fzf * PD * sin(PC * atan(PB * alpha_f - PE * (PB * alpha_f - atan(PB * alpha_f))));
   const T Fcr = Fzr * PD * sin(PC * atan(PB * alpha_r - PE * (PB * alpha_r - atan(PB * alpha_r))));
   f[0] = (x_d * cos(mu) - y_d * sin(mu)) * denom_nk;
@@ -107,29 +106,29 @@ template <class T> DEVINL void f_dyn(const T* x, const T* u, const Spl& sp, T* f
   f[5] = (LF * Fcf * cos(delta) - LR * Fcr) / VI;
   f[6] = u[1];
 }
-template <int NX, class T> DEVINL void model_f(const T* x, const T* u, const Spl& sp, T* f) {
-  if (NX == 5) f_kin(x, u, sp, f); else f_dyn(x, u, sp, f);
+template <int NX, class T, class PAR> DEVINL void model_f(const PAR p, const T* x, const T* u, const Spl& sp, T* f) {
+  if (NX == 5) f_kin(p, x, u, sp, f); else f_dyn(p, x, u, sp, f);
 }
 // One step of the NLP's rollout x+ = Psi(x, u) (integ: 0 Euler, 1 midpoint RK2, 2 classical RK4).  T = Dl gives the derivative of
 // the step along the seeded direction: the exact linearisation of the NLP build (ltv_build.hip, EXACT = true).
-template <int NX, class T> DEVINL void psi_step(const T* x, const T* u, const Spl& sp, double dt, int integ, T* xn) {
+template <int NX, class T, class PAR> DEVINL void psi_step(const PAR p, const T* x, const T* u, const Spl& sp, double dt, int integ, T* xn) {
   T k1[NX], xs[NX];
-  model_f<NX>(x, u, sp, k1);
+  model_f<NX>(p, x, u, sp, k1);
   if (integ == 0) {
     for (int j = 0; j < NX; ++j) xn[j] = x[j] + dt * k1[j];
   } else if (integ == 1) {
     T k2[NX];
     for (int j = 0; j < NX; ++j) xs[j] = x[j] + k1[j] * dt / 2;
-    model_f<NX>(xs, u, sp, k2);
+    model_f<NX>(p, xs, u, sp, k2);
     for (int j = 0; j < NX; ++j) xn[j] = x[j] + dt * k2[j];
   } else {
     T k2[NX], k3[NX], k4[NX];
     for (int j = 0; j < NX; ++j) xs[j] = x[j] + k1[j] * dt / 2;
-    model_f<NX>(xs, u, sp, k2);
+    model_f<NX>(p, xs, u, sp, k2);
     for (int j = 0; j < NX; ++j) xs[j] = x[j] + k2[j] * dt / 2;
-    model_f<NX>(xs, u, sp, k3);
+    model_f<NX>(p, xs, u, sp, k3);
     for (int j = 0; j < NX; ++j) xs[j] = x[j] + k3[j] * dt;
-    model_f<NX>(xs, u, sp, k4);
+    model_f<NX>(p, xs, u, sp, k4);
     for (int j = 0; j < NX; ++j) xn[j] = x[j] + dt * ((k1[j] + 2 * k2[j] + 2 * k3[j] + k4[j]) / 6);
   }
 }

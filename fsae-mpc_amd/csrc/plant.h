@@ -23,5 +23,6 @@ struct ClPlantParams {
   double* u_last;          // optional batch x 2: actuator rates of the last sub-step
 };
 hipError_t cl_pre_launch(const ClPreParams& P, hipStream_t st);
-hipError_t cl_plant_launch(const ClPlantParams& P, hipStream_t st);
+// par (optional): parameter blocks (include/fsaempc.h FSAEMPC_P_*), car b reads par + b * par_stride; null: f_cart_dyn.m's own constants
+hipError_t cl_plant_launch(const ClPlantParams& P, hipStream_t st, const double* par = nullptr, int par_stride = 0);
 hipError_t cl_accept_launch(int len_x, int len_u, int batch, const double* x_new, const double* u_new, const int* exitflag, double* x_keep, double* u_keep, hipStream_t st);

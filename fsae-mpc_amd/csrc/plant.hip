@@ -11,10 +11,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "plant.h"
+#include "mpc_params.h"
 
 namespace {
 
-#define DEVINL __device__ __forceinline__
 struct Spl { int M; double dl; const double* xP; const double* yP; };
 
 DEVINL double mmod(double a, double b) { return a - floor(a / b) * b; }
@@ -103,13 +103,14 @@ __global__ void cl_pre_kernel(ClPreParams P) {
   }
 }
 
-DEVINL void f_cart_dyn(const double* x, const double* u, double* f) {
-  const double m = 280, I = 200, lr = 0.6183, lf = 0.8672, g = 9.81;
+// (the car's constants come from a policy object p, mpc_params.h: FixedPar = f_cart_dyn.m's own, RtPar = the car's block)
+template <class PAR> DEVINL void f_cart_dyn(const PAR p, const double* x, const double* u, double* f) {
+  const double m = p.M, I = p.IZ, lr = p.LR, lf = p.LF;
   const double theta = x[2], x_d = x[3], y_d = x[4], theta_d = x[5], delta = x[6];
   const double alpha_f = delta - atan((y_d + lf * theta_d) / (x_d + 0.01));
   const double alpha_r = -atan((y_d - lr * theta_d) / (x_d + 0.01));
-  const double Fzf = m * g * lr / (lr + lf), Fzr = m * g * lf / (lr + lf);
-  const double B = 12.56, C = 1.38, D = 1.60, E = -0.58;
+  const double Fzf = p.FZF, Fzr = p.FZR;
+  const double B = p.PB, C = p.PC, D = p.PD, E = p.PE;
   const double Fcf = Fzf * D * sin(C * atan(B * alpha_f - E * (B * alpha_f - atan(B * alpha_f))));
   const double Fcr = Fzr * D * sin(C * atan(B * alpha_r - E * (B * alpha_r - atan(B * alpha_r))));
   f[0] = x_d * cos(theta) - y_d * sin(theta);
@@ -121,20 +122,20 @@ DEVINL void f_cart_dyn(const double* x, const double* u, double* f) {
   f[6] = u[1];
 }
 
-DEVINL void integrate_cart_dyn(double* x, const double* u, double dt) {
+template <class PAR> DEVINL void integrate_cart_dyn(const PAR p, double* x, const double* u, double dt) {
   double k1[7], k2[7], k3[7], k4[7], k5[7], k6[7], xs[7];
-  f_cart_dyn(x, u, k1);
+  f_cart_dyn(p, x, u, k1);
   for (int i = 0; i < 7; ++i) xs[i] = x[i] + k1[i] * dt / 2;
-  f_cart_dyn(xs, u, k2);
+  f_cart_dyn(p, xs, u, k2);
   for (int i = 0; i < 7; ++i) xs[i] = x[i] + k1[i] * dt / 4 + k2[i] * dt / 8;
-  f_cart_dyn(xs, u, k3);
+  f_cart_dyn(p, xs, u, k3);
   for (int i = 0; i < 7; ++i) xs[i] = x[i] - k2[i] * dt + 2 * k3[i] * dt;
-  f_cart_dyn(xs, u, k4);
+  f_cart_dyn(p, xs, u, k4);
   for (int i = 0; i < 7; ++i) xs[i] = x[i] + 7.0 / 27 * k2[i] * dt + 10.0 / 27 * k2[i] * dt + k4[i] * dt / 27;
-  f_cart_dyn(xs, u, k5);
+  f_cart_dyn(p, xs, u, k5);
   for (int i = 0; i < 7; ++i)
     xs[i] = x[i] + 28.0 / 625 * k1[i] * dt - k2[i] * dt / 5 + 546.0 / 625 * k3[i] * dt + 54.0 / 625 * k4[i] * dt - 378.0 / 625 * k5[i] * dt;
-  f_cart_dyn(xs, u, k6);
+  f_cart_dyn(p, xs, u, k6);
   for (int i = 0; i < 7; ++i) x[i] = x[i] + dt * (k1[i] / 24 + 5.0 / 48 * k4[i] + 27.0 / 56 * k5[i] + 125.0 / 336 * k6[i]);
 }
 
@@ -148,9 +149,16 @@ DEVINL double pid(double target, double current, double kp, double ki, double kd
   return output;
 }
 
-__global__ void cl_plant_kernel(ClPlantParams P) {
+// PAR = RtPar: car b drives with the block pa.values + b * pa.stride (one car per lane: per-lane loads); a block that cannot
+// describe a car holds it.
+template <class PAR> __global__ void cl_plant_kernel(ClPlantParams P, typename PAR::Args pa) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= P.batch) return;
+  PAR p;
+  if constexpr (PAR::RT) {
+    p = par_load(pa.values + (size_t)b * (size_t)pa.stride);
+    if (p.bad) return;
+  }
   if (P.finished && P.finished[b]) return;        // the reference leaves the loop when the lap is complete
   // The reference keeps driving on whatever plan the solver returned, whatever its exit flag (main.m:163-175); `exitflag`
   // (optional) only holds a car when the caller asks for it with a flag < -100 (not a solver outcome).
@@ -162,9 +170,9 @@ __global__ void cl_plant_kernel(ClPlantParams P) {
   const double v_ref = xo[3], delta_ref = xo[P.nx - 1];     // main.m:167-168 (x_opt(4), x_opt(N_x))
   if (!(fabs(v_ref) < INFINITY) || !(fabs(delta_ref) < INFINITY)) return;   // no finite plan at all: hold the car
   for (int j = 0; j < 10; ++j) {                             // main.m:171-175
-    u[0] = pid(v_ref, x[3], 16000.0, 0.0, 0.0, 2800.0, st);
-    u[1] = pid(delta_ref, x[6], 80.0, 0.0, 0.0, 0.8, st + 2);
-    integrate_cart_dyn(x, u, P.dt / 10);
+    u[0] = pid(v_ref, x[3], p.PID_KP_V, 0.0, 0.0, p.PID_MAX_F, st);
+    u[1] = pid(delta_ref, x[6], p.PID_KP_D, 0.0, 0.0, p.PID_MAX_DRATE, st + 2);
+    integrate_cart_dyn(p, x, u, P.dt / 10);
   }
   for (int i = 0; i < 7; ++i) P.cart[(size_t)b * 7 + i] = x[i];
   for (int i = 0; i < 4; ++i) P.pid[(size_t)b * 4 + i] = st[i];
@@ -199,8 +207,9 @@ hipError_t cl_pre_launch(const ClPreParams& P, hipStream_t st) {
   hipLaunchKernelGGL(cl_pre_kernel, dim3((P.batch + 63) / 64), dim3(64), 0, st, P);
   return hipGetLastError();
 }
-hipError_t cl_plant_launch(const ClPlantParams& P, hipStream_t st) {
+hipError_t cl_plant_launch(const ClPlantParams& P, hipStream_t st, const double* par, int par_stride) {
   if (P.batch == 0) return hipSuccess;
-  hipLaunchKernelGGL(cl_plant_kernel, dim3((P.batch + 63) / 64), dim3(64), 0, st, P);
+  if (par) hipLaunchKernelGGL(cl_plant_kernel<RtPar>, dim3((P.batch + 63) / 64), dim3(64), 0, st, P, ParArgs{par, par_stride, nullptr});
+  else hipLaunchKernelGGL(cl_plant_kernel<FixedPar>, dim3((P.batch + 63) / 64), dim3(64), 0, st, P, NoParArgs{});
   return hipGetLastError();
 }

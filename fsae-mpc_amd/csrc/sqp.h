@@ -20,11 +20,14 @@ struct SqpParams {
 // status of an instance still in the batch
 constexpr int SQP_RUNNING = 3;
 
-hipError_t sqp_init_launch(const SqpParams& P, const double* u_init, hipStream_t st);
+// par (optional; here and in sqp_linesearch_launch): parameter blocks of the batch (include/fsaempc.h FSAEMPC_P_*), instance i reads
+// par + i * par_stride; null: the kernels with the reference's constants compiled in
+hipError_t sqp_init_launch(const SqpParams& P, const double* u_init, hipStream_t st, const double* par = nullptr, int par_stride = 0);
 hipError_t sqp_compact_launch(const int* status, int B, int* idx, int* count, hipStream_t st);
 hipError_t sqp_gather_launch(const SqpParams& P, const int* idx, int cnt, double* gx0, double* gxref, double* gu, double* xinit, int nV,
                              hipStream_t st);
 // One launch per sweep: line search, penalty update, status, scatter of the accepted iterate.  Sub-batch arrays (cnt instances,
 // instance b is idx[b] of the batch): QP solution z (nV), its objective fval_qp (without the constant) + qconst, flag, iterations, lambda.
 hipError_t sqp_linesearch_launch(const SqpParams& P, const int* idx, int cnt, int sweep, const double* z, const double* fval_qp,
-                                 const double* qconst, const int* flag, const int* iter, const double* lambda, hipStream_t st);
+                                 const double* qconst, const int* flag, const int* iter, const double* lambda, hipStream_t st,
+                                 const double* par = nullptr, int par_stride = 0);

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import LtvDesc, QpAux, QpDesc, Spline, check, default_opts, lib
+from ._lib import LtvDesc, ParamBlock, QpAux, QpDesc, Spline, check, default_opts, lib
 from .synthetic import DYNAMIC, KINEMATIC
 
 
@@ -21,7 +21,9 @@ class LtvBatch:
     """Device-resident batched LTV-MPC step (one call = linearise + condense + solve + post-solve for
     `batch` independent instances).  Inputs/outputs are torch tensors on the GPU."""
 
-    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1):
+    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1, params=None):
+        """params: None (the reference's constants, compiled into the kernels), or a block of vehicle / cost / limit parameters
+        (fsaempc.default_params, PARAM_INDEX): (32,) shared by the batch or (batch, 32) per instance, numpy or a device tensor."""
         import torch
         self.torch = torch
         self.model, self.N, self.dt, self.batch = model, N, float(dt), batch
@@ -34,6 +36,12 @@ class LtvBatch:
         self.opts = options if options is not None else default_opts()
         self._ws = None
         self._qp = None
+        self.params = None
+        self.set_params(params)
+
+    def set_params(self, params):
+        """Swaps the parameter block (None: back to the compiled-in constants); nothing else of the batch object is rebuilt."""
+        self.params = ParamBlock(params, self.batch, self.device) if params is not None else None
 
     def _f64(self, *shape):
         return self.torch.empty(shape, dtype=self.torch.float64, device=self.device)
@@ -48,17 +56,22 @@ class LtvBatch:
                  lbA=self._f64(B, nC), ubA=self._f64(B, nC), pred=self._f64(B, N * nx), Bt=self._f64(B, nV, N * nx),
                  const=self._f64(B))
         P = lambda t: C.c_void_p(t.data_ptr())
-        rc = lib().fsaempc_ltv_build_qp_batch_device(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(x_lin), P(u_lin),
-                                                     P(q["H"]), P(q["g"]), P(q["A"]), P(q["lb"]), P(q["ub"]), P(q["lbA"]), P(q["ubA"]),
-                                                     P(q["pred"]), P(q["Bt"]), P(q["const"]), self._stream(stream))
+        out = (P(q["H"]), P(q["g"]), P(q["A"]), P(q["lb"]), P(q["ub"]), P(q["lbA"]), P(q["ubA"]), P(q["pred"]), P(q["Bt"]), P(q["const"]))
+        if self.params is not None:
+            rc = lib().fsaempc_ltv_build_qp_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref(), P(x0), P(x_ref), P(x_lin),
+                                                           P(u_lin), *out, self._stream(stream))
+        else:
+            rc = lib().fsaempc_ltv_build_qp_batch_device(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(x_lin), P(u_lin), *out,
+                                                         self._stream(stream))
         check(rc, "fsaempc_ltv_build_qp_batch_device")
         return q
 
-    def step(self, x0, x_ref, x_lin, u_lin, stream=None, want_aux=False, x_init=None, difficulty=None):
+    def step(self, x0, x_ref, x_lin, u_lin, stream=None, want_aux=False, x_init=None, difficulty=None, want_lambda=False):
         """Fused step.  Returns dict(u_opt (B,2N), x_opt (B,nx*N), slack (B,ns), fval, exitflag, iter); want_aux adds the solve's
         per-instance diagnostics `kkt` (achieved relative KKT residual) and `polished` (> 0: the returned point is the vertex); x_init
         (batch, nV): optional starting point of the interior-point solve (fsaempc_qp_aux.x_init); difficulty (batch,) int32: optional
-        effort estimate per instance for the launch order (fsaempc_qp_aux.difficulty)."""
+        effort estimate per instance for the launch order (fsaempc_qp_aux.difficulty); want_lambda adds `lam` (B, nV + nC), the multipliers
+        of the step's QP (variables [u_opt; slack], layout of fsaempc_qp_solve_batch_device)."""
         torch = self.torch
         B = self.batch
         need = lib().fsaempc_ltv_workspace_bytes(C.byref(self.desc))
@@ -72,6 +85,9 @@ class LtvBatch:
         if want_aux:
             out["kkt"] = self._f64(B)
             out["polished"] = torch.empty(B, dtype=torch.int32, device=self.device)
+        if want_lambda:
+            out["lam"] = self._f64(B, self.nV + self.nC)
+        lam = P(out["lam"]) if want_lambda else None
         if x_init is not None and (x_init.dtype != torch.float64 or not x_init.is_contiguous() or tuple(x_init.shape) != (B, self.nV)):
             raise ValueError("x_init must be a contiguous float64 (batch, nV) tensor on the GPU")
         xi = P(x_init) if x_init is not None else None   # starting point of the solve in the QP's variables [u (2N); slacks]
@@ -79,9 +95,20 @@ class LtvBatch:
             raise ValueError("difficulty must be a contiguous int32 (batch,) tensor on the GPU")
         df = P(difficulty) if difficulty is not None else None
         aux = QpAux(P(out["kkt"]), P(out["polished"]), xi, df) if want_aux else QpAux(None, None, xi, df)
-        rc = lib().fsaempc_ltv_step_batch_device_aux(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(x_lin), P(u_lin), C.byref(self.opts),
-                                                     P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]), P(out["exitflag"]), P(out["iter"]),
-                                                     C.byref(aux), P(self._ws), C.c_longlong(self._ws.numel() * 8), self._stream(stream))
+        if self.params is not None:
+            rc = lib().fsaempc_ltv_step_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref(), P(x0), P(x_ref), P(x_lin), P(u_lin),
+                                                       C.byref(self.opts), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]),
+                                                       P(out["exitflag"]), P(out["iter"]), lam, C.byref(aux), P(self._ws),
+                                                       C.c_longlong(self._ws.numel() * 8), self._stream(stream))
+        elif want_lambda:
+            rc = lib().fsaempc_ltv_step_batch_device_lambda(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(x_lin), P(u_lin), C.byref(self.opts),
+                                                            P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]), P(out["exitflag"]),
+                                                            P(out["iter"]), lam, C.byref(aux), P(self._ws), C.c_longlong(self._ws.numel() * 8),
+                                                            self._stream(stream))
+        else:
+            rc = lib().fsaempc_ltv_step_batch_device_aux(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(x_lin), P(u_lin), C.byref(self.opts),
+                                                         P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]), P(out["exitflag"]), P(out["iter"]),
+                                                         C.byref(aux), P(self._ws), C.c_longlong(self._ws.numel() * 8), self._stream(stream))
         check(rc, "fsaempc_ltv_step_batch_device_aux")
         return out
 

@@ -101,6 +101,13 @@ class QpFunction(torch.autograd.Function):
         return r.get("H"), r["g"], r.get("A"), r["lb"], r["ub"], r["lbA"], r["ubA"], None, None
 
 
+def _no_params(batch, what):
+    """The affine maps and the VJP kernels carry the reference's constants: refuse a batch with a parameter block instead of
+    differentiating a different problem."""
+    if getattr(batch, "params", None) is not None:
+        raise NotImplementedError("%s is not available for an LtvBatch with a parameter block (set_params(None) first)" % what)
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
 
@@ -112,6 +119,7 @@ def _stream(batch, stream):
 def ltv_step_lambda(batch, x0, x_ref, x_lin, u_lin, stream=None):
     """The fused step of `batch` (an LtvBatch) that also returns its QP's multipliers: dict(u_opt, x_opt, slack, fval, exitflag, iter,
     kkt, polished, lam (B, nV+nC)).  u_opt, x_opt, fval are those of LtvBatch.step on the same inputs."""
+    _no_params(batch, "ltv_step_lambda")
     B = batch.batch
     need = lib().fsaempc_ltv_workspace_bytes(C.byref(batch.desc))
     if need < 0:
@@ -135,6 +143,7 @@ def ltv_step_lambda(batch, x0, x_ref, x_lin, u_lin, stream=None):
 def ltv_step_affine_maps(batch, x_lin, u_lin, stream=None):
     """Abar (B, nx, nx N) and Crow (B, nx, nC): the memory of the column-major nx N x nx and nC x nx matrices of
     fsaempc_ltv_affine_maps_batch_device (Abar[b, j, e] = d pred_e / d x0_j; Crow[b, j, r] = coefficient of row r on state j)."""
+    _no_params(batch, "ltv_step_affine_maps")
     B = batch.batch
     Abar = torch.empty((B, batch.nx, batch.nx * batch.N), dtype=torch.float64, device=batch.device)
     Crow = torch.empty((B, batch.nx, batch.nC), dtype=torch.float64, device=batch.device)
@@ -147,6 +156,7 @@ def ltv_step_affine_maps(batch, x_lin, u_lin, stream=None):
 def ltv_step_vjp(batch, fwd, x0, x_ref, x_lin, u_lin, ubar=None, xbar=None, sbar=None, fbar=None, want_xref=True, stream=None):
     """VJP of the step in x0 and x_ref.  fwd: the dict of ltv_step_lambda on the same inputs.  Cotangents (B, 2N) / (B, nx N) / (B, ns)
     / (B,) for one column, or with a column axis (B, k, *) / (B, k); None = 0.  Returns dict(x0 (B[,k],nx), x_ref (B[,k],nx N), status)."""
+    _no_params(batch, "ltv_step_vjp")
     B, N, nx = batch.batch, batch.N, batch.nx
     given = [t for t in (ubar, xbar, sbar) if t is not None]
     cols = bool(given) and given[0].dim() == 3 or (fbar is not None and fbar.dim() == 2)
@@ -185,6 +195,7 @@ class LtvStepFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, batch, x0, x_ref, x_lin, u_lin, status_out=None):
+        _no_params(batch, "LtvStepFunction")
         x0, x_ref, x_lin, u_lin = (t.detach().contiguous() for t in (x0, x_ref, x_lin, u_lin))
         fwd = ltv_step_lambda(batch, x0, x_ref, x_lin, u_lin)
         ctx.batch, ctx.fwd, ctx.status_out = batch, fwd, status_out
@@ -211,6 +222,7 @@ def ltv_step_diff(batch, x0, x_ref, x_lin, u_lin, status_out=None):
 def feedback_gain(batch, x0, x_ref, x_lin, u_lin):
     """The local feedback law of the step: K (B, 2, nx) = d u_opt[:2] / d x0 (the first step's two inputs), as two VJP columns, and
     the per-instance status (B,) (negative: K is zero)."""
+    _no_params(batch, "feedback_gain")
     B = batch.batch
     fwd = ltv_step_lambda(batch, x0, x_ref, x_lin, u_lin)
     ubar = torch.zeros((B, 2, 2 * batch.N), dtype=torch.float64, device=batch.device)

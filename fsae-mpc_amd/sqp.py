@@ -3,7 +3,7 @@ rollout of the model as its dynamics, solved per instance by a Gauss-Newton SQP 
 search and per-instance termination.  All compute runs on the MI355X through libfsaempc.so (fsaempc_sqp_batch_device)."""
 import ctypes as C
 
-from ._lib import LtvDesc, QpOpts, SqpAux, Spline, check, default_opts, lib, sqp_default_opts
+from ._lib import LtvDesc, ParamBlock, QpOpts, SqpAux, Spline, check, default_opts, lib, sqp_default_opts
 from .ltvmpc import dims
 
 STATUS = {0: "converged", 1: "sweep limit", 2: "no step accepted", -1: "QP failed", -2: "QP infeasible"}
@@ -12,7 +12,7 @@ STATUS = {0: "converged", 1: "sweep limit", 2: "no step accepted", -1: "QP faile
 class SqpBatch:
     """Device-resident batched SQP.  Inputs / outputs are torch tensors on the GPU, laid out as for LtvBatch.step."""
 
-    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1):
+    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1, params=None):
         import torch
         self.torch = torch
         self.model, self.N, self.dt, self.batch = model, N, float(dt), batch
@@ -24,6 +24,13 @@ class SqpBatch:
         self.desc = LtvDesc(model, N, batch, self.dt, integrator)   # integrator: -1 model default (RK2 kin. / RK4 dyn.), 0 Euler, 1 RK2, 2 RK4
         self.opts = options if options is not None else default_opts()
         self._ws = None
+        self.params = None
+        self.set_params(params)
+
+    def set_params(self, params):
+        """The parameter block of the batch, as for LtvBatch: None, (32,) or (batch, 32); read by the build, the rollouts and the
+        line search."""
+        self.params = ParamBlock(params, self.batch, self.device) if params is not None else None
 
     def _f64(self, *shape):
         return self.torch.empty(shape, dtype=self.torch.float64, device=self.device)
@@ -40,9 +47,13 @@ class SqpBatch:
         q = dict(H=self._f64(B, nV, nV), g=self._f64(B, nV), A=self._f64(B, nV, nC), lb=self._f64(B, nV), ub=self._f64(B, nV),
                  lbA=self._f64(B, nC), ubA=self._f64(B, nC), pred=self._f64(B, N * nx), Bt=self._f64(B, nV, N * nx), const=self._f64(B))
         P = lambda t: C.c_void_p(t.data_ptr())
-        rc = lib().fsaempc_nlp_build_qp_batch_device(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(u_lin),
-                                                     P(q["H"]), P(q["g"]), P(q["A"]), P(q["lb"]), P(q["ub"]), P(q["lbA"]), P(q["ubA"]),
-                                                     P(q["pred"]), P(q["Bt"]), P(q["const"]), self._stream(stream))
+        out = (P(q["H"]), P(q["g"]), P(q["A"]), P(q["lb"]), P(q["ub"]), P(q["lbA"]), P(q["ubA"]), P(q["pred"]), P(q["Bt"]), P(q["const"]))
+        if self.params is not None:
+            rc = lib().fsaempc_nlp_build_qp_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref(), P(x0), P(x_ref), P(u_lin),
+                                                           *out, self._stream(stream))
+        else:
+            rc = lib().fsaempc_nlp_build_qp_batch_device(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(u_lin), *out,
+                                                         self._stream(stream))
         check(rc, "fsaempc_nlp_build_qp_batch_device")
         return q
 
@@ -72,9 +83,12 @@ class SqpBatch:
                    step_norm=self._f64(B), hard_viol=self._f64(B), merit=self._f64(B, o.max_sweeps))
         P = lambda t: C.c_void_p(t.data_ptr())
         aux = SqpAux(P(out["lambda"]), P(out["qp_iter"]), P(out["step_norm"]), P(out["hard_viol"]), P(out["merit"]))
-        rc = lib().fsaempc_sqp_batch_device(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(u_init), C.byref(self.opts), C.byref(o),
-                                            P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]), P(out["status"]), P(out["sweeps"]),
-                                            C.byref(aux), P(self._ws), C.c_longlong(self._ws.numel() * 8), self._stream(stream))
+        tail = (C.byref(self.opts), C.byref(o), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]), P(out["status"]),
+                P(out["sweeps"]), C.byref(aux), P(self._ws), C.c_longlong(self._ws.numel() * 8), self._stream(stream))
+        if self.params is not None:
+            rc = lib().fsaempc_sqp_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref(), P(x0), P(x_ref), P(u_init), *tail)
+        else:
+            rc = lib().fsaempc_sqp_batch_device(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(u_init), *tail)
         check(rc, "fsaempc_sqp_batch_device")
         return out
 

@@ -60,3 +60,27 @@ def instances(model, N, dt, L, seed, ids):
     u_lin = np.zeros((B, N, 2))
     x_ref = reference_live(x0, N, dt, 20.0)
     return x0, x_lin, u_lin, x_ref
+
+
+_PAR_SALT = np.uint64(0xD1B54A32D192ED03)
+_PAR_REL = list(range(0, 4)) + list(range(5, 8)) + list(range(9, 15)) + list(range(19, 28))   # drawn within +-spread of the default
+_PAR_LOG = list(range(15, 19))                                                               # slack costs: scaled by 10^U(-1, 1)
+
+
+def param_draws(model, ids, seed, spread):
+    """One parameter block per instance id (fsaempc_ltv_params, PARAM_INDEX): a pure function of (model, id, seed, spread), so the
+    shards of a multi-GPU run draw the same cars as the single-GPU run.  Entries 0-3 (M, IZ, LF, LR), 5-7 (PB, PC, PD), 9-14 (cost
+    weights) and 19-27 (limits, ellipse axes) are uniform within +-spread (relative) of the default, the slack costs 15-18 are
+    scaled by 10^U(-1, 1); GRAV, PE and the plant's PID entries stay at their defaults.  splitmix64 keyed by the id, as for
+    instances(), with a salt of its own.  Returns (len(ids), 32)."""
+    from ._lib import NPAR, default_params
+    ids = np.asarray(ids, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        st = (np.uint64(seed) ^ (ids * _GOLD)) ^ _PAR_SALT
+    out = np.repeat(default_params(model)[None, :], len(ids), axis=0)
+    assert out.shape[1] == NPAR
+    for j in _PAR_REL:
+        out[:, j] *= 1.0 + spread * (2.0 * _u01(st) - 1.0)
+    for j in _PAR_LOG:
+        out[:, j] *= 10.0 ** (2.0 * _u01(st) - 1.0)
+    return out

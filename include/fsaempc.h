@@ -418,6 +418,82 @@ int fsaempc_cl_plant_batch_device(int model, int N, double dt, int batch, double
 int fsaempc_cl_accept_batch_device(int model, int N, int batch, const double* x_new, const double* u_new, const int* exitflag,
                                    double* x_keep, double* u_keep, void* stream);
 
+/* ---- per-instance vehicle, cost and limit parameters ---------------------------------
+ * Every constant the reference assigns at the top of its drivers and models (ltvmpc_*_curvilinear.m:20-35, f_curv_*.m,
+ * dynamic_tyre_linearise_constraints.m, f_cart_dyn.m, main.m:84-88) as one block of FSAEMPC_NPAR doubles, shared by the batch or
+ * given per instance.  The entries without the _p suffix compute with the reference's values compiled in; the _p entries read
+ * the block (a NULL block, or NULL values, means the defaults and gives what the entry without the suffix gives).
+ * Fixed in both: the 5 exp(-x_d / 5) regularisation of the dynamic model, the plant's + 0.01, the 12 polygon sides and the
+ * pseudo-infinite 1e10 fillers.
+ * A block that cannot describe a car -- a non-finite entry; M, IZ, LF + LR or Q_TERMINAL <= 0; a negative weight, slack cost
+ * or limit (V_MIN may be any finite value) -- does not stop the batch: the build writes NaN into that instance's g, so the solve
+ * returns exit flag -1 with iter = 0 for it (the SQP: status -1), and the plant holds that car. */
+#define FSAEMPC_NPAR 32
+#define FSAEMPC_P_M            0   /* vehicle mass (280); also the divisor of the tyre rows */
+#define FSAEMPC_P_IZ           1   /* yaw inertia (200) */
+#define FSAEMPC_P_LF           2   /* centre of gravity to front axle (0.8672) */
+#define FSAEMPC_P_LR           3   /* centre of gravity to rear axle (0.6183) */
+#define FSAEMPC_P_GRAV         4   /* 9.81 */
+#define FSAEMPC_P_PB           5   /* Pacejka B, C, D, E (12.56, 1.38, 1.60, -0.58) */
+#define FSAEMPC_P_PC           6
+#define FSAEMPC_P_PD           7
+#define FSAEMPC_P_PE           8
+#define FSAEMPC_P_Q_S          9   /* state weights on s, n, mu (5, 250, 2000) */
+#define FSAEMPC_P_Q_N          10
+#define FSAEMPC_P_Q_MU         11
+#define FSAEMPC_P_Q_TERMINAL   12  /* factor on Q at k = N (10) */
+#define FSAEMPC_P_R_ACC        13  /* input weights (10, 10) */
+#define FSAEMPC_P_R_STEER      14
+#define FSAEMPC_P_R_SOFT0      15  /* slack costs: kinematic 1e8 (entry 15 only); dynamic 1e8, 1e6, 1e6, 1e4 */
+#define FSAEMPC_P_R_SOFT1      16
+#define FSAEMPC_P_R_SOFT2      17
+#define FSAEMPC_P_R_SOFT3      18
+#define FSAEMPC_P_U_ACC_MAX    19  /* input boxes (10, 0.4) */
+#define FSAEMPC_P_U_STEER_MAX  20
+#define FSAEMPC_P_DELTA_MAX    21  /* hard steering-angle row (0.4) */
+#define FSAEMPC_P_N_MAX        22  /* track half-width of the soft track rows (0.75) */
+#define FSAEMPC_P_V_MIN        23  /* hard speed row (0) */
+#define FSAEMPC_P_ALAT_MAX     24  /* kinematic: soft lateral-acceleration rows (5) */
+#define FSAEMPC_P_SLIP_MAX     25  /* dynamic: soft slip-angle rows (0.1) */
+#define FSAEMPC_P_ELL_LONG     26  /* dynamic: axes of the tyre ellipse behind the 12-gon rows (10.0, 9.163) */
+#define FSAEMPC_P_ELL_LAT      27
+#define FSAEMPC_P_PID_KP_V     28  /* plant only: velocity loop gain and force limit (16000, 2800) */
+#define FSAEMPC_P_PID_MAX_F    29
+#define FSAEMPC_P_PID_KP_D     30  /* plant only: steering loop gain and rate limit (80, 0.8) */
+#define FSAEMPC_P_PID_MAX_DRATE 31
+
+typedef struct {
+  const double* values;   /* device; FSAEMPC_NPAR doubles, or batch * FSAEMPC_NPAR instance-major */
+  int per_instance;       /* 0: one block shared by the batch; 1: one block per instance */
+} fsaempc_ltv_params;
+
+/* Host: the FSAEMPC_NPAR defaults of `model` (the values listed above) into out. */
+int fsaempc_ltv_default_params(int model, double* out);
+
+/* The entries above with a parameter block after `sp`.  Workspaces are those of the entries without the suffix.
+ * fsaempc_ltv_step_batch_device_p covers the three step forms: lambda and aux may each be NULL.
+ * The plant takes its own block (batch-shared or per car), so the controller's model and the car may differ. */
+int fsaempc_ltv_build_qp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream);
+int fsaempc_ltv_step_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                    void* workspace, long long workspace_bytes, void* stream);
+int fsaempc_nlp_build_qp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const double* x0, const double* x_ref, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream);
+int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                               const double* x0, const double* x_ref, const double* u_init,
+                               const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
+                               double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
+                               const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream);
+int fsaempc_cl_plant_batch_device_p(int model, int N, double dt, int batch, const fsaempc_ltv_params* par, double* cart, double* pid,
+                                    const double* x_opt, const int* finished, const int* exitflag, double* u_last, void* stream);
+
 /* ---- track pipeline (host side) --------------------------------------------------- */
 
 /* Spline table of a track as main.m:11-17 produces it: M arc-length segments, xP / yP = M x 4 Bezier control points per axis
