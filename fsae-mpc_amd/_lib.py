@@ -22,6 +22,8 @@ EXPORTS = [
     "fsaempc_ltv_step_vjp_batch_device",
     "fsaempc_ltv_default_params", "fsaempc_ltv_build_qp_batch_device_p", "fsaempc_ltv_step_batch_device_p",
     "fsaempc_nlp_build_qp_batch_device_p", "fsaempc_sqp_batch_device_p", "fsaempc_cl_plant_batch_device_p",
+    "fsaempc_ltv_blocked_nV", "fsaempc_ltv_build_qp_batch_device_b", "fsaempc_ltv_workspace_bytes_b", "fsaempc_ltv_step_batch_device_b",
+    "fsaempc_qp_workspace_bytes_s", "fsaempc_qp_solve_batch_device_s", "fsaempc_qp_layout",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -65,6 +67,43 @@ class LtvDesc(C.Structure):
 
 class LtvParams(C.Structure):
     _fields_ = [("values", C.c_void_p), ("per_instance", C.c_int)]
+
+
+class LtvBlocking(C.Structure):
+    _fields_ = [("n_blocks", C.c_int), ("len", C.POINTER(C.c_int))]
+
+
+def check_blocking(blocking, N):
+    """Validates a sequence of block lengths for a horizon of N steps (no library call) and returns it as a list of ints."""
+    try:
+        lens = [int(v) for v in blocking]
+    except TypeError:
+        raise ValueError("blocking must be a sequence of block lengths")
+    if any(int(v) != v for v in blocking):
+        raise ValueError("blocking: the block lengths must be integers")
+    if len(lens) < 1:
+        raise ValueError("blocking: at least one block")
+    if min(lens) < 1:
+        raise ValueError("blocking: every block length must be >= 1")
+    if sum(lens) != N:
+        raise ValueError("blocking: the block lengths sum to %d, the horizon has N = %d steps" % (sum(lens), N))
+    return lens
+
+
+class Blocking:
+    """A validated move blocking and the fsaempc_ltv_blocking that points at its (host) length array."""
+
+    def __init__(self, blocking, N):
+        self.lens = check_blocking(blocking, N)
+        self.n_blocks = len(self.lens)
+        self.trivial = self.n_blocks == N
+        self._arr = (C.c_int * self.n_blocks)(*self.lens)
+        self.c = LtvBlocking(self.n_blocks, C.cast(self._arr, C.POINTER(C.c_int)))
+        self.block_of_step = [j for j, l in enumerate(self.lens) for _ in range(l)]
+        self.start = [sum(self.lens[:j]) for j in range(self.n_blocks)]
+
+    def ref(self):
+        return C.byref(self.c)
 
 
 class SqpOpts(C.Structure):
@@ -138,6 +177,18 @@ def lib():
         L.fsaempc_sqp_batch_device_p.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams)] + [vp] * 3 + \
             [C.POINTER(QpOpts), C.POINTER(SqpOpts)] + [vp] * 6 + [C.POINTER(SqpAux), vp, ll, vp]
         L.fsaempc_cl_plant_batch_device_p.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(LtvParams), vp, vp, vp, vp, vp, vp, vp]
+        L.fsaempc_ltv_blocked_nV.argtypes = [C.c_int, C.POINTER(LtvBlocking)]
+        L.fsaempc_ltv_build_qp_batch_device_b.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(LtvBlocking)] + \
+            [vp] * 4 + [vp] * 7 + [vp] * 3 + [vp]
+        L.fsaempc_ltv_workspace_bytes_b.restype = C.c_longlong
+        L.fsaempc_ltv_workspace_bytes_b.argtypes = [C.POINTER(LtvDesc), C.POINTER(LtvBlocking)]
+        L.fsaempc_ltv_step_batch_device_b.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(LtvBlocking)] + \
+            [vp] * 4 + [C.POINTER(QpOpts)] + [vp] * 7 + [C.POINTER(QpAux), vp, ll, vp]
+        L.fsaempc_qp_workspace_bytes_s.restype = C.c_longlong
+        L.fsaempc_qp_workspace_bytes_s.argtypes = [C.POINTER(QpDesc), C.c_int]
+        L.fsaempc_qp_solve_batch_device_s.argtypes = [C.POINTER(QpDesc), C.c_int] + [vp] * 7 + [C.POINTER(QpOpts)] + [vp] * 5 + \
+            [C.POINTER(QpAux), vp, ll, vp]
+        L.fsaempc_qp_layout.argtypes = [C.POINTER(QpDesc), C.c_int, C.POINTER(C.c_int)]
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p
         L.fsaempc_track_from_csv.argtypes = [C.c_char_p, C.c_int, C.POINTER(TrackTable)]

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import ParamBlock, Spline, check, lib
+from ._lib import ParamBlock, Spline, check, check_blocking, lib
 from .ltvmpc import LtvBatch, dims
 
 
@@ -15,9 +15,12 @@ class ClosedLoop:
     plan -- and the exit flags are only tallied.  Cars that completed the lap (s >= L) or left the track keep their state."""
 
     def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
-                 params=None, plant_params=None):
+                 params=None, plant_params=None, blocking=None):
         """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
-        None = the same as params (both None: the reference's constants compiled into the kernels)."""
+        None = the same as params (both None: the reference's constants compiled into the kernels).  blocking: block lengths of the
+        controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2)."""
+        if blocking is not None:
+            check_blocking(blocking, N)   # (before the library is touched)
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -26,7 +29,8 @@ class ClosedLoop:
         cart0 = np.ascontiguousarray(np.asarray(cart0, dtype=np.float64).reshape(-1, 7))
         self.B = cart0.shape[0]
         self.track = track
-        self.mpc = LtvBatch(model, N, dt, track, self.B, device=device, options=options, integrator=integrator, params=params)
+        self.mpc = LtvBatch(model, N, dt, track, self.B, device=device, options=options, integrator=integrator, params=params,
+                            blocking=blocking)
         if plant_params is None:
             plant_params = params
         self.plant_params = ParamBlock(plant_params, self.B, self.device) if plant_params is not None else None
@@ -55,6 +59,8 @@ class ClosedLoop:
         self.launch_hint = bool(launch_hint)
         self._last_iter = None
         self._x_init = torch.zeros((self.B, self.mpc.nV), dtype=torch.float64, device=self.device) if self.warm_start else None
+        if self.warm_start and self.mpc.blocking is not None:
+            self._shift_idx = torch.tensor([min(s + 1, N - 1) for s in self.mpc.blocking.start], dtype=torch.long, device=self.device)
 
     def _stream(self, stream):
         return C.c_void_p(stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -84,10 +90,15 @@ class ClosedLoop:
         if self.warm_start and self.steps > 0:
             N = self.N
             x_init = self._x_init
-            x_init[:, : 2 * (N - 1)].view(self.B, N - 1, 2).copy_(self.u_opt[:, 1:, :])   # (no temporaries: strided views on both sides)
-            x_init[:, 2 * (N - 1): 2 * N].copy_(self.u_opt[:, N - 1, :])
+            nu = 2 * self.mpc.n_blocks
+            if self.mpc.blocking is not None:
+                # held inputs: the shifted previous plan (u_2 .. u_N, u_N) sampled at each block's first step
+                x_init[:, :nu].view(self.B, nu // 2, 2).copy_(self.u_opt[:, self._shift_idx, :])
+            else:
+                x_init[:, : 2 * (N - 1)].view(self.B, N - 1, 2).copy_(self.u_opt[:, 1:, :])   # (no temporaries: strided views on both sides)
+                x_init[:, 2 * (N - 1): 2 * N].copy_(self.u_opt[:, N - 1, :])
             if self._slack is not None:
-                x_init[:, 2 * N:].copy_(self._slack)
+                x_init[:, nu:].copy_(self._slack)
         out = self.mpc.step(self.x0, self.x_ref, self.x_opt, self.u_opt, stream=stream, x_init=x_init,
                             difficulty=self._last_iter if self.launch_hint else None)   # linearised about the previous plan (main.m:121-125)
         if self.warm_start:
@@ -120,14 +131,14 @@ def monte_carlo_carts(track, B, seed):
 
 
 def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
-                plant_params=None):
+                plant_params=None, blocking=None):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
     import torch
     cart0, s_init = monte_carlo_carts(track, B, seed)
     cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
-                    params=params, plant_params=plant_params)
+                    params=params, plant_params=plant_params, blocking=blocking)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

@@ -69,11 +69,30 @@ void fsaempc_qp_default_opts(fsaempc_qp_opts* o) {
   o->tol = 1e-8; o->tol_loose = 1e-6; o->tol_x = 1e-7; o->inf_bound = 1e9; o->max_iter = 100; o->polish = 1;
 }
 
-long long fsaempc_qp_workspace_bytes(const fsaempc_qp_desc* desc) {
-  if (!desc || desc->nV <= 0 || desc->nC < 0 || desc->batch < 0) return FSAEMPC_ERR_ARG;
+// n_slack of the _s entries: a negative value means "none given" (QP_NO_SLACK_HINT), else 0, 1 or 4 trailing slack variables
+static bool slack_hint_ok(const fsaempc_qp_desc* desc, int n_slack) {
+  if (n_slack < 0) return true;
+  return (n_slack == 0 || n_slack == 1 || n_slack == 4) && desc->nV > n_slack;
+}
+static int slack_hint(int n_slack) { return n_slack < 0 ? QP_NO_SLACK_HINT : n_slack; }
+
+long long fsaempc_qp_workspace_bytes_s(const fsaempc_qp_desc* desc, int n_slack) {
+  if (!desc || desc->nV <= 0 || desc->nC < 0 || desc->batch < 0 || !slack_hint_ok(desc, n_slack)) return FSAEMPC_ERR_ARG;
   if (desc->nV > FSAEMPC_MAX_NV) return FSAEMPC_ERR_DIM;
-  QpDims d; qp_make_dims(desc->nV, desc->nC, &d);
+  QpDims d; qp_make_dims(desc->nV, desc->nC, &d, slack_hint(n_slack));
+  if (d.T > QP_MAX_T) return FSAEMPC_ERR_DIM;
   return (long long)(d.ws_per_qp * sizeof(double) * (size_t)(desc->batch > 0 ? desc->batch : 1) + qp_order_bytes(desc->batch));
+}
+long long fsaempc_qp_workspace_bytes(const fsaempc_qp_desc* desc) { return fsaempc_qp_workspace_bytes_s(desc, -1); }
+
+int fsaempc_qp_layout(const fsaempc_qp_desc* desc, int n_slack, int out[4]) {
+  if (!desc || !out || desc->nV <= 0 || desc->nC < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (!slack_hint_ok(desc, n_slack)) return fail(FSAEMPC_ERR_ARG, "n_slack must be 0, 1 or 4 (negative: none given) and smaller than nV");
+  if (desc->nV > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
+  QpDims d; qp_make_dims(desc->nV, desc->nC, &d, slack_hint(n_slack));
+  if (d.T > QP_MAX_T) return fail(FSAEMPC_ERR_DIM, "more column tiles than the kernels are built for");
+  out[0] = d.T; out[1] = d.NB; out[2] = d.n; out[3] = qp_runs_wavefront_kernel(d) ? 1 : 0;
+  return 0;
 }
 
 int fsaempc_qp_solve_batch_device(const fsaempc_qp_desc* desc, const double* H, const double* g, const double* A,
@@ -87,14 +106,23 @@ int fsaempc_qp_solve_batch_device_aux(const fsaempc_qp_desc* desc, const double*
                                       const double* lb, const double* ub, const double* lbA, const double* ubA,
                                       const fsaempc_qp_opts* opts, double* x, double* fval, int* exitflag, int* iter,
                                       double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
+  return fsaempc_qp_solve_batch_device_s(desc, -1, H, g, A, lb, ub, lbA, ubA, opts, x, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream);
+}
+
+int fsaempc_qp_solve_batch_device_s(const fsaempc_qp_desc* desc, int n_slack, const double* H, const double* g, const double* A,
+                                    const double* lb, const double* ub, const double* lbA, const double* ubA,
+                                    const fsaempc_qp_opts* opts, double* x, double* fval, int* exitflag, int* iter,
+                                    double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
   if (!desc || !H || !g || !lb || !ub || !x || !fval || !exitflag || !iter || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (desc->nV <= 0 || desc->nC < 0 || desc->batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
   if (desc->nC > 0 && (!A || !lbA || !ubA)) return fail(FSAEMPC_ERR_ARG, "nC > 0 needs A, lbA, ubA");
   if (desc->nV > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
+  if (!slack_hint_ok(desc, n_slack)) return fail(FSAEMPC_ERR_ARG, "n_slack must be 0, 1 or 4 (negative: none given) and smaller than nV");
   if (desc->batch == 0) return 0;
   fsaempc_qp_opts o; if (opts) o = *opts; else fsaempc_qp_default_opts(&o);
   QpParams P; memset(&P, 0, sizeof(P));
-  qp_make_dims(desc->nV, desc->nC, &P.d);
+  qp_make_dims(desc->nV, desc->nC, &P.d, slack_hint(n_slack));
+  if (P.d.T > QP_MAX_T) return fail(FSAEMPC_ERR_DIM, "more column tiles than the kernels are built for");
   const size_t ws_qps = P.d.ws_per_qp * sizeof(double) * (size_t)desc->batch;
   if ((long long)(ws_qps + qp_order_bytes(desc->batch)) > workspace_bytes) return fail(FSAEMPC_ERR_WORKSPACE, "workspace too small");
   const char* no_order = getenv("FSAEMPC_QP_ORDER");   // A/B runs only: FSAEMPC_QP_ORDER=0 solves in index order (read per call)
@@ -546,6 +574,116 @@ static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, cons
     e = ltv_post_launch(fsaempc_ltv_nx(desc->model), desc->N, ltv_ns(desc->model), desc->batch, D(c.z), D(c.pred), D(c.Bt), D(c.qc),
                         u_opt, x_opt, slack, fval, (hipStream_t)stream); }
   if (e != hipSuccess) return hipfail(e, "ltv_post_launch");
+  if (timing) { e = hipEventRecord(g_evf[1], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
+  return 0;
+}
+
+/* ---- move blocking ---- */
+int fsaempc_ltv_blocked_nV(int model, const fsaempc_ltv_blocking* blk) {
+  if (!blk || blk->n_blocks < 1) return fail(FSAEMPC_ERR_ARG, "blocking: n_blocks >= 1");
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  return 2 * blk->n_blocks + ltv_ns(model);
+}
+
+// checks the descriptor pair and fills the kernels' block map; *trivial: one step per block (the unblocked problem)
+static int blk_check(const fsaempc_ltv_desc* d, const fsaempc_ltv_blocking* blk, LtvBlockMap* bm, bool* trivial) {
+  if (!d || !blk || !blk->len) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (d->N <= 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (blk->n_blocks < 1 || blk->n_blocks > d->N) return fail(FSAEMPC_ERR_ARG, "blocking: 1 <= n_blocks <= N");
+  long long sum = 0;
+  for (int j = 0; j < blk->n_blocks; ++j) { if (blk->len[j] < 1) return fail(FSAEMPC_ERR_ARG, "blocking: every block length >= 1"); sum += blk->len[j]; }
+  if (sum != d->N) return fail(FSAEMPC_ERR_ARG, "blocking: the block lengths must sum to N");
+  if (d->model != FSAEMPC_MODEL_KINEMATIC && d->model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (fsaempc_ltv_nV(d->model, d->N) > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "2N + ns exceeds FSAEMPC_MAX_NV");
+  memset(bm, 0, sizeof(*bm));
+  bm->M = blk->n_blocks;
+  int st = 0;
+  for (int j = 0; j < blk->n_blocks; ++j) { bm->start[j] = (unsigned char)st; st += blk->len[j]; }
+  bm->start[blk->n_blocks] = (unsigned char)st;
+  *trivial = blk->n_blocks == d->N;
+  return 0;
+}
+
+int fsaempc_ltv_build_qp_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const fsaempc_ltv_blocking* blk,
+                                        const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream) {
+  LtvBlockMap bm; bool trivial = false;
+  int rc = blk_check(desc, blk, &bm, &trivial); if (rc) return rc;
+  if (trivial) return fsaempc_ltv_build_qp_batch_device_p(desc, sp, par, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
+  rc = ltv_check(desc, sp); if (rc) return rc;
+  if (!x0 || !x_ref || !x_lin || !u_lin || !H || !g || !A || !lb || !ub || !lbA || !ubA || !Bt) return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
+  if (ltv_build_blocked_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N, bm.M, 256) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
+  if (desc->batch == 0) return 0;
+  LtvParams P; memset(&P, 0, sizeof(P));
+  P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.dt = desc->dt;
+  P.integ = ltv_integ(desc);
+  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP;
+  P.x0 = x0; P.x_ref = x_ref; P.x_lin = x_lin; P.u_lin = u_lin;
+  P.H = H; P.g = g; P.A = A; P.lb = lb; P.ub = ub; P.lbA = lbA; P.ubA = ubA; P.pred = pred; P.Bt = Bt; P.qconst = qconst;
+  hipError_t e = ltv_build_blocked_launch(P, bm, par_values(par), par_stride(par), desc->batch, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "ltv_build_blocked_launch");
+  return 0;
+}
+
+// the carve of ltv_carve in blocked sizes; the QP workspace is sized with the same slack hint the solve is given
+static void ltv_carve_b(const fsaempc_ltv_desc* d, int M, LtvCarve* c) {
+  const size_t B = d->batch > 0 ? d->batch : 1, nx = fsaempc_ltv_nx(d->model), N = d->N;
+  const size_t nV = 2 * (size_t)M + ltv_ns(d->model), nC = fsaempc_ltv_nC(d->model, d->N), R = nx * N;
+  size_t off = 0;
+  auto take = [&](size_t cnt) { size_t o = off; off = align64(off + cnt * sizeof(double)); return o; };
+  c->H = take(B * nV * nV); c->g = take(B * nV); c->A = take(B * nC * nV); c->lb = take(B * nV); c->ub = take(B * nV);
+  c->lbA = take(B * nC); c->ubA = take(B * nC); c->pred = take(B * R); c->Bt = take(B * R * nV); c->qc = take(B); c->z = take(B * nV);
+  off = (off + 255) & ~(size_t)255;
+  c->qpws = off;
+  fsaempc_qp_desc q{(int)nV, (int)nC, (int)B, 0};
+  long long w = fsaempc_qp_workspace_bytes_s(&q, ltv_ns(d->model));
+  c->total = off + (w > 0 ? (size_t)w : 0);
+}
+
+long long fsaempc_ltv_workspace_bytes_b(const fsaempc_ltv_desc* desc, const fsaempc_ltv_blocking* blk) {
+  if (!desc || desc->batch < 0) return FSAEMPC_ERR_ARG;
+  LtvBlockMap bm; bool trivial = false;
+  int rc = blk_check(desc, blk, &bm, &trivial); if (rc) return rc;
+  if (trivial) return fsaempc_ltv_workspace_bytes(desc);
+  LtvCarve c; ltv_carve_b(desc, bm.M, &c);
+  return (long long)c.total;
+}
+
+int fsaempc_ltv_step_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const fsaempc_ltv_blocking* blk,
+                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                    void* workspace, long long workspace_bytes, void* stream) {
+  LtvBlockMap bm; bool trivial = false;
+  int rc = blk_check(desc, blk, &bm, &trivial); if (rc) return rc;
+  if (trivial) return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream, par);
+  rc = ltv_check(desc, sp); if (rc) return rc;
+  if (!x0 || !x_ref || !x_lin || !u_lin || !u_opt || !x_opt || !slack || !fval || !exitflag || !iter || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (desc->batch == 0) return 0;
+  LtvCarve c; ltv_carve_b(desc, bm.M, &c);
+  if ((long long)c.total > workspace_bytes) return fail(FSAEMPC_ERR_WORKSPACE, "workspace too small");
+  char* w = (char*)workspace;
+  auto D = [&](size_t off) { return (double*)(w + off); };
+  Range whole("fsaempc.ltv.step_blocked");
+  const bool timing = g_timing.load();
+  if (timing) { hipError_t e = hipEventRecord(g_evf[0], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
+  { Range r("fsaempc.ltv.build_blocked");
+    rc = fsaempc_ltv_build_qp_batch_device_b(desc, sp, par, blk, x0, x_ref, x_lin, u_lin, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA),
+                                             D(c.pred), D(c.Bt), D(c.qc), stream); }
+  if (rc) return rc;
+  const int ns = ltv_ns(desc->model);
+  fsaempc_qp_desc q{2 * bm.M + ns, fsaempc_ltv_nC(desc->model, desc->N), desc->batch, 0};
+  rc = fsaempc_qp_solve_batch_device_s(&q, ns, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA), opts, D(c.z), fval, exitflag, iter,
+                                       lambda, aux, w + c.qpws, (long long)(c.total - c.qpws), stream);
+  if (rc) return rc;
+  hipError_t e;
+  { Range r("fsaempc.ltv.post");
+    e = ltv_post_blocked_launch(fsaempc_ltv_nx(desc->model), desc->N, ns, bm, desc->batch, D(c.z), D(c.pred), D(c.Bt), D(c.qc),
+                                u_opt, x_opt, slack, fval, (hipStream_t)stream); }
+  if (e != hipSuccess) return hipfail(e, "ltv_post_blocked_launch");
   if (timing) { e = hipEventRecord(g_evf[1], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
   return 0;
 }

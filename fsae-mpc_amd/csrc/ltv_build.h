@@ -22,6 +22,17 @@ size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact = false, bool 
 hipError_t ltv_build_par_launch(const LtvParams& P, const double* values, int stride, const int* idx, int batch, hipStream_t st,
                                 bool exact = false);
 
+// Move blocking (ltv_build_blocked.hip): M blocks of consecutive steps share one input pair.  start[j] is the first
+// step of block j, start[M] = N; the map is a kernel argument (no device copy).  All QP tensors of P are in blocked sizes
+// (nV_b = 2 M + ns); values = nullptr selects the compiled-in constants, else workgroup b reads values + b * stride.
+struct LtvBlockMap { int M; unsigned char start[98]; };
+size_t ltv_build_blocked_lds_bytes(int nx, int N, int M, int threads);
+hipError_t ltv_build_blocked_launch(const LtvParams& P, const LtvBlockMap& bm, const double* values, int stride, int batch, hipStream_t st);
+// post-solve of a blocked step: x_opt = pred + Bt_b z, u_opt = the held inputs expanded to 2N, slack, fval += const
+hipError_t ltv_post_blocked_launch(int nx, int N, int ns, const LtvBlockMap& bm, int batch, const double* z, const double* pred,
+                                   const double* Bt, const double* qconst, double* u_opt, double* x_opt, double* slack, double* fval,
+                                   hipStream_t st);
+
 // sensitivities: the affine maps of the build in x0 / x_ref (Abar R x nx, Crow nC x nx per instance, column-major),
 // the cotangent of the QP variables of a step (z = [u_opt; slack], zbar = [ubar; sbar] + Bt' xbar, kc columns) and the chain from the
 // QP cotangents (gbar, lbAbar, ubAbar) to x0bar (kc x nx) / xrefbar (kc x R); status < 0 gives zeros

@@ -60,7 +60,12 @@ struct QpParams {
 #define QP_ORDER_MIN_BATCH 256
 inline size_t qp_order_bytes(int batch) { return batch > QP_ORDER_MIN_BATCH ? (((size_t)2 * batch * sizeof(int)) + 255) & ~(size_t)255 : 0; }
 
-void qp_make_dims(int n, int m, QpDims* d);
+// n_slack: the caller's count of trailing slack variables (0, 1 or 4), or QP_NO_SLACK_HINT: decide by nV mod 16 and the row / column
+// signature of the reference's QPs, as always.  With a count the last n_slack variables are the border whatever nV and nC are and the
+// core is padded to a multiple of 16 with dummy variables (QpDims::nu): the route of QPs whose slack columns the signature cannot
+// recognise (move-blocked LTV-MPC QPs: nC of the full horizon, fewer variables)
+#define QP_NO_SLACK_HINT (-1)
+void qp_make_dims(int n, int m, QpDims* d, int n_slack = QP_NO_SLACK_HINT);
 // solver index -> caller's variable index (-1: dummy padding variable), and back
 __host__ __device__ inline int qp_user_index(const QpDims& d, int i) { const int ncu = d.nu - d.nb; return i < ncu ? i : (i >= d.nc && d.nb > 0 ? ncu + (i - d.nc) : (i < d.nu && d.nb == 0 ? i : -1)); }
 __host__ __device__ inline int qp_solver_index(const QpDims& d, int u) { const int ncu = d.nu - d.nb; return (d.nb > 0 && u >= ncu) ? d.nc + (u - ncu) : u; }

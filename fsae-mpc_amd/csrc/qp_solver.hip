@@ -2348,7 +2348,7 @@ template <int T> __global__ __launch_bounds__(64) void factor_probe_kernel(QpPar
 }
 #endif
 
-void qp_make_dims(int n, int m, QpDims* d) {
+void qp_make_dims(int n, int m, QpDims* d, int n_slack) {
   d->n = n; d->nu = n; d->m = m;
   // 1..4 trailing variables (the slack columns of the LTV-MPC QPs: nV = 2N + 1 or 2N + 4) are a *border*: they are
   // handled on the VALU instead of costing a whole 16-wide tile row/column of MFMA work and operand traffic
@@ -2365,7 +2365,10 @@ void qp_make_dims(int n, int m, QpDims* d) {
   // the end game went non-finite; ids 0..16383 all solved, vertex rate 98.7 -> 99.0 % with the column as the border; the cost measured
   // on that shape is within noise now, 910 k vs 914 k QP/s).  FSAEMPC_SLACK_BORDER=0 switches it off, =1 is the old "where it pays"
   // rule (A/B runs and tests).
-  if (d->nb == 0 && n >= 20) {
+  if (n_slack >= 0) {   // the caller names its trailing slack columns: they are the border, the core is padded with dummy variables
+    d->T = (n - n_slack + 15) / 16; d->nb = n_slack;
+    if (n_slack > 0) d->n = 16 * d->T + n_slack;
+  } else if (d->nb == 0 && n >= 20) {
     const char* sb = getenv("FSAEMPC_SLACK_BORDER");
     const int ns = (m == 10 * (n - 4) && ((n - 4) % 2) == 0) ? 4 : ((m == 3 * (n - 1) && ((n - 1) % 2) == 0) ? 1 : 0);
     const int Tp = (n - ns + 15) / 16;

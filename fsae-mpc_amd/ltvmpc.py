@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import LtvDesc, ParamBlock, QpAux, QpDesc, Spline, check, default_opts, lib
+from ._lib import Blocking, LtvDesc, ParamBlock, QpAux, QpDesc, Spline, check, default_opts, lib
 from .synthetic import DYNAMIC, KINEMATIC
 
 
@@ -21,14 +21,22 @@ class LtvBatch:
     """Device-resident batched LTV-MPC step (one call = linearise + condense + solve + post-solve for
     `batch` independent instances).  Inputs/outputs are torch tensors on the GPU."""
 
-    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1, params=None):
+    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1, params=None, blocking=None):
         """params: None (the reference's constants, compiled into the kernels), or a block of vehicle / cost / limit parameters
-        (fsaempc.default_params, PARAM_INDEX): (32,) shared by the batch or (batch, 32) per instance, numpy or a device tensor."""
+        (fsaempc.default_params, PARAM_INDEX): (32,) shared by the batch or (batch, 32) per instance, numpy or a device tensor.
+        blocking: None, or a sequence of block lengths (each >= 1, sum N): the input is held over each block of consecutive steps
+        (move blocking).  The QP then has nV = 2 * n_blocks + ns variables [v_1 .. v_M; slacks]: build_qp, x_init and
+        lam are in these sizes, while u_opt stays (B, 2N), the held values."""
+        self.blocking = Blocking(blocking, N) if blocking is not None else None   # (validated before the library is touched)
         import torch
         self.torch = torch
         self.model, self.N, self.dt, self.batch = model, N, float(dt), batch
         self.device = torch.device(device)
         self.nx, self.ns, self.nV, self.nC = dims(model, N)
+        self.n_blocks = self.blocking.n_blocks if self.blocking is not None else N
+        self.block_of_step = list(self.blocking.block_of_step) if self.blocking is not None else list(range(N))
+        if self.blocking is not None:
+            self.nV = 2 * self.n_blocks + self.ns
         self.track = track
         self.xP, self.yP = track.device(self.device)
         self.sp = Spline(track.M, track.dl, C.c_void_p(self.xP.data_ptr()), C.c_void_p(self.yP.data_ptr()))
@@ -57,7 +65,10 @@ class LtvBatch:
                  const=self._f64(B))
         P = lambda t: C.c_void_p(t.data_ptr())
         out = (P(q["H"]), P(q["g"]), P(q["A"]), P(q["lb"]), P(q["ub"]), P(q["lbA"]), P(q["ubA"]), P(q["pred"]), P(q["Bt"]), P(q["const"]))
-        if self.params is not None:
+        if self.blocking is not None:
+            rc = lib().fsaempc_ltv_build_qp_batch_device_b(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
+                                                           self.blocking.ref(), P(x0), P(x_ref), P(x_lin), P(u_lin), *out, self._stream(stream))
+        elif self.params is not None:
             rc = lib().fsaempc_ltv_build_qp_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref(), P(x0), P(x_ref), P(x_lin),
                                                            P(u_lin), *out, self._stream(stream))
         else:
@@ -71,10 +82,14 @@ class LtvBatch:
         per-instance diagnostics `kkt` (achieved relative KKT residual) and `polished` (> 0: the returned point is the vertex); x_init
         (batch, nV): optional starting point of the interior-point solve (fsaempc_qp_aux.x_init); difficulty (batch,) int32: optional
         effort estimate per instance for the launch order (fsaempc_qp_aux.difficulty); want_lambda adds `lam` (B, nV + nC), the multipliers
-        of the step's QP (variables [u_opt; slack], layout of fsaempc_qp_solve_batch_device)."""
+        of the step's QP (variables [u_opt; slack], layout of fsaempc_qp_solve_batch_device).  With move blocking x_init and lam are in the
+        blocked variables [v_1 .. v_M; slack] (nV = 2 n_blocks + ns); u_opt is the held plan, (B, 2N)."""
         torch = self.torch
         B = self.batch
-        need = lib().fsaempc_ltv_workspace_bytes(C.byref(self.desc))
+        if self.blocking is not None:
+            need = lib().fsaempc_ltv_workspace_bytes_b(C.byref(self.desc), self.blocking.ref())
+        else:
+            need = lib().fsaempc_ltv_workspace_bytes(C.byref(self.desc))
         if need < 0:
             check(int(need), "fsaempc_ltv_workspace_bytes")
         if self._ws is None or self._ws.numel() * 8 < need:
@@ -95,7 +110,13 @@ class LtvBatch:
             raise ValueError("difficulty must be a contiguous int32 (batch,) tensor on the GPU")
         df = P(difficulty) if difficulty is not None else None
         aux = QpAux(P(out["kkt"]), P(out["polished"]), xi, df) if want_aux else QpAux(None, None, xi, df)
-        if self.params is not None:
+        if self.blocking is not None:
+            rc = lib().fsaempc_ltv_step_batch_device_b(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
+                                                       self.blocking.ref(), P(x0), P(x_ref), P(x_lin), P(u_lin),
+                                                       C.byref(self.opts), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]),
+                                                       P(out["exitflag"]), P(out["iter"]), lam, C.byref(aux), P(self._ws),
+                                                       C.c_longlong(self._ws.numel() * 8), self._stream(stream))
+        elif self.params is not None:
             rc = lib().fsaempc_ltv_step_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref(), P(x0), P(x_ref), P(x_lin), P(u_lin),
                                                        C.byref(self.opts), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]),
                                                        P(out["exitflag"]), P(out["iter"]), lam, C.byref(aux), P(self._ws),

@@ -77,22 +77,43 @@ def qpOASES(H, g, *args, options=None):
     return x.T, fval, flag, it, lam.T, aux
 
 
+def _slack_hint(n_slack):
+    if n_slack is None:
+        return -1
+    if n_slack not in (0, 1, 4):
+        raise ValueError("n_slack must be None, 0, 1 or 4")
+    return int(n_slack)
+
+
+def qp_layout(nV, nC, n_slack=None):
+    """How the solver lays out a QP of this shape (fsaempc_qp_layout; a host function: no GPU needed): dict(T = 16-wide column tiles
+    of the matrix-core part, NB = border width of the kernel variant, n_solver = the solver's variable count with its dummy padding,
+    wavefront_kernel = True for the one-wavefront kernel, False for the workgroup kernel)."""
+    out = (C.c_int * 4)()
+    desc = QpDesc(int(nV), int(nC), 1, 0)
+    check(lib().fsaempc_qp_layout(C.byref(desc), _slack_hint(n_slack), out), "fsaempc_qp_layout")
+    return dict(T=out[0], NB=out[1], n_solver=out[2], wavefront_kernel=bool(out[3]))
+
+
 def qp_solve_batch_device(H, g, A, lb, ub, lbA, ubA, options=None, want_lambda=False, workspace=None, stream=None,
-                          shared_HA=False, want_aux=False, x_init=None, difficulty=None):
+                          shared_HA=False, want_aux=False, x_init=None, difficulty=None, n_slack=None):
     """Device-resident batched solve on torch CUDA(HIP) tensors (instance-major, each instance column-major):
     H (B,nV,nV), g (B,nV), A (B,nV,nC) [memory of a column-major nC x nV matrix], lb/ub (B,nV), lbA/ubA (B,nC).
     Asynchronous on `stream` (default: torch's current stream).  Returns dict of device tensors; want_aux adds `kkt`
     (relative KKT residual of the returned point) and `polished` (> 0: the active-set refinement reached the vertex); x_init (B,nV):
-    optional starting point of the interior-point iteration (clamped to the bounds)."""
+    optional starting point of the interior-point iteration (clamped to the bounds).  n_slack (None, 0, 1 or 4): the number of trailing
+    slack variables, for QPs whose slack columns the solver cannot recognise by shape (fsaempc_qp_solve_batch_device_s); None leaves
+    the layout to the library, as always."""
     import torch
     B, nV = g.shape
+    ns_hint = _slack_hint(n_slack)
     nC = lbA.shape[1] if lbA is not None else 0
     dev = g.device
     for t in (H, g, A, lb, ub, lbA, ubA):
         if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda):
             raise ValueError("device tensors must be contiguous float64 on the GPU")
     desc = QpDesc(nV, nC, B, 1 if shared_HA else 0)
-    need = lib().fsaempc_qp_workspace_bytes(C.byref(desc))
+    need = lib().fsaempc_qp_workspace_bytes_s(C.byref(desc), ns_hint)
     if need < 0:
         check(int(need), "fsaempc_qp_workspace_bytes")
     if workspace is None or workspace.numel() * workspace.element_size() < need:
@@ -112,9 +133,9 @@ def qp_solve_batch_device(H, g, A, lb, ub, lbA, ubA, options=None, want_lambda=F
     if difficulty is not None and (difficulty.dtype != torch.int32 or not difficulty.is_contiguous() or not difficulty.is_cuda or tuple(difficulty.shape) != (B,)):
         raise ValueError("difficulty must be a contiguous int32 (B,) tensor on the GPU")
     aux = QpAux(P(kkt), P(pol), P(x_init), P(difficulty))   # per-instance diagnostics (the analogue of qpOASES' auxOutput) + optional starting point
-    rc = lib().fsaempc_qp_solve_batch_device_aux(C.byref(desc), P(H), P(g), P(A), P(lb), P(ub), P(lbA), P(ubA), C.byref(opts),
-                                                 P(x), P(fval), P(flag), P(it), P(lam), C.byref(aux), P(workspace),
-                                                 C.c_longlong(workspace.numel() * 8), C.c_void_p(st))
+    rc = lib().fsaempc_qp_solve_batch_device_s(C.byref(desc), ns_hint, P(H), P(g), P(A), P(lb), P(ub), P(lbA), P(ubA), C.byref(opts),
+                                               P(x), P(fval), P(flag), P(it), P(lam), C.byref(aux), P(workspace),
+                                               C.c_longlong(workspace.numel() * 8), C.c_void_p(st))
     check(rc, "fsaempc_qp_solve_batch_device_aux")
     return dict(x=x, fval=fval, exitflag=flag, iter=it, lam=lam, workspace=workspace, kkt=kkt, polished=pol)
 

@@ -106,6 +106,9 @@ def _no_params(batch, what):
     differentiating a different problem."""
     if getattr(batch, "params", None) is not None:
         raise NotImplementedError("%s is not available for an LtvBatch with a parameter block (set_params(None) first)" % what)
+    blk = getattr(batch, "blocking", None)
+    if blk is not None and not blk.trivial:   # the same holds for move blocking: the maps and the VJP chain are those of the unblocked build
+        raise NotImplementedError("%s is not available for an LtvBatch with move blocking (blocking=None, or one step per block)" % what)
 
 
 def _ptr(t):

@@ -3,7 +3,7 @@ rollout of the model as its dynamics, solved per instance by a Gauss-Newton SQP 
 search and per-instance termination.  All compute runs on the MI355X through libfsaempc.so (fsaempc_sqp_batch_device)."""
 import ctypes as C
 
-from ._lib import LtvDesc, ParamBlock, QpOpts, SqpAux, Spline, check, default_opts, lib, sqp_default_opts
+from ._lib import LtvDesc, ParamBlock, QpOpts, SqpAux, Spline, check, check_blocking, default_opts, lib, sqp_default_opts
 from .ltvmpc import dims
 
 STATUS = {0: "converged", 1: "sweep limit", 2: "no step accepted", -1: "QP failed", -2: "QP infeasible"}
@@ -12,7 +12,12 @@ STATUS = {0: "converged", 1: "sweep limit", 2: "no step accepted", -1: "QP faile
 class SqpBatch:
     """Device-resident batched SQP.  Inputs / outputs are torch tensors on the GPU, laid out as for LtvBatch.step."""
 
-    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1, params=None):
+    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1, params=None, blocking=None):
+        """blocking: accepted for symmetry with LtvBatch, but only the trivial one ([1] * N): the exact build of the NLP has no
+        move-blocked form (LtvBatch.sqp re-linearises a blocked batch)."""
+        if blocking is not None and len(check_blocking(blocking, N)) != N:
+            raise NotImplementedError("SqpBatch (the exact build of the NLP, nlp_build_qp) is not available with move blocking; "
+                                      "LtvBatch(..., blocking=...).sqp re-linearises a blocked batch")
         import torch
         self.torch = torch
         self.model, self.N, self.dt, self.batch = model, N, float(dt), batch

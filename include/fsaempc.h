@@ -494,6 +494,59 @@ int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_splin
 int fsaempc_cl_plant_batch_device_p(int model, int N, double dt, int batch, const fsaempc_ltv_params* par, double* cart, double* pid,
                                     const double* x_opt, const int* finished, const int* exitflag, double* u_last, void* stream);
 
+/* ---- move blocking: held inputs --------------------------------------------------
+ * The input is held constant over groups of consecutive horizon steps: block j covers steps start_j .. start_j + len_j - 1 and
+ * u_k = v_block(k).  The QP's variables are [v_1 .. v_M; slacks], nV_b = 2 M + ns; its rows stay those of the unblocked problem
+ * (nC = 6N / 20N).  With E the (2N + ns) x (2M + ns) matrix that copies v_block(k) to step k, the blocked QP is H_b = E'HE,
+ * g_b = E'g, A_b = AE of the unblocked one, with the bounds of each block's first member.  One blocking is shared by the batch.
+ * Errors: n_blocks < 1, a length < 1 or a sum other than desc->N give FSAEMPC_ERR_ARG; 2N + ns > FSAEMPC_MAX_NV stays
+ * FSAEMPC_ERR_DIM (a long horizon does not become admissible by blocking it).  n_blocks == N is the unblocked problem: the entries
+ * hand over to their _p forms and return bitwise what those return. */
+typedef struct {
+  int n_blocks;      /* M, 1..N */
+  const int* len;    /* HOST array of M block lengths, each >= 1, sum == desc->N; shared by the batch */
+} fsaempc_ltv_blocking;
+
+/* 2 M + ns (host, no device needed); < 0: FSAEMPC_ERR_ARG */
+int fsaempc_ltv_blocked_nV(int model, const fsaempc_ltv_blocking* blk);
+/* fsaempc_ltv_build_qp_batch_device_p in blocked sizes (nV_b for nV everywhere: H nV_b^2, g / lb / ub nV_b, A nC x nV_b); Bt is
+ * nx N x nV_b and holds the held-input response in the block columns (zeros in the slack columns).  par may be NULL. */
+int fsaempc_ltv_build_qp_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const fsaempc_ltv_blocking* blk,
+                                        const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream);
+long long fsaempc_ltv_workspace_bytes_b(const fsaempc_ltv_desc* desc, const fsaempc_ltv_blocking* blk);
+/* The fused step (the _p form: lambda and aux may each be NULL).  u_opt is returned EXPANDED to 2N, the held values, so what
+ * consumes a plan (fsaempc_cl_accept_batch_device, the plant, the next linearisation point) works unchanged; x_opt = pred + Bt_b z;
+ * slack and fval (constant included) as always; lambda has nV_b + nC entries; aux->x_init is in the blocked variables (nV_b).
+ * The solve goes through fsaempc_qp_solve_batch_device_s with the model's slack count. */
+int fsaempc_ltv_step_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const fsaempc_ltv_blocking* blk,
+                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                    void* workspace, long long workspace_bytes, void* stream);
+
+/* The batched solve with the caller's count of trailing slack variables.  The solver keeps the 1 / 4 slack columns of an LTV-MPC QP
+ * off the matrix cores (a "border"); without a count it recognises them by nV mod 16 or by the row / column signature of the
+ * reference's QPs (nC = 3 (nV - 1) or 10 (nV - 4)), which a QP with condensed columns no longer has.  n_slack: 0, 1 or 4 -- the last
+ * n_slack variables are the border, the core is padded to a multiple of 16 with dummy variables; negative -- none given, exactly
+ * fsaempc_qp_workspace_bytes / fsaempc_qp_solve_batch_device_aux.  Results of a solve do not depend on the count beyond rounding;
+ * the workspace size does: size and solve must be given the same count. */
+long long fsaempc_qp_workspace_bytes_s(const fsaempc_qp_desc* desc, int n_slack);
+int fsaempc_qp_solve_batch_device_s(const fsaempc_qp_desc* desc, int n_slack,
+                                    const double* H, const double* g, const double* A,
+                                    const double* lb, const double* ub, const double* lbA, const double* ubA,
+                                    const fsaempc_qp_opts* opts,
+                                    double* x, double* fval, int* exitflag, int* iter, double* lambda,
+                                    const fsaempc_qp_aux* aux,
+                                    void* workspace, long long workspace_bytes, void* stream);
+/* Host only (no device needed): how a QP of this shape is laid out and which kernel solves it.  out[0] = 16-wide column tiles of
+ * the matrix-core part, out[1] = border width of the kernel variant (0, 1 or 4), out[2] = the solver's variable count (dummy
+ * padding included), out[3] = 1 for the one-wavefront kernel, 0 for the workgroup kernel. */
+int fsaempc_qp_layout(const fsaempc_qp_desc* desc, int n_slack, int out[4]);
+
 /* ---- track pipeline (host side) --------------------------------------------------- */
 
 /* Spline table of a track as main.m:11-17 produces it: M arc-length segments, xP / yP = M x 4 Bezier control points per axis
