@@ -549,6 +549,15 @@ template <int C> struct IC { static constexpr int value = C; };
 //   (The wrong iterates of some -O2/-O3 builds were NOT a ring hazard: DESIGN.md, "Build-variant fragility: root cause".)
 // The asm memory clobbers keep the compiler from moving LDS reads or DMA issues across the wait.
 // ---------------------------------------------------------------------------------------------
+#if defined(QP_STREAM_CARRY) && (defined(QP_DRAIN_STREAM) || defined(QP_MFMA_SOLVES))
+#error "QP_STREAM_CARRY: the full-drain ring restarts per pass by construction, and the MFMA solves use the ring as scratch between passes"
+#endif
+DEVINL int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }   // a wave-uniform value the compiler could not prove uniform -> SGPR
+DEVINL const char* uni(const char* p) {
+  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
+}
 #ifdef QP_DRAIN_STREAM   // the full-drain double buffer of the fragility investigation (kept for A/B runs): lead = one pair
 template <int T> struct StreamCfg {
   static constexpr int R = 3 * T;   // (ring sized as below so that both variants share the LDS layout)
@@ -557,13 +566,21 @@ template <int T> struct Stream {
   static constexpr int R = StreamCfg<T>::R;
   const char* gnext;   // wave-uniform: global address of the next record to issue
   int half;            // ring half that holds the pair to consume next
+  int tend[T + 1];     // phase ends of the stream directory (read once, see below)
   DEVINL void issue(const Ctx& k, int slot) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gnext + k.lane * 16),
                                      (__attribute__((address_space(3))) void*)(k.ring + slot * 128), 16, 0, 0);
     gnext += 1024;
   }
-  DEVINL void start(const Ctx& k, int c0) {   // c0: tile count of the first pair
+  DEVINL void open(const Ctx& k) {
+#pragma unroll
+    for (int C = 0; C <= T; ++C) tend[C] = uni(k.tend[C]);
+  }
+  DEVINL void start(const Ctx& k) {
+#pragma unroll
+    for (int C = 0; C <= T; ++C) tend[C] = uni(tend[C]);
     gnext = reinterpret_cast<const char*>(k.Aw); half = 0;
+    const int c0 = k.ntr > 0 ? k.tcs[0] : 0;   // tile count of the first pair
 #pragma unroll
     for (int t = 0; t < T; ++t) if (t < c0) issue(k, t);
   }
@@ -577,36 +594,106 @@ template <int T> struct Stream {
     for (int t = 0; t < C; ++t) b[t] = *reinterpret_cast<const v2d*>(k.ring + (half * T + t) * 128 + k.lane * 2);
     half ^= 1;
   }
-  DEVINL void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+  DEVINL void finish() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+  DEVINL void close() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 };
 #else
 // Lead of D = 2T records (two pairs of k-steps at the full tile count, more in the sparse early trips) behind a COUNTED wait:
 // a pair's C records are consumed after C new ones have been issued and `s_waitcnt vmcnt(D)` says that at most D vector-memory
 // operations are still outstanding.  Loads (LDS-DMA, global, scratch) return in issue order, so the D newest outstanding loads
-// are never this pair's; stores may retire in any order, which can only make the wait longer, never shorter.  The producer walks
-// the linear record stream and runs up to D records past its end (still inside this QP's workspace).  One pair of lead (the
-// full-drain variant above) left passes 2 and 3 waiting on the DMA: their VALU work per pair is shorter than the latency.
+// are never this pair's; stores may retire in any order, which can only make the wait longer, never shorter.  One pair of lead
+// (the full-drain variant above) left passes 2 and 3 waiting on the DMA: their VALU work per pair is shorter than the latency.
+//
+// ONE Stream object per kernel invocation, taken by reference by every pass.  open() reads the phase ends tend[0..T] of the stream
+// directory once, before the kernel's first store, as scalar loads; read inside a pass they are vector loads (the kernel has
+// stored to global memory by then, the compiler may no longer treat the directory as unclobbered), and the wait for an ordinary
+// load in a loop that issues LDS-DMA is a full `vmcnt(0)`: five drains of the ring per pass (1 % of the headline solve kernel).
+//
+// Shipped: every pass restarts at record 0 with an empty ring (start() issues D records), the producer runs up to D records past
+// the end of the stream (still inside this QP's workspace) and finish() drains those dead loads before the pass returns.
+//
+// -DQP_STREAM_CARRY (A/B runs; measured and NOT shipped, profiles/stream_carry/README.md) carries the producer from pass to
+// pass instead.  Every pass consumes the same nrec = aoff[ntr] records from record 0 in the same order and the producer issues
+// one record per record consumed, so the D records it is ahead at the end of a pass are, with the address wrapped at the end
+// of A~, records 0..D-1 of the NEXT pass: open() issues the first D records once, no pass starts cold and nothing is fetched
+// that is not consumed (the last pass of the kernel excepted).
+//   Invariant between passes: the producer is exactly D records ahead; ring slots slot_e .. slot_e+D-1 (mod R) hold -- or have
+//   in flight -- records 0..D-1 (mod nrec) of A~; gnext is the address of record D mod nrec, `left` the records before its next
+//   wrap.  The T slots behind them are dead.  Nobody but issue() writes the ring (the tile-transpose scratch that shares its LDS
+//   exists only under -DQP_MFMA_SOLVES, which cannot be combined with the carry), and A~ is constant for the whole kernel, so a
+//   record fetched early is the record a later fetch would see.
+//   The counted wait is unchanged: whatever vector-memory loads the code between two passes issues come AFTER the carried head
+//   in issue order, so at a pass's first `vmcnt(D)` the D newest outstanding loads are again never the pair about to be read.
+//   A stream shorter than the lead (nrec < D) wraps more than once per pass; the ring then holds repeats of the stream, the
+//   record count per wait -- and hence the wait -- is the same.
+//   finish() then ends a pass without a wait (nothing the pass itself still needs is outstanding; -DQP_STREAM_PASS_DRAIN puts the
+//   full drain back, same speed), and close() is the one full drain before the wave ends: no LDS-DMA may land in LDS that has
+//   been handed to another workgroup.
+//   Why it does not pay: the first coefficient slot of a pass (CoefStage, ordinary loads) is waited for with a full drain at the
+//   top of the first trip anyway, so the cold start of the ring hides behind a latency that stays, while the wrap costs scalar
+//   work per record.
 template <int T> struct StreamCfg {
   static constexpr int D = 2 * T;
   static constexpr int R = D + T;
 };
 template <int T> struct Stream {
   static constexpr int D = StreamCfg<T>::D, R = StreamCfg<T>::R;
-  const char* gnext; int slot_i, slot_e;
+  // wave-uniform producer / consumer state: next global address, ring slots to issue into / consume from; carried stream only:
+  // records left before the producer wraps, records of the stream
+  const char* gnext; int slot_i, slot_e, left, nrec;
+  int tend[T + 1];   // phase ends of the stream directory (tend[C] = number of trips with at most C tiles), read once
   DEVINL void issue(const Ctx& k) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gnext + k.lane * 16),
                                      (__attribute__((address_space(3))) void*)(k.ring + slot_i * 128), 16, 0, 0);
     gnext += 1024;
     slot_i = slot_i + 1 == R ? 0 : slot_i + 1;
   }
-  DEVINL void start(const Ctx& k, int) {
-    gnext = reinterpret_cast<const char*>(k.Aw); slot_i = 0; slot_e = 0;
+  DEVINL void issue_wrap(const Ctx& k) {
+    issue(k);
+    if (--left == 0) { gnext = reinterpret_cast<const char*>(k.Aw); left = nrec; }
+  }
+  DEVINL void open(const Ctx& k) {   // once per kernel invocation, before the first pass
+    gnext = reinterpret_cast<const char*>(k.Aw); slot_i = 0; slot_e = 0; left = nrec = 0;
 #pragma unroll
-    for (int j = 0; j < D; ++j) issue(k);
+    for (int C = 0; C <= T; ++C) tend[C] = uni(k.tend[C]);
+#ifdef QP_STREAM_CARRY
+    if (k.ntr > 0) {
+      left = nrec = uni(k.aoff[k.ntr]);
+#pragma unroll
+      for (int j = 0; j < D; ++j) issue_wrap(k);
+    }
+#endif
+  }
+  // Top of a pass.  Called on EVERY path into the pass, an empty stream (ntr == 0) included: the state has come through loops whose
+  // exits depend on cross-lane reductions, the compiler takes it for divergent, and one path on which it is not made uniform again
+  // puts it -- and the address and slot arithmetic of every record -- into vector registers.
+  DEVINL void start(const Ctx& k) {
+#ifndef QP_STREAM_CARRY
+    gnext = reinterpret_cast<const char*>(k.Aw); slot_i = 0; slot_e = 0;
+    if (k.ntr > 0) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) issue(k);
+    }
+#else
+    gnext = uni(gnext); slot_i = uni(slot_i); slot_e = uni(slot_e); left = uni(left); nrec = uni(nrec);
+#endif
+#pragma unroll
+    for (int C = 0; C <= T; ++C) tend[C] = uni(tend[C]);
   }
   template <int C> DEVINL void next_pair(const Ctx& k, v2d* b, int) {
+#ifndef QP_STREAM_CARRY
 #pragma unroll
     for (int t = 0; t < C; ++t) issue(k);
+#else
+    if (left > C) {   // (all but one pair of a pass: no wrap inside this group)
+#pragma unroll
+      for (int t = 0; t < C; ++t) issue(k);
+      left -= C;
+    } else {
+#pragma unroll
+      for (int t = 0; t < C; ++t) issue_wrap(k);
+    }
+#endif
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(D) : "memory");
 #pragma unroll
     for (int t = 0; t < C; ++t) {
@@ -615,7 +702,12 @@ template <int T> struct Stream {
     }
     slot_e += C; if (slot_e >= R) slot_e -= R;
   }
-  DEVINL void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+  DEVINL void finish() {   // end of a pass (ntr > 0)
+#if !defined(QP_STREAM_CARRY) || defined(QP_STREAM_PASS_DRAIN)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+  }
+  DEVINL void close() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 };
 #endif
 
@@ -643,7 +735,7 @@ template <int NA> struct CoefStage {
 // The stream is walked trip by trip (4 k-steps); a trip with tc column tiles only touches the tc(tc+1)/2 accumulator
 // tiles it can reach.  Trips are sorted by tc, so the pass is T phases with compile-time tile counts (phase C: all
 // trips with tc == C) and no branches inside a trip.
-template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, v4d* acc, double* P1, double* P2, double* P3, double* MB) {
+template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, Stream<T>& st, v4d* acc, double* P1, double* P2, double* P3, double* MB) {
   constexpr int NBB = NB > 0 ? NB : 1;
   constexpr int NA = 4 + NB;
   const int JS = k.J * 64;
@@ -663,13 +755,13 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, v4d* acc, double* P
     for (int f = 0; f < NBB; ++f) sbb[e][f] = 0;
     pwb[0][e] = pwb[1][e] = pwb[2][e] = 0;
   }
-  Stream<T> st;
   CoefStage<NA> cs;
   int tr = 0;
-  if (k.ntr > 0) { st.start(k, k.tcs[0]); cs.load(k, arr, 0); }
+  st.start(k);
+  if (k.ntr > 0) cs.load(k, arr, 0);
   auto phase = [&](auto Cc) __attribute__((always_inline)) {
     constexpr int C = decltype(Cc)::value;
-    const int tr_end = k.tend[C];
+    const int tr_end = st.tend[C];
     for (; tr < tr_end; ++tr) {
       if ((tr & 3) == 0) { cs.commit(k); cs.load(k, arr, (tr >> 2) + 1); }
 #pragma unroll
@@ -716,7 +808,7 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, v4d* acc, double* P
   if constexpr (T >= 6) phase(IC<6>{});
   if constexpr (T >= 7) phase(IC<7>{});
   if constexpr (T >= 8) phase(IC<8>{});
-  if (k.ntr > 0) st.drain();
+  if (k.ntr > 0) st.finish();
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     double v1 = q_sum(p1[t]), v2 = q_sum(p2[t]), v3 = q_sum(p3[t]);
@@ -742,7 +834,7 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, v4d* acc, double* P
 //   w_r = (va+a1)(b1 + c1 (va+a1)) - (a2-va)(b2 + c2 (a2-va))      (a,b,c: per-row coefficients of row phase 1)
 // is formed and p_cor += w_r a_r is accumulated in the same pass (saves one full stream over A per iteration).
 // FUSE 3 is the polish step (see the kernel).  Same operand stream and phase structure as pass 1.
-template <int T, int NB, int NVEC, int FUSE> DEVINL void pass_Av(const Ctx& k, const double* const* vin, double* const* rout, double* Pcor, double* Pcor2 = nullptr, const double* const* cfarr = nullptr) {
+template <int T, int NB, int NVEC, int FUSE> DEVINL void pass_Av(const Ctx& k, Stream<T>& st, const double* const* vin, double* const* rout, double* Pcor, double* Pcor2 = nullptr, const double* const* cfarr = nullptr) {
   constexpr int NBB = NB > 0 ? NB : 1;
   constexpr int NC = FUSE == 1 ? 6 : (FUSE >= 2 ? 3 : 0);   // per-row coefficient arrays of the fused part
   constexpr int NA = NC + NB;
@@ -769,13 +861,13 @@ template <int T, int NB, int NVEC, int FUSE> DEVINL void pass_Av(const Ctx& k, c
   double keep[NVEC + 1];   // last entry: the updated multiplier of the polish modes (written to rout[NVEC])
 #pragma unroll
   for (int e = 0; e < NVEC + 1; ++e) keep[e] = 0.0;
-  Stream<T> st;
   CoefStage<NA> cs;
   int tr = 0;
-  if (k.ntr > 0) { st.start(k, k.tcs[0]); if (NA > 0) cs.load(k, arr, 0); }
+  st.start(k);
+  if (k.ntr > 0 && NA > 0) cs.load(k, arr, 0);
   auto phase = [&](auto Cc) __attribute__((always_inline)) {
     constexpr int C = decltype(Cc)::value;
-    const int tr_end = k.tend[C];
+    const int tr_end = st.tend[C];
     for (; tr < tr_end; ++tr) {
       if (NA > 0 && (tr & 3) == 0) { cs.commit(k); cs.load(k, arr, (tr >> 2) + 1); }
 #pragma unroll
@@ -833,7 +925,7 @@ template <int T, int NB, int NVEC, int FUSE> DEVINL void pass_Av(const Ctx& k, c
   if constexpr (T >= 6) phase(IC<6>{});
   if constexpr (T >= 7) phase(IC<7>{});
   if constexpr (T >= 8) phase(IC<8>{});
-  if (k.ntr > 0) st.drain();
+  if (k.ntr > 0) st.finish();
   if (FUSE) {
 #pragma unroll
     for (int t = 0; t < T; ++t) {
@@ -1264,6 +1356,10 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
   };
   auto hx_full = [&](const double* XV) __attribute__((always_inline)) { hx_tiles<T>(k, XV, HX); hx_border(XV); };
 
+  // the operand stream of every pass of this invocation: its first D records fly while the vectors and bounds are set up
+  Stream<T> st;
+  st.open(k);
+
   // ---- load n-vectors, initial x = clamp(0, l, u) (scaled), count finite sides ----
   for (int i = lane; i < k.np; i += 64) { G[i] = gw[i]; EV[i] = Es[i]; R1[i] = 0; R2[i] = 0; DX[i] = 0; }
   int cnt_local = 0, infeas = 0;
@@ -1304,7 +1400,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
   // ---- v = G x ----
   {
     const double* vin[1] = {X}; double* rout[1] = {aV};
-    pass_Av<T, NB, 1, 0>(k, vin, rout, nullptr);
+    pass_Av<T, NB, 1, 0>(k, st, vin, rout, nullptr);
     for (int jb = 0; jb < k.JB; ++jb) { const int i = jb * 64 + lane; aV[(J + jb) * 64 + lane] = i < n ? X[i] : 0.0; }
   }
   // ---- initial slacks / multipliers in the equilibrated problem: t = max(resid, T0), z = Z0 (a scan over the
@@ -1597,7 +1693,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
     hx_border(X);
     STAMP(2);
 #endif
-    pass_syrk<T, NB>(k, acc, P1, P2, P3, MB);
+    pass_syrk<T, NB>(k, st, acc, P1, P2, P3, MB);
     WAVE_SYNC();
     STAMP(3);
     // objective, dual residual
@@ -1700,7 +1796,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
     // ================= pass 2: va = G dxa, vc = G dxc =================
     {
       const double* vin[2] = {R1, R2}; double* rout[2] = {aVA, aVC};
-      pass_Av<T, NB, 2, 1>(k, vin, rout, P1);   // fused: P1 = A~' w_cor
+      pass_Av<T, NB, 2, 1>(k, st, vin, rout, P1);   // fused: P1 = A~' w_cor
       for (int jb = 0; jb < k.JB; ++jb) {
         const int i = jb * 64 + lane;
         aVA[(J + jb) * 64 + lane] = i < n ? R1[i] : 0.0;
@@ -1763,7 +1859,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
     // ================= pass 4: G dx_cor =================
     {
       const double* vin[1] = {DX}; double* rout[1] = {aW2};  // W2 reused for G dx_cor
-      pass_Av<T, NB, 1, 0>(k, vin, rout, nullptr);
+      pass_Av<T, NB, 1, 0>(k, st, vin, rout, nullptr);
       for (int jb = 0; jb < k.JB; ++jb) { const int i = jb * 64 + lane; aW2[(J + jb) * 64 + lane] = i < n ? DX[i] : 0.0; }
     }
     STAMP(11);
@@ -1924,7 +2020,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
     double* ATR = R1; double* ATP = P3;                                               // A_W'r and A_W'p (n-vectors, by recurrence)
     if (!v_current) {
       const double* vin[1] = {X}; double* rout[1] = {aV};
-      pass_Av<T, NB, 1, 0>(k, vin, rout, nullptr);
+      pass_Av<T, NB, 1, 0>(k, st, vin, rout, nullptr);
       for (int jb = 0; jb < k.JB; ++jb) { const int i = jb * 64 + lane; aV[(J + jb) * 64 + lane] = i < n ? X[i] : 0.0; }
     }
     for (int js = 0; js < JT; ++js) {
@@ -1948,7 +2044,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
     }
     WAVE_SYNC();
     acc_init<T>(k, acc);
-    pass_syrk<T, NB>(k, acc, P1, P2, P3, MB);
+    pass_syrk<T, NB>(k, st, acc, P1, P2, P3, MB);
     WAVE_SYNC();
     for (int i = lane; i < k.np; i += 64) { R1[i] = 0.0; R2[i] = 0.0; }
     WAVE_SYNC();
@@ -1965,7 +2061,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
     // gradient of the augmented Lagrangian at (z, y): v = A~z, y^ = y - rho c, P1 = A~'y^, P2 = rho A_W'c; then grad = H~z + g - P1
     auto eval_zy = [&]() __attribute__((always_inline)) {
       const double* vin[1] = {R2}; double* rout[2] = {aVA, aVC};
-      pass_Av<T, NB, 1, 3>(k, vin, rout, P1, P2, cf_eval);
+      pass_Av<T, NB, 1, 3>(k, st, vin, rout, P1, P2, cf_eval);
       hx_full(R2);
       WAVE_SYNC();
     };
@@ -2012,7 +2108,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
         WAVE_SYNC();
         {
           const double* vin[1] = {DX}; double* rout[2] = {aVA, aVC};
-          pass_Av<T, NB, 1, 3>(k, vin, rout, P1, P2, cf_cg);   // aVA = A~w; P2 = rho A_W'(A_W w)
+          pass_Av<T, NB, 1, 3>(k, st, vin, rout, P1, P2, cf_cg);   // aVA = A~w; P2 = rho A_W'(A_W w)
         }
         WAVE_SYNC();
         double pq_l = 0.0;
@@ -2186,6 +2282,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
   }
   STAMP(13);
   STAMP_OUT;
+  st.close();   // every exit of the iteration loop and of the refinement, and the early flags -1 / -2, come through here
 #ifdef QP_DEBUG_DUMP
   if (P.dump && P.dump_stage == 5 && b == P.dump_iter && lane == 0) { double* o_ = P.dump + 16 * 120; o_[0] = (double)flag; o_[1] = (double)it; o_[2] = (double)flag_polished; o_[3] = merit_s; }
 #endif
@@ -2272,8 +2369,11 @@ template <int T, int NB> __global__ __launch_bounds__(64) void syrk_probe_kernel
   v4d acc[Tri<T>::NT];
   acc_init<T>(k, acc);
   const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-  for (int r = 0; r < reps; ++r) {
-    pass_syrk<T, NB>(k, acc, vecp(k, V_P1), vecp(k, V_P2), vecp(k, V_P3), MB);
+  for (int r = 0; r < reps; ++r) {   // a fresh stream per repetition: the cost of one pass from a cold start
+    Stream<T> st;
+    st.open(k);
+    pass_syrk<T, NB>(k, st, acc, vecp(k, V_P1), vecp(k, V_P2), vecp(k, V_P3), MB);
+    st.close();
     __syncthreads();
   }
   const unsigned long long t1 = __builtin_amdgcn_s_memtime();
