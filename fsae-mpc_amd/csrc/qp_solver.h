@@ -72,6 +72,7 @@ __host__ __device__ inline int qp_solver_index(const QpDims& d, int u) { const i
 bool qp_runs_wavefront_kernel(const QpDims& d);   // kernel selection of qp_launch
 hipError_t qp_launch(const QpParams& P, int batch, hipStream_t st, hipEvent_t ev_mid = nullptr);
 int qp_selftest_mfma(char* msg, int msglen);
+int qp_selftest_lane_reduce(char* msg, int msglen);   // DPP / lane-swap reductions against zero-filling moves and an LDS tree
 // LDS bytes of the workgroup solve kernel (qp_wg.hip); NBk = border width of the kernel variant (0 or 4).  Mirrors the carve at
 // the top of qp_wg_kernel.
 #define QP_WG_NVEC_FIXED 14   /* X G HX P1 P2 P3 DX E R1 R2 + DV W1V W2V LV */

@@ -40,6 +40,11 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 // The solve kernel runs one wavefront per workgroup: its lanes exchange data through LDS (and their own rows of global
 // memory) in program order, and the hardware keeps the DS / vector-memory operations of one wave in order, so a
 // workgroup barrier (s_barrier + full s_waitcnt drain) is not needed -- a compiler-level fence is.
+// 1: the two right-hand sides of an iteration's factor go through the triangular solves together (A/B builds; the shipped build
+// solves them one after the other: profiles/lane_reduce/README.md)
+#ifndef QP_SOLVE_PAIR
+#define QP_SOLVE_PAIR 0
+#endif
 #ifndef QP_FULL_BARRIERS
 #define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 #else
@@ -53,26 +58,51 @@ DEVINL double rl(double v, int src) {  // wave-uniform broadcast of lane `src` (
   int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
   return __hiloint2double(hi, lo);
 }
-template <int CTRL> DEVINL double dpp_f64(double v) {  // data-parallel-primitive lane move of both halves (VALU speed, no LDS)
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+// Lane move of both halves of a double (VALU speed, no LDS).  ZF = false leaves the destination's old value undefined: no zero is
+// written into the destination first (one v_mov per half and move), which is only correct where EVERY lane of the wave is active --
+// with bound_ctrl off a disabled source lane leaves `old` in the destination.  All the controls used here (quad_perm,
+// row_half_mirror, row_mirror; full row and bank masks) have a valid source lane for every destination lane, so with all 64 lanes
+// active `old` is never observable.  ZF = true is the zero-filling form for call sites in (possibly) lane-divergent control flow.
+template <int CTRL, bool ZF = false> DEVINL double dpp_f64(double v) {
+  int lo, hi;
+  if (ZF) {
+    lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+  } else {
+    lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, false);
+  }
   return __hiloint2double(hi, lo);
 }
-DEVINL double grp16_sum(double v) {  // sum over the 16 lanes sharing l>>4 (one DPP row); every lane gets the total
-  v += dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141>(v);   // row_half_mirror
-  v += dpp_f64<0x140>(v);   // row_mirror
-  return v;
+struct OpSum { static DEVINL double f(double a, double b) { return a + b; } };
+struct OpMax { static DEVINL double f(double a, double b) { return fmax(a, b); } };
+struct OpMin { static DEVINL double f(double a, double b) { return fmin(a, b); } };
+// Reduction over the 16 lanes sharing l>>4 (one DPP row) of N independent values; every lane gets the totals.  Pairing: lane^1,
+// lane^2, lane <-> 7-lane within 8, lane <-> 15-lane within 16.  Each step is done for all N before the next one, so the N chains
+// (move -> add -> move ...) are interleaved in source order and fill each other's DPP hazard slots.
+template <class OP, int CTRL, bool ZF, int N> DEVINL void grp16_step(double (&v)[N]) {
+  double m[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) m[i] = dpp_f64<CTRL, ZF>(v[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = OP::f(v[i], m[i]);
 }
-DEVINL double grp16_max(double v) {
-  v = fmax(v, dpp_f64<0xB1>(v)); v = fmax(v, dpp_f64<0x4E>(v)); v = fmax(v, dpp_f64<0x141>(v)); v = fmax(v, dpp_f64<0x140>(v));
-  return v;
+template <class OP, bool ZF, int N> DEVINL void grp16_reduce(double (&v)[N]) {
+  grp16_step<OP, 0xB1, ZF>(v);    // quad_perm [1,0,3,2]
+  grp16_step<OP, 0x4E, ZF>(v);    // quad_perm [2,3,0,1]
+  grp16_step<OP, 0x141, ZF>(v);   // row_half_mirror
+  grp16_step<OP, 0x140, ZF>(v);   // row_mirror
 }
-DEVINL double grp16_min(double v) {
-  v = fmin(v, dpp_f64<0xB1>(v)); v = fmin(v, dpp_f64<0x4E>(v)); v = fmin(v, dpp_f64<0x141>(v)); v = fmin(v, dpp_f64<0x140>(v));
-  return v;
-}
+template <int N> DEVINL void grp16_sum(double (&v)[N]) { grp16_reduce<OpSum, false>(v); }
+template <int N> DEVINL void grp16_max(double (&v)[N]) { grp16_reduce<OpMax, false>(v); }
+template <int N> DEVINL void grp16_min(double (&v)[N]) { grp16_reduce<OpMin, false>(v); }
+DEVINL double grp16_sum(double v) { double a[1] = {v}; grp16_reduce<OpSum, false>(a); return a[0]; }
+DEVINL double grp16_max(double v) { double a[1] = {v}; grp16_reduce<OpMax, false>(a); return a[0]; }
+DEVINL double grp16_min(double v) { double a[1] = {v}; grp16_reduce<OpMin, false>(a); return a[0]; }
+// the zero-filling forms (correct with disabled lanes: those contribute a zero)
+DEVINL double grp16_sum_zf(double v) { double a[1] = {v}; grp16_reduce<OpSum, true>(a); return a[0]; }
+DEVINL double grp16_max_zf(double v) { double a[1] = {v}; grp16_reduce<OpMax, true>(a); return a[0]; }
+DEVINL double grp16_min_zf(double v) { double a[1] = {v}; grp16_reduce<OpMin, true>(a); return a[0]; }
 // Exchange between the four 16-lane rows of a wave with the gfx950 lane-swap instructions (VALU speed; the ds_bpermute
 // round trips of __shfl_xor cost ~100 cycles each and a wave reduction needed twelve of them):
 //   v_permlane16_swap a, b : a.row1 <-> b.row0, a.row3 <-> b.row2     v_permlane32_swap a, b : a.rows23 <-> b.rows01
@@ -100,6 +130,22 @@ DEVINL double q_min(double v) { RowPair r = rows_xor16(v); v = fmin(r.a, r.b); r
 DEVINL double wave_sum(double v) { return q_sum(grp16_sum(v)); }
 DEVINL double wave_max(double v) { return q_max(grp16_max(v)); }
 DEVINL double wave_min(double v) { return q_min(grp16_min(v)); }
+DEVINL double wave_sum_zf(double v) { return q_sum(grp16_sum_zf(v)); }
+DEVINL double wave_max_zf(double v) { return q_max(grp16_max_zf(v)); }
+DEVINL double wave_min_zf(double v) { return q_min(grp16_min_zf(v)); }
+// N independent sums over the four lane groups / over the whole wave, step by step for all N
+template <int N> DEVINL void q_sum(double (&v)[N]) {
+  RowPair r[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) r[i] = rows_xor16(v[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = r[i].a + r[i].b;
+#pragma unroll
+  for (int i = 0; i < N; ++i) r[i] = rows_xor32(v[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = r[i].a + r[i].b;
+}
+template <int N> DEVINL void wave_sum(double (&v)[N]) { grp16_sum(v); q_sum(v); }
 
 template <int T> struct Tri {
   static constexpr int NT = T * (T + 1) / 2;
@@ -178,7 +224,7 @@ __global__ __launch_bounds__(1024) void qp_prep_kernel(QpParams P) {
     if (Esh[j] < 0) {  // uniform over the workgroup
       double cm = 0;
       for (int r = tid; r < m; r += NTH) cm = fmax(cm, fabs(Aat(r, j)));
-      cm = wave_max(cm);
+      cm = wave_max_zf(cm);   // (prep kernel: keeps the zero-filling lane moves)
       if (lane == 0) red[w] = cm;
       __syncthreads();
       if (tid == 0) { double mx = 0.0; for (int i = 0; i < NW; ++i) mx = fmax(mx, red[i]); Esh[j] = mx > 1e-12 ? 1.0 / mx : 1.0; }
@@ -527,9 +573,11 @@ template <int T> DEVINL void hx_from_acc(const Ctx& k, const v4d* acc, const dou
   for (int J = 0; J < T; ++J) { const double v = q_sum(sc[J]); if (k.q == 0) HX[16 * J + k.c] = v; }
   WAVE_SYNC();
 #pragma unroll
-  for (int I = 0; I < T - 1; ++I)
+  for (int I = 0; I < T - 1; ++I) {
+    grp16_sum(sr[I]);
 #pragma unroll
-    for (int p = 0; p < 4; ++p) { const double v = grp16_sum(sr[I][p]); if (k.c == 0) HX[16 * I + k.q + 4 * p] += v; }
+    for (int p = 0; p < 4; ++p) if (k.c == 0) HX[16 * I + k.q + 4 * p] += sr[I][p];
+  }
 }
 
 template <int C> struct IC { static constexpr int value = C; };
@@ -876,16 +924,24 @@ template <int T, int NB, int NVEC, int FUSE> DEVINL void pass_Av(const Ctx& k, S
         st.template next_pair<C>(k, b, u == 0 ? C : (tr + 1 < tr_end ? C : (tr + 1 < k.ntr ? k.tcs[tr + 1] : 0)));
         if (NA > 0) cs.read_pair(k, 4 * tr + 2 * u, cf);
         asm volatile("" ::: "memory");
+        double ds[2 * NVEC];   // the two k-steps times the NVEC vectors: independent row sums, reduced as one batch
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int e = 0; e < NVEC; ++e) {
+            double a = 0.0;
+#pragma unroll
+            for (int t = 0; t < C; ++t) a = fma(b[t][h], v[e][t], a);
+            ds[h * NVEC + e] = a;
+          }
+        grp16_sum(ds);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int s = 4 * tr + 2 * u + h;
           const int cc = s & 15;
 #pragma unroll
           for (int e = 0; e < NVEC; ++e) {
-            double dsum = 0.0;
-#pragma unroll
-            for (int t = 0; t < C; ++t) dsum = fma(b[t][h], v[e][t], dsum);
-            dsum = grp16_sum(dsum);
+            double dsum = ds[h * NVEC + e];
 #pragma unroll
             for (int f = 0; f < NB; ++f) dsum = fma(cf[NC + f][h], vb[e][f], dsum);
             if (k.c == cc) keep[e] = dsum;
@@ -1169,60 +1225,119 @@ template <int T> DEVINL void reg_backward(const Ctx& k, const v4d* acc, const do
 // riding along the factorisation, as in round 1, they went through substitution-like panel operations; without it 1 of 4096
 // kinematic N = 20 instances diverged), the corrector solve never had it.
 // U'y = b:  t_K = b_K - sum_{I<K} U_IK' y_I (by column),  y_K = U_KK^-T t_K (by row).  B: LDS vector (core part).
-template <int T, bool REFINE> DEVINL void vec_forward(const Ctx& k, const v4d* acc, const double* YL, const double* B, double (&y)[T][4]) {
+// NV right-hand sides of one factor are solved together: one tile load per K for all of them and their reductions as one batch
+// (NV x 4 independent chains); the operations of each vector and their order are those of a solve of that vector alone.
+template <int T, bool REFINE, int NV> DEVINL void vec_forward(const Ctx& k, const v4d* acc, const double* YL, const double* const (&B)[NV], double (&y)[NV][T][4]) {
 #pragma unroll
   for (int K = 0; K < T; ++K) {
-    double s = 0.0;
+    double s[NV], t[NV];
 #pragma unroll
-    for (int I = 0; I < K; ++I)
+    for (int v = 0; v < NV; ++v) {
+      s[v] = 0.0;
 #pragma unroll
-      for (int p = 0; p < 4; ++p) s = fma(acc[Tri<T>::idx(I, K)][p], y[I][p], s);   // this lane group's rows of (U_IK' y_I)[c]
-    const double t = B[16 * K + k.c] - (K > 0 ? q_sum(s) : 0.0);
+      for (int I = 0; I < K; ++I)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) s[v] = fma(acc[Tri<T>::idx(I, K)][p], y[v][I][p], s[v]);   // this lane group's rows of (U_IK' y_I)[c]
+    }
+    if (K > 0) q_sum(s);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) t[v] = B[v][16 * K + k.c] - (K > 0 ? s[v] : 0.0);
     const v4d Yt = tile_load(k, YL + K * 272);                                        // U_KK^-T
+    double yk[NV * 4];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) y[K][p] = grp16_sum(Yt[p] * t);                       // y_K[q+4p] = sum_c Y[q+4p][c] t[c]
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int p = 0; p < 4; ++p) yk[4 * v + p] = Yt[p] * t[v];
+    grp16_sum(yk);                                                                    // y_K[q+4p] = sum_c Y[q+4p][c] t[c]
     if (REFINE) {
       const v4d& U = acc[Tri<T>::idx(K, K)];
 #pragma unroll
       for (int rep = 0; rep < QP_SOLVE_REFINE_STEPS; ++rep) {
-        double r = 0.0;
+        double r[NV], dy[NV * 4];
 #pragma unroll
-        for (int p = 0; p < 4; ++p) r = fma(U[p], y[K][p], r);
-        r = t - q_sum(r);                                                             // t - U_KK' y  (by column)
+        for (int v = 0; v < NV; ++v) {
+          r[v] = 0.0;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) y[K][p] += grp16_sum(Yt[p] * r);
+          for (int p = 0; p < 4; ++p) r[v] = fma(U[p], yk[4 * v + p], r[v]);
+        }
+        q_sum(r);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          r[v] = t[v] - r[v];                                                         // t - U_KK' y  (by column)
+#pragma unroll
+          for (int p = 0; p < 4; ++p) dy[4 * v + p] = Yt[p] * r[v];
+        }
+        grp16_sum(dy);
+#pragma unroll
+        for (int i = 0; i < NV * 4; ++i) yk[i] += dy[i];
       }
     }
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int p = 0; p < 4; ++p) y[v][K][p] = yk[4 * v + p];
   }
 }
-// U x = y:  w_K = y_K - sum_{J>K} U_KJ x_J (by row),  x_K = U_KK^-1 w_K = (U_KK^-T)' w_K (by column) -> X (LDS vector, core part)
-template <int T, bool REFINE> DEVINL void vec_backward(const Ctx& k, const v4d* acc, const double* YL, const double (&y)[T][4], double* X) {
-  double x[T];
+template <int T, bool REFINE> DEVINL void vec_forward(const Ctx& k, const v4d* acc, const double* YL, const double* B, double (&y)[T][4]) {
+  const double* const b1[1] = {B};
+  vec_forward<T, REFINE, 1>(k, acc, YL, b1, reinterpret_cast<double (&)[1][T][4]>(y));
+}
+// U x = y:  w_K = y_K - sum_{J>K} U_KJ x_J (by row),  x_K = U_KK^-1 w_K = (U_KK^-T)' w_K (by column) -> X (LDS vectors, core part)
+template <int T, bool REFINE, int NV> DEVINL void vec_backward(const Ctx& k, const v4d* acc, const double* YL, const double (&y)[NV][T][4], double* const (&X)[NV]) {
+  double x[NV][T];
 #pragma unroll
   for (int K = T - 1; K >= 0; --K) {
     const v4d Yt = tile_load(k, YL + K * 272);
-    double w[4], s2 = 0.0;
+    double w[NV * 4], s[NV * 4], s2[NV];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      double s = 0.0;
+    for (int v = 0; v < NV; ++v)
 #pragma unroll
-      for (int J = K + 1; J < T; ++J) s = fma(acc[Tri<T>::idx(K, J)][p], x[J], s);    // this lane's column of (U_KJ x_J)[q+4p]
-      w[p] = y[K][p] - (K < T - 1 ? grp16_sum(s) : 0.0);
-      s2 = fma(Yt[p], w[p], s2);
+      for (int p = 0; p < 4; ++p) {
+        s[4 * v + p] = 0.0;
+#pragma unroll
+        for (int J = K + 1; J < T; ++J) s[4 * v + p] = fma(acc[Tri<T>::idx(K, J)][p], x[v][J], s[4 * v + p]);   // this lane's column of (U_KJ x_J)[q+4p]
+      }
+    if (K < T - 1) grp16_sum(s);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      s2[v] = 0.0;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        w[4 * v + p] = y[v][K][p] - (K < T - 1 ? s[4 * v + p] : 0.0);
+        s2[v] = fma(Yt[p], w[4 * v + p], s2[v]);
+      }
     }
-    x[K] = q_sum(s2);
+    q_sum(s2);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) x[v][K] = s2[v];
     if (REFINE) {
       const v4d& U = acc[Tri<T>::idx(K, K)];
 #pragma unroll
       for (int rep = 0; rep < QP_SOLVE_REFINE_STEPS; ++rep) {
-        double d = 0.0;
+        double d[NV], ux[NV * 4];
 #pragma unroll
-        for (int p = 0; p < 4; ++p) d = fma(Yt[p], w[p] - grp16_sum(U[p] * x[K]), d);  // Y' (w - U_KK x)
-        x[K] += q_sum(d);
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+          for (int p = 0; p < 4; ++p) ux[4 * v + p] = U[p] * x[v][K];
+        grp16_sum(ux);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          d[v] = 0.0;
+#pragma unroll
+          for (int p = 0; p < 4; ++p) d[v] = fma(Yt[p], w[4 * v + p] - ux[4 * v + p], d[v]);   // Y' (w - U_KK x)
+        }
+        q_sum(d);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) x[v][K] += d[v];
       }
     }
-    if (k.q == 0) X[16 * K + k.c] = x[K];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) if (k.q == 0) X[v][16 * K + k.c] = x[v][K];
   }
+}
+template <int T, bool REFINE> DEVINL void vec_backward(const Ctx& k, const v4d* acc, const double* YL, const double (&y)[T][4], double* X) {
+  double* const x1[1] = {X};
+  vec_backward<T, REFINE, 1>(k, acc, YL, reinterpret_cast<const double (&)[1][T][4]>(y), x1);
 }
 // by-row vector <-> LDS vector
 template <int T> DEVINL void vec_rows_store(const Ctx& k, const double (&y)[T][4], double* V) {
@@ -1350,8 +1465,9 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
           if (i < nc) HX[i] += add;
         }
       }
+      wave_sum(sb);
 #pragma unroll
-      for (int e = 0; e < NB; ++e) { const double tot = wave_sum(sb[e]); if (lane == 0) HX[nc + e] = tot; }
+      for (int e = 0; e < NB; ++e) if (lane == 0) HX[nc + e] = sb[e];
     }
   };
   auto hx_full = [&](const double* XV) __attribute__((always_inline)) { hx_tiles<T>(k, XV, HX); hx_border(XV); };
@@ -1477,12 +1593,16 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
   // and y_c - sum_e u_e x_e in the core, ready for the backward sweep
   auto border_solve = [&](double* R) __attribute__((always_inline)) {
     if (NB > 0) {
-      double yb[NBB], xb[NBB];
+      double yb[NBB], xb[NBB], dsum[NBB];
 #pragma unroll
       for (int e = 0; e < NB; ++e) {
-        double dsum = 0.0;
-        for (int h = 0; h < 2; ++h) { const int i = lane + 64 * h; if (i < nc) dsum = fma(MB[e * k.np + i], R[i], dsum); }
-        double tt = R[nc + e] - wave_sum(dsum);
+        dsum[e] = 0.0;
+        for (int h = 0; h < 2; ++h) { const int i = lane + 64 * h; if (i < nc) dsum[e] = fma(MB[e * k.np + i], R[i], dsum[e]); }
+      }
+      wave_sum(dsum);
+#pragma unroll
+      for (int e = 0; e < NB; ++e) {
+        double tt = R[nc + e] - dsum[e];
 #pragma unroll
         for (int g2 = 0; g2 < e; ++g2) tt -= Ubb[g2][e] * yb[g2];
         yb[e] = tt / Ubb[e][e];
@@ -1583,15 +1703,20 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
       }
       WAVE_SYNC();
 #endif
-      double S[NBB][NBB];
+      double S[NBB][NBB], ss[NBB * (NBB + 1) / 2];   // the sums of all S[e][f], e <= f, reduced as one batch
 #pragma unroll
-      for (int e = 0; e < NB; ++e)
+      for (int e = 0, j = 0; e < NB; ++e)
 #pragma unroll
-        for (int f = e; f < NB; ++f) {
+        for (int f = e; f < NB; ++f, ++j) {
           double dsum = 0.0;
           for (int h = 0; h < 2; ++h) { const int i = lane + 64 * h; if (i < nc) dsum = fma(MB[e * k.np + i], MB[f * k.np + i], dsum); }
-          S[e][f] = MB[e * k.np + nc + f] - wave_sum(dsum);
+          ss[j] = dsum;
         }
+      wave_sum(ss);
+#pragma unroll
+      for (int e = 0, j = 0; e < NB; ++e)
+#pragma unroll
+        for (int f = e; f < NB; ++f, ++j) S[e][f] = MB[e * k.np + nc + f] - ss[j];
 #pragma unroll
       for (int e = 0; e < NB; ++e) {
         double dd = S[e][e];
@@ -1619,9 +1744,14 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
     { double* vout[2] = {R1, R2}; rhs_store<T, 2>(k, rh, vout); }
 #else
     {
-      double y1[T][4], y2[T][4];
+      double y12[2][T][4];
+      double (&y1)[T][4] = y12[0], (&y2)[T][4] = y12[1];
+#if QP_SOLVE_PAIR
+      { const double* const b12[2] = {R1, R2}; vec_forward<T, true, 2>(k, acc, YL, b12, y12); }
+#else
       vec_forward<T, true>(k, acc, YL, R1, y1);
       vec_forward<T, true>(k, acc, YL, R2, y2);
+#endif
       if (NB > 0) {
         WAVE_SYNC();
         vec_rows_store<T>(k, y1, R1); vec_rows_store<T>(k, y2, R2);
@@ -1630,8 +1760,12 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
         vec_rows_load<T>(k, R1, y1); vec_rows_load<T>(k, R2, y2);
       }
       WAVE_SYNC();
+#if QP_SOLVE_PAIR
+      { double* const x12[2] = {R1, R2}; vec_backward<T, true, 2>(k, acc, YL, y12, x12); }
+#else
       vec_backward<T, true>(k, acc, YL, y1, R1);
       vec_backward<T, true>(k, acc, YL, y2, R2);
+#endif
     }
 #endif
     WAVE_SYNC();
@@ -2334,6 +2468,107 @@ __global__ void mfma_selftest_kernel(const double* Am, const double* Bm, double*
 #pragma unroll
   for (int p = 0; p < 4; ++p) Cm[((lane >> 4) + 4 * p) * 16 + (lane & 15)] = c[p];
 }
+
+// ---------------------------------------------------------------------------------------------
+// Lane-reduction self test: one wave, all lanes active.  Every reduction (single, batched, 16-lane row / four rows / whole wave) is
+// compared bit for bit (NaN = NaN) with the zero-filling lane moves and with a plain tree through LDS that pairs the same lanes
+// in the same order: lane^1, lane^2, lane <-> 7-lane within 8, lane <-> 15-lane within 16, rows 0<->1 and 2<->3, halves.
+// ---------------------------------------------------------------------------------------------
+DEVINL bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b) || (a != a && b != b); }
+template <class OP> DEVINL double lds_grp16(double* sh, int lane, double v) {
+  const int src[4] = {lane ^ 1, lane ^ 2, (lane & ~7) | (7 - (lane & 7)), (lane & ~15) | (15 - (lane & 15))};
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    sh[lane] = v; __syncthreads();
+    const double o = sh[src[s]]; __syncthreads();
+    v = OP::f(v, o);
+  }
+  return v;
+}
+template <class OP> DEVINL double lds_q(double* sh, int lane, double v) {   // (row0,row1) -> row0 op row1 on both, as the lane swaps give it
+#pragma unroll
+  for (int bit = 16; bit <= 32; bit <<= 1) {
+    sh[lane] = v; __syncthreads();
+    const double a = sh[lane & ~bit], b = sh[lane | bit]; __syncthreads();
+    v = OP::f(a, b);
+  }
+  return v;
+}
+DEVINL double q_named(OpSum, double v) { return q_sum(v); }
+DEVINL double q_named(OpMax, double v) { return q_max(v); }
+DEVINL double q_named(OpMin, double v) { return q_min(v); }
+DEVINL double wave_named(OpSum, double v) { return wave_sum(v); }
+DEVINL double wave_named(OpMax, double v) { return wave_max(v); }
+DEVINL double wave_named(OpMin, double v) { return wave_min(v); }
+DEVINL double wave_named_zf(OpSum, double v) { return wave_sum_zf(v); }
+DEVINL double wave_named_zf(OpMax, double v) { return wave_max_zf(v); }
+DEVINL double wave_named_zf(OpMin, double v) { return wave_min_zf(v); }
+DEVINL double grp16_named(OpSum, double v) { return grp16_sum(v); }
+DEVINL double grp16_named(OpMax, double v) { return grp16_max(v); }
+DEVINL double grp16_named(OpMin, double v) { return grp16_min(v); }
+template <int N> DEVINL void grp16_named(OpSum, double (&v)[N]) { grp16_sum(v); }
+template <int N> DEVINL void grp16_named(OpMax, double (&v)[N]) { grp16_max(v); }
+template <int N> DEVINL void grp16_named(OpMin, double (&v)[N]) { grp16_min(v); }
+template <class OP, int N> DEVINL int lane_reduce_batch_bad(const double (&x)[8], const double (&rz)[8], const double (&rl_)[8]) {
+  double a[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) a[i] = x[i];
+  grp16_named(OP{}, a);
+  int bad = 0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) bad += (same_bits(a[i], rz[i]) ? 0 : 1) + (same_bits(a[i], rl_[i]) ? 0 : 1);
+  return bad;
+}
+// returns this lane's number of mismatches; `first` gets a code (100 * test + op) of the first kind of test that failed
+template <class OP> DEVINL int lane_reduce_op_bad(int op, double* sh, int lane, const double (&x)[8], int& first) {
+  double rz[8], rl_[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    double z[1] = {x[i]};
+    grp16_reduce<OP, true>(z);
+    rz[i] = z[0];
+    rl_[i] = lds_grp16<OP>(sh, lane, x[i]);
+  }
+  int bad = 0, b;
+  auto note = [&](int test, int nb) { if (nb && first < 0) first = 100 * test + op; bad += nb; };
+  { const double g = grp16_named(OP{}, x[0]); note(1, (same_bits(g, rz[0]) ? 0 : 1) + (same_bits(g, rl_[0]) ? 0 : 1)); }
+  b = lane_reduce_batch_bad<OP, 2>(x, rz, rl_); note(2, b);
+  b = lane_reduce_batch_bad<OP, 4>(x, rz, rl_); note(4, b);
+  b = lane_reduce_batch_bad<OP, 8>(x, rz, rl_); note(8, b);
+  { const double g = q_named(OP{}, x[1]); note(16, same_bits(g, lds_q<OP>(sh, lane, x[1])) ? 0 : 1); }
+  {
+    const double g = wave_named(OP{}, x[2]), z = wave_named_zf(OP{}, x[2]), l = lds_q<OP>(sh, lane, rl_[2]);
+    note(64, (same_bits(g, z) ? 0 : 1) + (same_bits(g, l) ? 0 : 1));
+  }
+  return bad;
+}
+__global__ __launch_bounds__(64) void lane_reduce_selftest_kernel(const double* __restrict__ in, int rounds, int* __restrict__ out) {
+  __shared__ double sh[64];
+  const int lane = threadIdx.x;
+  int bad = 0, first = -1, first_round = -1;
+  for (int r = 0; r < rounds; ++r) {   // (uniform trip count: every lane stays active)
+    double x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = in[((size_t)r * 8 + i) * 64 + lane];
+    const int before = bad;
+    bad += lane_reduce_op_bad<OpSum>(0, sh, lane, x, first);
+    bad += lane_reduce_op_bad<OpMax>(1, sh, lane, x, first);
+    bad += lane_reduce_op_bad<OpMin>(2, sh, lane, x, first);
+    {   // adjacent whole-wave sums as one batch
+      double a[4] = {x[4], x[5], x[6], x[7]};
+      wave_sum(a);
+      int nb = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) nb += same_bits(a[i], wave_sum_zf(x[4 + i])) ? 0 : 1;
+      if (nb && first < 0) first = 100 * 65;
+      bad += nb;
+    }
+    if (bad != before && first_round < 0) first_round = r;
+  }
+  if (bad) {
+    if (atomicAdd(&out[0], bad) == 0) { out[1] = first; out[2] = first_round; out[3] = lane; }
+  }
+}
 #endif  // QP_MAIN_TU
 
 }  // namespace
@@ -2688,5 +2923,36 @@ int qp_selftest_mfma(char* msg, int msglen) {
   int bad = 0;
   for (int i = 0; i < 256; ++i) if (hC[i] != ref[i]) { if (!bad) snprintf(msg, msglen, "mfma layout mismatch at (%d,%d): got %g want %g", i / 16, i % 16, hC[i], ref[i]); ++bad; }
   return bad;
+}
+
+int qp_selftest_lane_reduce(char* msg, int msglen) {
+  const int rounds = 256, nval = rounds * 8 * 64;
+  double* h = (double*)malloc(sizeof(double) * nval);
+  if (!h) return -1;
+  unsigned long long st = 0x9E3779B97F4A7C15ull;   // fixed seed
+  auto rnd = [&]() { st = st * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(st >> 33); };
+  for (int i = 0; i < nval; ++i) {   // magnitudes 1e-300 .. 1e300, both signs
+    const double e = -300.0 + 600.0 * (rnd() / 2147483648.0), m = 1.0 + 9.0 * (rnd() / 2147483648.0);
+    h[i] = ((rnd() & 1) ? -1.0 : 1.0) * m * pow(10.0, e);
+  }
+  const double special[8] = {0.0, -0.0, 4.9406564584124654e-324, -2.2250738585072009e-308 / 3.0, INFINITY, -INFINITY, NAN, -NAN};
+  for (int g = 0; g < rounds * 8; ++g) {   // three of four 64-lane vectors get one special value in a single lane
+    const unsigned u = rnd();
+    if ((u & 3) != 0) h[(size_t)g * 64 + ((u >> 2) & 63)] = special[(u >> 8) & 7];
+    if ((u & 0x30000) == 0x30000) h[(size_t)g * 64 + ((u >> 18) & 63)] = special[(u >> 24) & 7];   // sometimes a second one
+  }
+  double* d = 0; int* dout = 0; int hout[4] = {0, 0, 0, 0};
+  if (hipMalloc(&d, sizeof(double) * nval) != hipSuccess || hipMalloc(&dout, sizeof(hout)) != hipSuccess) { free(h); if (d) (void)hipFree(d); return -1; }
+  (void)hipMemcpy(d, h, sizeof(double) * nval, hipMemcpyHostToDevice);
+  (void)hipMemset(dout, 0, sizeof(hout));
+  free(h);
+  hipLaunchKernelGGL(lane_reduce_selftest_kernel, dim3(1), dim3(64), 0, 0, d, rounds, dout);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(hout, dout, sizeof(hout), hipMemcpyDeviceToHost);
+  (void)hipFree(d); (void)hipFree(dout);
+  if (e != hipSuccess) { snprintf(msg, msglen, "lane-reduce selftest: %s", hipGetErrorString(e)); return -1; }
+  if (hout[0]) snprintf(msg, msglen, "lane reductions: %d mismatches, first: test %d (1/2/4/8: grp16 single / batched, 16: q, 64: wave, 65: wave_sum batch) op %d (sum/max/min) round %d lane %d",
+                        hout[0], hout[1] / 100, hout[1] % 100, hout[2], hout[3]);
+  return hout[0];
 }
 #endif  // QP_MAIN_TU

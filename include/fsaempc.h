@@ -576,6 +576,11 @@ const char* fsaempc_last_error(void);
 /* Runs the on-device fp64 MFMA layout self-test (v_mfma_f64_16x16x4_f64 operand / accumulator
  * lane maps the kernels rely on).  Returns 0 if the hardware matches, >0 number of mismatches. */
 int fsaempc_selftest_mfma(void);
+/* Runs the on-device self-test of the cross-lane reductions of the solve kernel (DPP row reductions, single and batched, lane-swap
+ * reductions over the four rows, whole-wave reductions) on 256 rounds of doubles that mix magnitudes 1e-300..1e300, +-0, denormals,
+ * +-Inf and NaN: bit for bit against the zero-filling lane moves and against a tree through LDS with the same pairing.
+ * Returns 0 if all agree, >0 number of mismatches, <0 without a device. */
+int fsaempc_selftest_lane_reduce(void);
 /* Debug hook of the diagnostic builds only (libfsaempc_dbg.so, -DQP_DEBUG_DUMP; the shipped kernels carry no dump
  * branches and ignore it): dumps solver internals of instance 0 after `stage` (see qp_solver.hip) into `out` (device
  * pointer, >= 4*nV*nV+8*(nV+nC) doubles).  Process-global, not thread-safe. */
