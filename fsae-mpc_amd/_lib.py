@@ -24,6 +24,7 @@ EXPORTS = [
     "fsaempc_nlp_build_qp_batch_device_p", "fsaempc_sqp_batch_device_p", "fsaempc_cl_plant_batch_device_p",
     "fsaempc_ltv_blocked_nV", "fsaempc_ltv_build_qp_batch_device_b", "fsaempc_ltv_workspace_bytes_b", "fsaempc_ltv_step_batch_device_b",
     "fsaempc_qp_workspace_bytes_s", "fsaempc_qp_solve_batch_device_s", "fsaempc_qp_layout",
+    "fsaempc_plan_profile_batch_device", "fsaempc_plan_reference_batch_device", "fsaempc_cl_pre_plan_batch_device",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -71,6 +72,13 @@ class LtvParams(C.Structure):
 
 class LtvBlocking(C.Structure):
     _fields_ = [("n_blocks", C.c_int), ("len", C.POINTER(C.c_int))]
+
+
+PLAN_MAX_NS = 4096   # FSAEMPC_PLAN_MAX_NS
+
+
+class PlanTable(C.Structure):   # fsaempc_plan
+    _fields_ = [("table", C.c_void_p), ("t", C.c_void_p), ("N_s", C.c_int), ("ds", C.c_double), ("per_instance", C.c_int)]
 
 
 def check_blocking(blocking, N):
@@ -189,6 +197,11 @@ def lib():
         L.fsaempc_qp_solve_batch_device_s.argtypes = [C.POINTER(QpDesc), C.c_int] + [vp] * 7 + [C.POINTER(QpOpts)] + [vp] * 5 + \
             [C.POINTER(QpAux), vp, ll, vp]
         L.fsaempc_qp_layout.argtypes = [C.POINTER(QpDesc), C.c_int, C.POINTER(C.c_int)]
+        L.fsaempc_plan_profile_batch_device.argtypes = [C.c_int, C.POINTER(Spline), C.c_double, C.POINTER(LtvParams), C.c_int, C.c_int,
+                                                        C.c_double, C.c_double, vp, vp, vp]
+        L.fsaempc_plan_reference_batch_device.argtypes = [C.c_int, C.POINTER(PlanTable), vp, C.c_double, C.c_int, C.c_int, vp, vp]
+        L.fsaempc_cl_pre_plan_batch_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(Spline), C.POINTER(PlanTable),
+                                                       vp, vp, C.c_int, vp, vp, vp, vp]
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p
         L.fsaempc_track_from_csv.argtypes = [C.c_char_p, C.c_int, C.POINTER(TrackTable)]

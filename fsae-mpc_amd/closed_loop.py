@@ -6,6 +6,7 @@ import numpy as np
 
 from ._lib import ParamBlock, Spline, check, check_blocking, lib
 from .ltvmpc import LtvBatch, dims
+from .plan import Plan
 
 
 class ClosedLoop:
@@ -15,12 +16,20 @@ class ClosedLoop:
     plan -- and the exit flags are only tallied.  Cars that completed the lap (s >= L) or left the track keep their state."""
 
     def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
-                 params=None, plant_params=None, blocking=None):
+                 params=None, plant_params=None, blocking=None, reference=None):
         """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
         None = the same as params (both None: the reference's constants compiled into the kernels).  blocking: block lengths of the
-        controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2)."""
+        controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2).  reference: None = the live
+        generator of main.m:107-114 (a ramp to target_vel); a Plan = main.m:115, the cars track it (shared, or one table per car;
+        target_vel is then unused)."""
         if blocking is not None:
             check_blocking(blocking, N)   # (before the library is touched)
+        if reference is not None:
+            if not isinstance(reference, Plan):
+                raise ValueError("reference must be None or a Plan")
+            reference.check_batch(np.asarray(cart0).size // 7)
+            reference.check_device(device)
+        self.reference = reference
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -68,6 +77,12 @@ class ClosedLoop:
     def pre(self, stream=None):
         P = lambda t: C.c_void_p(t.data_ptr())
         s_guess = self.x_opt[:, 0, 0].contiguous()
+        if self.reference is not None:
+            rc = lib().fsaempc_cl_pre_plan_batch_device(self.model, self.N, C.c_double(self.dt), C.c_double(self.track.L), C.byref(self.mpc.sp),
+                                                        self.reference.ref(), P(self.cart), P(s_guess), self.B, P(self.x0), P(self.x_ref),
+                                                        P(self.finished), self._stream(stream))
+            check(rc, "fsaempc_cl_pre_plan_batch_device")
+            return
         rc = lib().fsaempc_cl_pre_batch_device(self.model, self.N, C.c_double(self.dt), C.c_double(self.target_vel), C.c_double(self.track.L),
                                                C.byref(self.mpc.sp), P(self.cart), P(s_guess), self.B, P(self.x0), P(self.x_ref),
                                                P(self.finished), self._stream(stream))
@@ -131,14 +146,15 @@ def monte_carlo_carts(track, B, seed):
 
 
 def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
-                plant_params=None, blocking=None):
+                plant_params=None, blocking=None, reference=None):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
+    reference: None (the live ramp) or a Plan the cars track (ClosedLoop).
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
     import torch
     cart0, s_init = monte_carlo_carts(track, B, seed)
     cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
-                    params=params, plant_params=plant_params, blocking=blocking)
+                    params=params, plant_params=plant_params, blocking=blocking, reference=reference)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

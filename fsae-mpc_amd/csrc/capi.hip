@@ -15,6 +15,7 @@
 #include "ltv_build.h"
 #include "reference.h"
 #include "plant.h"
+#include "planner.h"
 #include "sqp.h"
 #include "qp_sens.h"
 
@@ -938,6 +939,60 @@ int fsaempc_cl_accept_batch_device(int model, int N, int batch, const double* x_
   if (N <= 0 || batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
   hipError_t e = cl_accept_launch(fsaempc_ltv_nx(model) * N, 2 * N, batch, x_new, u_new, exitflag, x_keep, u_keep, (hipStream_t)stream);
   if (e != hipSuccess) return hipfail(e, "cl_accept_launch");
+  return 0;
+}
+
+/* ---- s-domain plans ---- */
+static bool pos_finite(double v) { return v > 0 && v < INFINITY; }
+static int plan_check(const fsaempc_plan* plan, PlanTable* out) {
+  if (!plan || !plan->table || !plan->t) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (plan->N_s < 1 || !pos_finite(plan->ds)) return fail(FSAEMPC_ERR_ARG, "bad plan dimensions");
+  out->table = plan->table; out->t = plan->t; out->N_s = plan->N_s; out->ds = plan->ds; out->per_instance = plan->per_instance ? 1 : 0;
+  return 0;
+}
+
+int fsaempc_plan_profile_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, int n_plans, int N_s,
+                                      double v_cap, double grip, double* table, double* t, void* stream) {
+  if (!sp || !sp->xP || !sp->yP || !table || !t) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (sp->M <= 0 || !(sp->dl > 0)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (N_s < 2 || N_s > FSAEMPC_PLAN_MAX_NS) return fail(FSAEMPC_ERR_ARG, "N_s must be 2 .. FSAEMPC_PLAN_MAX_NS");
+  if (!pos_finite(v_cap) || !pos_finite(grip) || !pos_finite(L)) return fail(FSAEMPC_ERR_ARG, "v_cap, grip and L must be finite and > 0");
+  if (grip > 1) return fail(FSAEMPC_ERR_ARG, "grip must be <= 1");
+  if (n_plans < 1) return fail(FSAEMPC_ERR_ARG, "n_plans must be >= 1");
+  if (par_values(par) && !par->per_instance && n_plans != 1) return fail(FSAEMPC_ERR_ARG, "a shared parameter block makes one plan");
+  PlanProfileParams P; P.dynamic = model == FSAEMPC_MODEL_DYNAMIC; P.n_plans = n_plans; P.N_s = N_s; P.ds = L / N_s; P.v_cap = v_cap; P.grip = grip;
+  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP; P.table = table; P.t = t;
+  hipError_t e = plan_profile_launch(P, par_values(par), par_stride(par), (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "plan_profile_launch");
+  return 0;
+}
+
+int fsaempc_plan_reference_batch_device(int model, const fsaempc_plan* plan, const double* s0, double dt, int N, int batch, double* x_ref,
+                                        void* stream) {
+  PlanRefParams P;
+  if (int rc = plan_check(plan, &P.plan)) return rc;
+  if (!s0 || !x_ref) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (N <= 0 || batch < 0 || !pos_finite(dt)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  P.nx = fsaempc_ltv_nx(model); P.N = N; P.batch = batch; P.dt = dt; P.s0 = s0; P.x_ref = x_ref;
+  hipError_t e = plan_reference_launch(P, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "plan_reference_launch");
+  return 0;
+}
+
+int fsaempc_cl_pre_plan_batch_device(int model, int N, double dt, double L, const fsaempc_spline* sp, const fsaempc_plan* plan,
+                                     const double* cart, const double* s_guess, int batch, double* x0, double* x_ref, int* finished,
+                                     void* stream) {
+  ClPrePlanParams P;
+  if (!sp || !sp->xP || !sp->yP || !cart || !s_guess || !x0 || !x_ref || !finished) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (int rc = plan_check(plan, &P.plan)) return rc;
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (N <= 0 || batch < 0 || !pos_finite(dt) || sp->M <= 0 || !(sp->dl > 0) || !(L > 0)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  P.nx = fsaempc_ltv_nx(model); P.N = N; P.batch = batch; P.dt = dt; P.L = L;
+  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP; P.cart = cart; P.s_guess = s_guess; P.x0 = x0; P.x_ref = x_ref; P.finished = finished;
+  hipError_t e = cl_pre_plan_launch(P, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "cl_pre_plan_launch");
   return 0;
 }
 

@@ -12,55 +12,9 @@
 #include <math.h>
 #include "plant.h"
 #include "mpc_params.h"
+#include "cl_frame.h"
 
 namespace {
-
-struct Spl { int M; double dl; const double* xP; const double* yP; };
-
-DEVINL double mmod(double a, double b) { return a - floor(a / b) * b; }
-DEVINL void seg_lookup(int M, double dl, double t, int& seg, double& tau) {
-  const double per = dl * (double)M;
-  double r = t - floor(t / per) * per;  // MATLAB mod()
-  if (r < 0) r += per;
-  if (r >= per) r -= per;
-  int i = 0;
-  if (r >= 0 && r < per) i = (int)floor(r / dl);   // a non-finite arc length (a car whose state blew up) must not index the table
-  if (i >= M) i = M - 1;
-  if (i < 0) i = 0;
-  seg = i; tau = r / dl - (double)i;
-}
-// value, first and second derivative of one Bezier spline at t (interpolate_spline{,_d,_dd}.m)
-DEVINL void spline3(const double* P, int M, double dl, double t, double& v, double& d, double& dd) {
-  int i; double u;
-  seg_lookup(M, dl, t, i, u);
-  const double p0 = P[i], p1 = P[i + M], p2 = P[i + 2 * M], p3 = P[i + 3 * M];
-  const double w = 1 - u;
-  v = p0 * (w * w * w) + 3 * p1 * (w * w) * u + 3 * p2 * w * (u * u) + p3 * (u * u * u);
-  d = (-3 * w * w * p0 + 3 * (3 * u * u - 4 * u + 1) * p1 + 3 * (2 * u - 3 * u * u) * p2 + 3 * u * u * p3) / dl;
-  dd = (6 * w * p0 + 6 * (3 * u - 2) * p1 + 6 * (1 - 3 * u) * p2 + 6 * u * p3) / (dl * dl);
-}
-
-DEVINL double closest_point(const Spl& sp, double x0, double y0, double s, double epsilon) {
-  double delta = epsilon * 2;
-  int guard = 0;
-  while (fabs(delta) > epsilon && guard++ < 1000) {   // bounded: every thread leaves the loop (the reference spins on NaN)
-    double X, Xd, Xdd, Y, Yd, Ydd;
-    spline3(sp.xP, sp.M, sp.dl, s, X, Xd, Xdd);
-    spline3(sp.yP, sp.M, sp.dl, s, Y, Yd, Ydd);
-    const double dist_d = 2 * (X - x0) * Xd + 2 * (Y - y0) * Yd;
-    const double dist_dd = 2 * (X - x0) * Xdd + 2 * Xd * Xd + 2 * (Y - y0) * Ydd + 2 * Yd * Yd;
-    delta = dist_d / dist_dd;
-    s = s - delta;
-  }
-  return s;
-}
-
-DEVINL double angdiff(double alpha, double beta) {   // MATLAB angdiff: beta - alpha wrapped to [-pi, pi]
-  const double d = beta - alpha;
-  double w = mmod(d + M_PI, 2 * M_PI) - M_PI;
-  if (w == -M_PI && d > 0) w = M_PI;
-  return w;
-}
 
 __global__ void cl_pre_kernel(ClPreParams P) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,0 +1,135 @@
+"""s-domain plans: the table the reference's loop is meant to track (main.m:20 makes it with
+dynamic_minimum_time_planner, main.m:115 resamples it with obtain_reference).  `Plan.profile` fills one on the device with the
+planner stand-in (a quasi-steady-state minimum-time speed profile on the centre line), `Plan.from_table` takes a user's own;
+`plan.reference` and ClosedLoop(reference=plan) resample it in time for a batch of cars."""
+import ctypes as C
+import math
+
+import numpy as np
+
+from ._lib import NPAR, PLAN_MAX_NS, ParamBlock, PlanTable, Spline, check, lib
+
+
+def check_profile_args(N_s, v_cap, grip, n_plans):
+    """Validates the arguments of Plan.profile (no library call)."""
+    if int(N_s) != N_s or not 2 <= N_s <= PLAN_MAX_NS:
+        raise ValueError("N_s must be an integer in 2 .. %d, got %r" % (PLAN_MAX_NS, N_s))
+    for name, v in (("v_cap", v_cap), ("grip", grip)):
+        if not (isinstance(v, (int, float, np.floating, np.integer)) and math.isfinite(v) and v > 0):
+            raise ValueError("%s must be finite and > 0, got %r" % (name, v))
+    if grip > 1:
+        raise ValueError("grip must be <= 1, got %r" % (grip,))
+    if int(n_plans) != n_plans or n_plans < 1:
+        raise ValueError("n_plans must be an integer >= 1, got %r" % (n_plans,))
+
+
+def check_table(table, t, ds):
+    """Validates the shapes of a user's plan (no library call); returns (P, N_s).  table: (N_s, 8), (8 N_s,) or (P, N_s, 8);
+    t: (N_s,) or (P, N_s)."""
+    ts, tt = tuple(table.shape), tuple(t.shape)
+    if len(tt) == 1 and len(ts) == 1 and ts[0] == 8 * tt[0]:
+        ts = (tt[0], 8)
+    if len(tt) == 1 and ts == (tt[0], 8):
+        P, N_s = 1, tt[0]
+    elif len(tt) == 2 and ts == (tt[0], tt[1], 8):
+        P, N_s = tt
+    else:
+        raise ValueError("plan shapes disagree: table %s (want (N_s, 8) or (P, N_s, 8)), t %s (want (N_s,) or (P, N_s))" % (tuple(table.shape), tt))
+    if N_s < 1 or P < 1:
+        raise ValueError("an empty plan")
+    if not (math.isfinite(ds) and ds > 0):
+        raise ValueError("ds must be finite and > 0, got %r" % (ds,))
+    return P, N_s
+
+
+class Plan:
+    """P plans of N_s cells on the device: table (P, N_s, 8) = n, mu, x_d, y_d, theta_d, delta, a, delta_d per cell, t (P, N_s)
+    traversal times, ds the cell length.  P = 1: shared by every car; otherwise car b drives on plan b."""
+
+    def __init__(self, table, t, ds):
+        self.table, self.t, self.ds = table, t, float(ds)
+        self.P, self.N_s = int(t.shape[0]), int(t.shape[1])
+        self.device = table.device
+        self.c = PlanTable(C.c_void_p(table.data_ptr()), C.c_void_p(t.data_ptr()), self.N_s, self.ds, 1 if self.P > 1 else 0)
+
+    def ref(self):
+        return C.byref(self.c)
+
+    @staticmethod
+    def profile(model, track, N_s=500, v_cap=20.0, grip=1.0, params=None, n_plans=1, device="cuda:0", stream=None):
+        """The planner stand-in on the device (fsaempc_plan_profile_batch_device).  params: None (the reference's constants),
+        (32,) one car, or (P, 32) one plan per block (n_plans is then P)."""
+        check_profile_args(N_s, v_cap, grip, n_plans)
+        if model not in (0, 1):
+            raise ValueError("unknown model %r" % (model,))
+        if params is not None:
+            if not hasattr(params, "shape"):
+                try:
+                    params = np.asarray(params, dtype=np.float64)
+                except (TypeError, ValueError):
+                    raise ValueError("params must be an array of %d or (n_plans, %d) numbers" % (NPAR, NPAR))
+            shape = tuple(params.shape)
+            if len(shape) == 2 and shape[1] == NPAR and shape[0] >= 1 and n_plans in (1, shape[0]):
+                n_plans = shape[0]
+            elif shape != (NPAR,) or n_plans != 1:
+                raise ValueError("params must be (%d,) with n_plans = 1 or (n_plans, %d), got %s with n_plans = %d" % (NPAR, NPAR, shape, n_plans))
+        import torch
+        dev = torch.device(device)
+        N_s, n_plans = int(N_s), int(n_plans)
+        xP, yP = track.device(dev)
+        sp = Spline(track.M, track.dl, C.c_void_p(xP.data_ptr()), C.c_void_p(yP.data_ptr()))
+        blocks = ParamBlock(params, n_plans, dev) if params is not None else None
+        table = torch.empty((n_plans, N_s, 8), dtype=torch.float64, device=dev)
+        t = torch.empty((n_plans, N_s), dtype=torch.float64, device=dev)
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+        rc = lib().fsaempc_plan_profile_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                     n_plans, N_s, C.c_double(v_cap), C.c_double(grip), C.c_void_p(table.data_ptr()),
+                                                     C.c_void_p(t.data_ptr()), st)
+        check(rc, "fsaempc_plan_profile_batch_device")
+        plan = Plan(table, t, track.L / N_s)
+        plan._blocks = blocks   # (read by a launch that may still be queued)
+        return plan
+
+    @staticmethod
+    def from_table(table, t, ds, device="cuda:0"):
+        """A user's own plan (numpy arrays or tensors), from the reference's planner for instance: table (N_s, 8), (8 N_s,) or
+        (P, N_s, 8), t (N_s,) or (P, N_s), ds the cell length."""
+        if not hasattr(table, "shape"):
+            table = np.asarray(table, dtype=np.float64)
+        if not hasattr(t, "shape"):
+            t = np.asarray(t, dtype=np.float64)
+        P, N_s = check_table(table, t, ds)
+        import torch
+        dev = torch.device(device)
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))).to(device=dev, dtype=torch.float64)
+        return Plan(up(table).reshape(P, N_s, 8).contiguous(), up(t).reshape(P, N_s).contiguous(), ds)
+
+    def lap_time(self):
+        """Sum of the traversal times of each plan, (P,) numpy."""
+        return self.t.sum(dim=1).cpu().numpy()
+
+    def check_batch(self, B):
+        if self.P not in (1, B):
+            raise ValueError("the plan holds %d tables: it serves a batch of %d (one per car) or any batch (one shared), not %d" % (self.P, self.P, B))
+
+    def check_device(self, device):
+        """The plan lives on one device; the loop that tracks it must run there (compared by name, before any device call)."""
+        want, have = str(device), str(self.device)
+        if want.split(":")[0] != have.split(":")[0] or (":" in want and ":" in have and want != have):
+            raise ValueError("the plan is on %s, the loop on %s" % (have, want))
+
+    def reference(self, model, s0, N, dt, stream=None):
+        """x_ref (B, N, nx) for cars at arc lengths s0 (B,), the layout LtvBatch.step takes (fsaempc_plan_reference_batch_device)."""
+        import torch
+        if not isinstance(s0, torch.Tensor):
+            s0 = torch.from_numpy(np.ascontiguousarray(np.atleast_1d(s0), dtype=np.float64))
+        s0 = s0.to(device=self.device, dtype=torch.float64).contiguous().reshape(-1)
+        B = s0.numel()
+        self.check_batch(B)
+        nx = 5 if model == 0 else 7
+        x_ref = torch.empty((B, int(N), nx), dtype=torch.float64, device=self.device)
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream)
+        rc = lib().fsaempc_plan_reference_batch_device(int(model), self.ref(), C.c_void_p(s0.data_ptr()), C.c_double(dt), int(N), B,
+                                                       C.c_void_p(x_ref.data_ptr()), st)
+        check(rc, "fsaempc_plan_reference_batch_device")
+        return x_ref

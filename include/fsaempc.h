@@ -494,6 +494,55 @@ int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_splin
 int fsaempc_cl_plant_batch_device_p(int model, int N, double dt, int batch, const fsaempc_ltv_params* par, double* cart, double* pid,
                                     const double* x_opt, const int* finished, const int* exitflag, double* u_last, void* stream);
 
+/* ---- s-domain plans: a speed-profile planner and the loop that tracks a plan -----------
+ * The reference's controller is meant to track a planned trajectory: main.m:20 computes an s-domain plan with
+ * dynamic_minimum_time_planner (IPOPT; not part of this build) and main.m:115 resamples it in time with obtain_reference.
+ * fsaempc_plan is that table as data; fsaempc_plan_profile_batch_device fills one with a stand-in: a quasi-steady-state
+ * minimum-time speed profile on the centre line (n = 0: no racing line, no lateral dynamics). */
+typedef struct {          /* a planner table as obtain_reference.m:7-15 reads it */
+  const double* table;    /* device; N_s * 8 per plan (n, mu, x_d, y_d, theta_d, delta, a, delta_d per cell) */
+  const double* t;        /* device; N_s per plan: per-cell traversal times (dynamic_minimum_time_planner.m:73-83) */
+  int N_s; double ds;     /* cells per lap, cell length = L / N_s; cell i sits at s_i = i * ds */
+  int per_instance;       /* 0: one plan shared by the batch; 1: one plan per instance, instance-major */
+} fsaempc_plan;
+#define FSAEMPC_PLAN_MAX_NS 4096   /* the planner keeps curvature and speed of a plan in LDS: 16 bytes per cell */
+
+/*
+ * Fills n_plans plans of N_s cells (table: n_plans * N_s * 8, t: n_plans * N_s; ds = L / N_s) for the track `sp` of length L.
+ * Per cell: k = kappa(s_i), K = max(|k|, 1e-12), vlat = min(v_cap, sqrt(A_lat / K)); from the first cell of least vlat one forward
+ * pass v_i = min(v_i, sqrt(v_p^2 + 2 a_x(v_p, K_p) ds)) over the lap and one backward pass with the successor in place of the
+ * predecessor.  Limits by model: kinematic A_lat = grip ALAT_MAX, a_x = grip U_ACC_MAX; dynamic A_lat = grip ELL_LAT,
+ * a_x = min(U_ACC_MAX, grip ELL_LONG X(min(v^2 K / A_lat, 1))), X the first-quadrant boundary of the 12-gon of the tyre rows
+ * (dynamic_tyre_linearise_constraints.m:18-23).  Table: n = mu = y_d = 0, x_d = v, theta_d = v k, delta = atan((LF + LR) k),
+ * a = (v_next^2 - v^2) / (2 ds), t = ds / v, delta_d = (delta_next - delta) / t, indices cyclic.
+ * par: NULL (defaults), one shared block (n_plans must be 1) or n_plans blocks (per_instance).  A block that cannot describe a car
+ * gives that plan NaN in every entry; the other plans are unaffected.
+ * FSAEMPC_ERR_ARG before any launch: N_s < 2 or > FSAEMPC_PLAN_MAX_NS; v_cap, grip or L not finite or <= 0; grip > 1; n_plans < 1;
+ * a shared block with n_plans > 1.
+ */
+int fsaempc_plan_profile_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par,
+                                      int n_plans, int N_s, double v_cap, double grip,
+                                      double* table, double* t, void* stream);
+
+/*
+ * obtain_reference (util/obtain_reference.m:1-48, main.m:115) on a plan, batched over s0, in the state layout of the model:
+ * x_ref is nx x N column-major per instance; dynamic: the seven rows of obtain_reference.m:41-47; kinematic: rows
+ * [s, n, mu, hypot(x_d, y_d), delta] (main.m:95's rule for x0).  The walk over the cells advances at most N_s cells per horizon
+ * step, and it ends at the first cell it meets whose time is zero, negative or not finite: from that horizon step on the car's rows
+ * are NaN (so is every row after a step that would circle the lap).  Never a hang, never a read outside the table.
+ * A non-finite s0 is walked from 0 (finite placeholder rows).
+ */
+int fsaempc_plan_reference_batch_device(int model, const fsaempc_plan* plan, const double* s0, double dt, int N, int batch,
+                                        double* x_ref, void* stream);   /* x_ref: nx x N per instance, model layout */
+
+/*
+ * fsaempc_cl_pre_batch_device with the live ramp of main.m:107-114 replaced by main.m:115: same frame transform, x0 assembly, lap
+ * check and out-of-race rule, then x_ref from the plan at the car's own s (one kernel).  plan->per_instance: one plan per car.
+ */
+int fsaempc_cl_pre_plan_batch_device(int model, int N, double dt, double L, const fsaempc_spline* sp, const fsaempc_plan* plan,
+                                     const double* cart, const double* s_guess, int batch,
+                                     double* x0, double* x_ref, int* finished, void* stream);
+
 /* ---- move blocking: held inputs --------------------------------------------------
  * The input is held constant over groups of consecutive horizon steps: block j covers steps start_j .. start_j + len_j - 1 and
  * u_k = v_block(k).  The QP's variables are [v_1 .. v_M; slacks], nV_b = 2 M + ns; its rows stay those of the unblocked problem

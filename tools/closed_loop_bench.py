@@ -3,7 +3,8 @@
 one batch of B LTV-MPC QPs (frame transform + reference -> linearise/condense/solve -> PID + plant), all on the device with
 no per-step read-back (fsae_mpc_amd.monte_carlo).  Prints one JSON line: QP solves/s over the QPs of the cars still
 driving, the exit-flag tally the way main.m:209,222 reports it ("abnormal exits %"), iterations, progress.
-usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40]"""
+--plan: the cars track a plan of the planner stand-in (fsaempc.Plan.profile) instead of the live ramp to 20 m/s.
+usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--plan [--grip G] [--cells N_s]]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -21,13 +22,40 @@ def main():
     ap.add_argument("--max-iter", type=int, default=100, help="interior-point iteration limit (bounds the batch tail)")
     ap.add_argument("--no-launch-hint", action="store_true", help="do not hand the previous iteration counts to the solve as its launch-order estimate (A/B)")
     ap.add_argument("--warm", action="store_true", help="start every solve from the previous plan shifted by one stage (ClosedLoop(warm_start=True))")
+    ap.add_argument("--plan", action="store_true", help="track a speed-profile plan (Plan.profile) instead of the live ramp")
+    ap.add_argument("--grip", type=float, default=1.0, help="with --plan: share of the lateral / longitudinal limits the plan uses, (0, 1]")
+    ap.add_argument("--cells", type=int, default=500, help="with --plan: cells per lap (N_s)")
     a = ap.parse_args()
     model = fm.KINEMATIC if a.model == "kinematic" else fm.DYNAMIC
     tr = fm.Track.load("fss2019")
-    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm)          # warm-up (allocations, code load)
+    plan = fm.Plan.profile(model, tr, N_s=a.cells, grip=a.grip) if a.plan else None
+    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan)          # warm-up (allocations, code load)
+    n_max = float(fm.default_params(model)[fm.PARAM_INDEX["N_MAX"]])
+    opts = fm.default_opts(max_iter=a.max_iter)
     t0 = time.perf_counter()
-    cl, fl, it, ac = fm.monte_carlo(model, a.horizon, tr, a.batch, a.steps, a.seed, options=fm.default_opts(max_iter=a.max_iter), warm_start=a.warm, launch_hint=not a.no_launch_hint)
+    # the loop of fm.monte_carlo with two more counts kept on the device: steps off the track (|n| > N_MAX) and the last arc length of
+    # every car while it drives
+    cart0, s_init = fm.monte_carlo_carts(tr, a.batch, a.seed)
+    cl = fm.ClosedLoop(model, a.horizon, 0.05, tr, cart0, options=opts, warm_start=a.warm, launch_hint=not a.no_launch_hint, reference=plan)
+    cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]
+    cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]
+    fl_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
+    it_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
+    ac_d = torch.zeros((a.steps, a.batch), dtype=torch.bool, device=cl.device)
+    off = torch.zeros((), dtype=torch.int64, device=cl.device)
+    s_first = s_last = None
+    for t in range(a.steps):
+        out = cl.step()
+        drv = cl.finished == 0
+        fl_d[t] = out["exitflag"]; it_d[t] = out["iter"]; ac_d[t] = drv
+        if s_first is None:
+            s_first = cl.x0[:, 0].clone(); s_last = cl.x0[:, 0].clone()
+        off += ((cl.x0[:, 1].abs() > n_max) & drv).sum()
+        s_last = torch.where(drv, cl.x0[:, 0], s_last)
+    torch.cuda.synchronize(cl.device)
+    fl, it, ac = fl_d.cpu().numpy(), it_d.cpu().numpy(), ac_d.cpu().numpy()
     dt_wall = time.perf_counter() - t0
+    dist = (s_last - s_first).cpu().numpy()
     n_act = int(ac.sum())
     hist = {int(k_): int(c_) for k_, c_ in zip(*np.unique(fl[ac], return_counts=True))}
     solved = int(((fl == 0) & ac).sum())
@@ -52,6 +80,9 @@ def main():
                    "mean_ipm_iterations": float(it[ac].mean()) if n_act else 0.0,
                    "cars_past_end_of_track_parameter": int((cl.finished == 1).sum().item()), "cars_lost": int((cl.finished == 2).sum().item()),
                    "mean_speed_end": float(cl.cart[:, 3].mean().item()),
+                   "reference": ("plan: speed profile, N_s = %d, grip %g, lap %.2f s" % (a.cells, a.grip, float(plan.lap_time()[0]))) if a.plan else "live ramp to 20 m/s",
+                   "steps_off_track_abs_n_gt_N_MAX": int(off.item()), "mean_distance_covered_m": float(np.nanmean(dist)),
+                   "total_distance_covered_m": float(np.nansum(dist)),
                    "median_abs_lateral_offset_end": float(np.nanmedian(np.abs(x0[:, 1]))), "seed": a.seed, "max_iter": a.max_iter, "warm_start": bool(a.warm), "launch_hint": not a.no_launch_hint}}))
 
 
