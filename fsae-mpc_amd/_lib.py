@@ -25,6 +25,8 @@ EXPORTS = [
     "fsaempc_ltv_blocked_nV", "fsaempc_ltv_build_qp_batch_device_b", "fsaempc_ltv_workspace_bytes_b", "fsaempc_ltv_step_batch_device_b",
     "fsaempc_qp_workspace_bytes_s", "fsaempc_qp_solve_batch_device_s", "fsaempc_qp_layout",
     "fsaempc_plan_profile_batch_device", "fsaempc_plan_reference_batch_device", "fsaempc_cl_pre_plan_batch_device",
+    "fsaempc_raceline_build_qp_device", "fsaempc_plan_line_profile_batch_device", "fsaempc_plan_raceline_workspace_bytes",
+    "fsaempc_plan_raceline_batch_device",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -75,6 +77,9 @@ class LtvBlocking(C.Structure):
 
 
 PLAN_MAX_NS = 4096   # FSAEMPC_PLAN_MAX_NS
+LINE_MAX_NS = 2048   # FSAEMPC_LINE_MAX_NS
+LINE_MIN_NC = 8      # FSAEMPC_LINE_MIN_NC
+MAX_NV = 196         # FSAEMPC_MAX_NV
 
 
 class PlanTable(C.Structure):   # fsaempc_plan
@@ -202,6 +207,13 @@ def lib():
         L.fsaempc_plan_reference_batch_device.argtypes = [C.c_int, C.POINTER(PlanTable), vp, C.c_double, C.c_int, C.c_int, vp, vp]
         L.fsaempc_cl_pre_plan_batch_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(Spline), C.POINTER(PlanTable),
                                                        vp, vp, C.c_int, vp, vp, vp, vp]
+        L.fsaempc_raceline_build_qp_device.argtypes = [C.POINTER(Spline), C.c_double, C.c_int, C.c_int, vp, vp, vp]
+        L.fsaempc_plan_line_profile_batch_device.argtypes = [C.c_int, C.POINTER(Spline), C.c_double, C.POINTER(LtvParams), C.c_int, C.c_int, C.c_int,
+                                                             vp, C.c_int, C.c_double, C.c_double, vp, vp, vp]
+        L.fsaempc_plan_raceline_workspace_bytes.restype = C.c_longlong
+        L.fsaempc_plan_raceline_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.fsaempc_plan_raceline_batch_device.argtypes = [C.c_int, C.POINTER(Spline), C.c_double, C.POINTER(LtvParams), C.c_int, C.c_int, C.c_int,
+                                                         C.c_double, C.c_double, C.c_double, C.POINTER(QpOpts), vp, vp, vp, vp, vp, ll, vp]
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p
         L.fsaempc_track_from_csv.argtypes = [C.c_char_p, C.c_int, C.POINTER(TrackTable)]

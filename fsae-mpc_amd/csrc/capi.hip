@@ -16,6 +16,7 @@
 #include "reference.h"
 #include "plant.h"
 #include "planner.h"
+#include "raceline.h"
 #include "sqp.h"
 #include "qp_sens.h"
 
@@ -993,6 +994,108 @@ int fsaempc_cl_pre_plan_batch_device(int model, int N, double dt, double L, cons
   P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP; P.cart = cart; P.s_guess = s_guess; P.x0 = x0; P.x_ref = x_ref; P.finished = finished;
   hipError_t e = cl_pre_plan_launch(P, (hipStream_t)stream);
   if (e != hipSuccess) return hipfail(e, "cl_pre_plan_launch");
+  return 0;
+}
+
+/* ---- minimum-curvature racing line ---- */
+static int line_check(const fsaempc_spline* sp, double L, int N_s, int N_c) {
+  if (!sp || !sp->xP || !sp->yP) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (sp->M <= 0 || !(sp->dl > 0)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (!pos_finite(L)) return fail(FSAEMPC_ERR_ARG, "L must be finite and > 0");
+  if (N_c < FSAEMPC_LINE_MIN_NC || N_c > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_ARG, "N_c must be FSAEMPC_LINE_MIN_NC .. FSAEMPC_MAX_NV");
+  if (N_s < 2 * N_c || N_s > FSAEMPC_LINE_MAX_NS) return fail(FSAEMPC_ERR_ARG, "N_s must be 2 N_c .. FSAEMPC_LINE_MAX_NS");
+  return 0;
+}
+static int line_profile_check(int model, const fsaempc_ltv_params* par, int n_plans, double v_cap, double grip) {
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (!pos_finite(v_cap) || !pos_finite(grip)) return fail(FSAEMPC_ERR_ARG, "v_cap and grip must be finite and > 0");
+  if (grip > 1) return fail(FSAEMPC_ERR_ARG, "grip must be <= 1");
+  if (n_plans < 1) return fail(FSAEMPC_ERR_ARG, "n_plans must be >= 1");
+  if (par_values(par) && !par->per_instance && n_plans != 1) return fail(FSAEMPC_ERR_ARG, "a shared parameter block makes one plan");
+  return 0;
+}
+static RacelineQpParams line_qp_params(const fsaempc_spline* sp, double L, int N_s, int N_c, double* H, double* g) {
+  RacelineQpParams Q; Q.N_s = N_s; Q.N_c = N_c; Q.ds = L / N_s; Q.spM = sp->M; Q.spdl = sp->dl; Q.xP = sp->xP; Q.yP = sp->yP; Q.H = H; Q.g = g;
+  return Q;
+}
+static PlanLineParams line_profile_params(int model, const fsaempc_spline* sp, double L, int n_plans, int N_s, int N_c, double v_cap, double grip,
+                                          double* table, double* t) {
+  PlanLineParams P; memset(&P, 0, sizeof(P));
+  P.dynamic = model == FSAEMPC_MODEL_DYNAMIC; P.n_plans = n_plans; P.N_s = N_s; P.N_c = N_c; P.ds = L / N_s; P.h = L / N_c; P.v_cap = v_cap; P.grip = grip;
+  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP; P.table = table; P.t = t;
+  return P;
+}
+
+int fsaempc_raceline_build_qp_device(const fsaempc_spline* sp, double L, int N_s, int N_c, double* H, double* g, void* stream) {
+  if (!H || !g) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (int rc = line_check(sp, L, N_s, N_c)) return rc;
+  hipError_t e = raceline_qp_launch(line_qp_params(sp, L, N_s, N_c, H, g), (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "raceline_qp_launch");
+  return 0;
+}
+
+int fsaempc_plan_line_profile_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, int n_plans, int N_s,
+                                           int N_c, const double* line, int line_per_plan, double v_cap, double grip, double* table, double* t,
+                                           void* stream) {
+  if (!line || !table || !t) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (int rc = line_check(sp, L, N_s, N_c)) return rc;
+  if (int rc = line_profile_check(model, par, n_plans, v_cap, grip)) return rc;
+  PlanLineParams P = line_profile_params(model, sp, L, n_plans, N_s, N_c, v_cap, grip, table, t);
+  P.line = line; P.line_stride = line_per_plan ? N_c : 0;
+  hipError_t e = plan_line_profile_launch(P, par_values(par), par_stride(par), (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "plan_line_profile_launch");
+  return 0;
+}
+
+// workspace of fsaempc_plan_raceline_batch_device: H | g, lb, ub (n_plans x N_c each) | fval | iter | the solver's own
+struct LineCarve { size_t H, g, lb, ub, fval, iter, qp, total; long long qp_bytes; };
+static int line_carve(int n_plans, int N_c, LineCarve* c) {
+  if (n_plans < 1 || N_c < FSAEMPC_LINE_MIN_NC || N_c > FSAEMPC_MAX_NV) return FSAEMPC_ERR_ARG;
+  const fsaempc_qp_desc d = {N_c, 0, n_plans, 1};
+  c->qp_bytes = fsaempc_qp_workspace_bytes_s(&d, 0);
+  if (c->qp_bytes < 0) return (int)c->qp_bytes;
+  const size_t vec = align64((size_t)n_plans * N_c * sizeof(double));
+  size_t off = 0;
+  c->H = off; off += align64((size_t)N_c * N_c * sizeof(double));
+  c->g = off; off += vec;
+  c->lb = off; off += vec;
+  c->ub = off; off += vec;
+  c->fval = off; off += align64((size_t)n_plans * sizeof(double));
+  c->iter = off; off += align64((size_t)n_plans * sizeof(int));
+  c->qp = off; off += (size_t)c->qp_bytes;
+  c->total = off;
+  return 0;
+}
+long long fsaempc_plan_raceline_workspace_bytes(int n_plans, int N_c) {
+  LineCarve c;
+  if (int rc = line_carve(n_plans, N_c, &c)) return rc;
+  return (long long)c.total;
+}
+
+int fsaempc_plan_raceline_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, int n_plans, int N_s,
+                                       int N_c, double margin, double v_cap, double grip, const fsaempc_qp_opts* opts, double* line, int* flag,
+                                       double* table, double* t, void* workspace, long long workspace_bytes, void* stream) {
+  if (!line || !flag || !table || !t || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (int rc = line_check(sp, L, N_s, N_c)) return rc;
+  if (int rc = line_profile_check(model, par, n_plans, v_cap, grip)) return rc;
+  if (!(margin >= 0 && margin < INFINITY)) return fail(FSAEMPC_ERR_ARG, "margin must be finite and >= 0");
+  LineCarve c;
+  if (int rc = line_carve(n_plans, N_c, &c)) return fail(rc, "bad dimensions");
+  if ((long long)c.total > workspace_bytes) return fail(FSAEMPC_ERR_WORKSPACE, "workspace too small");
+  char* ws = (char*)workspace;
+  double *H = (double*)(ws + c.H), *g = (double*)(ws + c.g), *lb = (double*)(ws + c.lb), *ub = (double*)(ws + c.ub);
+  hipError_t e = raceline_qp_launch(line_qp_params(sp, L, N_s, N_c, H, g), (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "raceline_qp_launch");
+  RacelineBoundsParams B; B.n_plans = n_plans; B.N_c = N_c; B.margin = margin; B.g = g; B.lb = lb; B.ub = ub;
+  e = raceline_bounds_launch(B, par_values(par), par_stride(par), (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "raceline_bounds_launch");
+  const fsaempc_qp_desc d = {N_c, 0, n_plans, 1};
+  if (int rc = fsaempc_qp_solve_batch_device_s(&d, 0, H, g, nullptr, lb, ub, nullptr, nullptr, opts, line, (double*)(ws + c.fval), flag,
+                                               (int*)(ws + c.iter), nullptr, nullptr, ws + c.qp, c.qp_bytes, stream)) return rc;
+  PlanLineParams P = line_profile_params(model, sp, L, n_plans, N_s, N_c, v_cap, grip, table, t);
+  P.line = line; P.line_stride = N_c; P.flag = flag; P.line_out = line; P.check_width = 1; P.margin = margin;
+  e = plan_line_profile_launch(P, par_values(par), par_stride(par), (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "plan_line_profile_launch");
   return 0;
 }
 

@@ -1,13 +1,14 @@
 """s-domain plans: the table the reference's loop is meant to track (main.m:20 makes it with
 dynamic_minimum_time_planner, main.m:115 resamples it with obtain_reference).  `Plan.profile` fills one on the device with the
 planner stand-in (a quasi-steady-state minimum-time speed profile on the centre line), `Plan.from_table` takes a user's own;
-`plan.reference` and ClosedLoop(reference=plan) resample it in time for a batch of cars."""
+`plan.reference` and ClosedLoop(reference=plan) resample it in time for a batch of cars.  `Plan.raceline` chooses a minimum-curvature
+line first and makes the profile on it; `Plan.profile(line=c)` takes a user's own control points."""
 import ctypes as C
 import math
 
 import numpy as np
 
-from ._lib import NPAR, PLAN_MAX_NS, ParamBlock, PlanTable, Spline, check, lib
+from ._lib import LINE_MAX_NS, LINE_MIN_NC, MAX_NV, NPAR, PLAN_MAX_NS, ParamBlock, PlanTable, Spline, check, default_opts, lib
 
 
 def check_profile_args(N_s, v_cap, grip, n_plans):
@@ -21,6 +22,51 @@ def check_profile_args(N_s, v_cap, grip, n_plans):
         raise ValueError("grip must be <= 1, got %r" % (grip,))
     if int(n_plans) != n_plans or n_plans < 1:
         raise ValueError("n_plans must be an integer >= 1, got %r" % (n_plans,))
+
+
+def check_line_args(N_s, N_c, margin=None):
+    """Validates the cell and control-point counts of a line, and the margin of Plan.raceline (no library call)."""
+    if int(N_c) != N_c or not LINE_MIN_NC <= N_c <= MAX_NV:
+        raise ValueError("N_c must be an integer in %d .. %d, got %r" % (LINE_MIN_NC, MAX_NV, N_c))
+    if int(N_s) != N_s or not 2 * N_c <= N_s <= LINE_MAX_NS:
+        raise ValueError("N_s must be an integer in 2 N_c = %d .. %d, got %r" % (2 * N_c, LINE_MAX_NS, N_s))
+    if margin is not None and not (isinstance(margin, (int, float, np.floating, np.integer)) and math.isfinite(margin) and margin >= 0):
+        raise ValueError("margin must be finite and >= 0, got %r" % (margin,))
+
+
+def check_params(params, n_plans):
+    """Validates the parameter blocks of a planner call against n_plans (no library call); returns (params, n_plans)."""
+    if params is None:
+        return None, n_plans
+    if not hasattr(params, "shape"):
+        try:
+            params = np.asarray(params, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("params must be an array of %d or (n_plans, %d) numbers" % (NPAR, NPAR))
+    shape = tuple(params.shape)
+    if len(shape) == 2 and shape[1] == NPAR and shape[0] >= 1 and n_plans in (1, shape[0]):
+        n_plans = shape[0]
+    elif shape != (NPAR,) or n_plans != 1:
+        raise ValueError("params must be (%d,) with n_plans = 1 or (n_plans, %d), got %s with n_plans = %d" % (NPAR, NPAR, shape, n_plans))
+    return params, n_plans
+
+
+def check_line(line, N_s, n_plans):
+    """Validates a user's control points, (N_c,) or (P, N_c), against N_s and n_plans (no library call); returns (line, N_c, n_plans)."""
+    if not hasattr(line, "shape"):
+        try:
+            line = np.asarray(line, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("line must be an array of (N_c,) or (n_plans, N_c) numbers")
+    shape = tuple(line.shape)
+    if len(shape) not in (1, 2) or (len(shape) == 2 and shape[0] < 1):
+        raise ValueError("line must be (N_c,) or (n_plans, N_c), got %s" % (shape,))
+    check_line_args(N_s, shape[-1])
+    if len(shape) == 2 and shape[0] != n_plans:
+        if n_plans != 1:
+            raise ValueError("line holds %d sets of control points, n_plans = %d" % (shape[0], n_plans))
+        n_plans = shape[0]
+    return line, shape[-1], n_plans
 
 
 def check_table(table, t, ds):
@@ -51,28 +97,27 @@ class Plan:
         self.P, self.N_s = int(t.shape[0]), int(t.shape[1])
         self.device = table.device
         self.c = PlanTable(C.c_void_p(table.data_ptr()), C.c_void_p(t.data_ptr()), self.N_s, self.ds, 1 if self.P > 1 else 0)
+        self.line, self.line_flag = None, None   # control points of the lateral offset and the flags of their QPs (Plan.raceline)
 
     def ref(self):
         return C.byref(self.c)
 
     @staticmethod
-    def profile(model, track, N_s=500, v_cap=20.0, grip=1.0, params=None, n_plans=1, device="cuda:0", stream=None):
+    def profile(model, track, N_s=500, v_cap=20.0, grip=1.0, params=None, n_plans=1, device="cuda:0", stream=None, line=None):
         """The planner stand-in on the device (fsaempc_plan_profile_batch_device).  params: None (the reference's constants),
-        (32,) one car, or (P, 32) one plan per block (n_plans is then P)."""
+        (32,) one car, or (P, 32) one plan per block (n_plans is then P).  line: None (the centre line) or the control points of a
+        lateral offset, (N_c,) shared by the plans or (P, N_c) (fsaempc_plan_line_profile_batch_device)."""
         check_profile_args(N_s, v_cap, grip, n_plans)
         if model not in (0, 1):
             raise ValueError("unknown model %r" % (model,))
-        if params is not None:
-            if not hasattr(params, "shape"):
-                try:
-                    params = np.asarray(params, dtype=np.float64)
-                except (TypeError, ValueError):
-                    raise ValueError("params must be an array of %d or (n_plans, %d) numbers" % (NPAR, NPAR))
-            shape = tuple(params.shape)
-            if len(shape) == 2 and shape[1] == NPAR and shape[0] >= 1 and n_plans in (1, shape[0]):
-                n_plans = shape[0]
-            elif shape != (NPAR,) or n_plans != 1:
-                raise ValueError("params must be (%d,) with n_plans = 1 or (n_plans, %d), got %s with n_plans = %d" % (NPAR, NPAR, shape, n_plans))
+        params, n_plans = check_params(params, n_plans)
+        N_c = 0
+        if line is not None:
+            line, N_c, n_line = check_line(line, N_s, n_plans)
+            if n_line != n_plans:
+                if params is not None and len(tuple(params.shape)) == 1:
+                    raise ValueError("a shared parameter block makes one plan, line holds %d" % n_line)
+                n_plans = n_line
         import torch
         dev = torch.device(device)
         N_s, n_plans = int(N_s), int(n_plans)
@@ -82,12 +127,61 @@ class Plan:
         table = torch.empty((n_plans, N_s, 8), dtype=torch.float64, device=dev)
         t = torch.empty((n_plans, N_s), dtype=torch.float64, device=dev)
         st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
-        rc = lib().fsaempc_plan_profile_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
-                                                     n_plans, N_s, C.c_double(v_cap), C.c_double(grip), C.c_void_p(table.data_ptr()),
-                                                     C.c_void_p(t.data_ptr()), st)
-        check(rc, "fsaempc_plan_profile_batch_device")
+        if line is None:
+            rc = lib().fsaempc_plan_profile_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                         n_plans, N_s, C.c_double(v_cap), C.c_double(grip), C.c_void_p(table.data_ptr()),
+                                                         C.c_void_p(t.data_ptr()), st)
+            check(rc, "fsaempc_plan_profile_batch_device")
+        else:
+            c = (line if isinstance(line, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(line, dtype=np.float64)))
+            c = c.to(device=dev, dtype=torch.float64).contiguous()
+            rc = lib().fsaempc_plan_line_profile_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                              n_plans, N_s, int(N_c), C.c_void_p(c.data_ptr()), 1 if c.dim() == 2 else 0,
+                                                              C.c_double(v_cap), C.c_double(grip), C.c_void_p(table.data_ptr()),
+                                                              C.c_void_p(t.data_ptr()), st)
+            check(rc, "fsaempc_plan_line_profile_batch_device")
         plan = Plan(table, t, track.L / N_s)
         plan._blocks = blocks   # (read by a launch that may still be queued)
+        if line is not None:
+            plan.line = c.reshape(-1, int(N_c))
+        return plan
+
+    @staticmethod
+    def raceline(model, track, N_s=500, N_c=100, margin=0.25, v_cap=20.0, grip=1.0, params=None, n_plans=1, options=None, device="cuda:0",
+                 stream=None):
+        """Racing-line plans (fsaempc_plan_raceline_batch_device): a minimum-curvature line within +-(N_MAX - margin) of
+        the centre line (N_MAX: the block's, default 0.75) as N_c control points of a periodic cubic B-spline, then the profile of
+        Plan.profile on it.  Returns a Plan with .line (P, N_c) control points and .line_flag (P,) exit flags of the line QPs; a plan
+        whose flag is not 0 is the centre-line plan."""
+        check_profile_args(N_s, v_cap, grip, n_plans)
+        check_line_args(N_s, N_c, margin)
+        if model not in (0, 1):
+            raise ValueError("unknown model %r" % (model,))
+        params, n_plans = check_params(params, n_plans)
+        import torch
+        dev = torch.device(device)
+        N_s, N_c, n_plans = int(N_s), int(N_c), int(n_plans)
+        xP, yP = track.device(dev)
+        sp = Spline(track.M, track.dl, C.c_void_p(xP.data_ptr()), C.c_void_p(yP.data_ptr()))
+        blocks = ParamBlock(params, n_plans, dev) if params is not None else None
+        need = lib().fsaempc_plan_raceline_workspace_bytes(n_plans, N_c)
+        if need < 0:
+            check(int(need), "fsaempc_plan_raceline_workspace_bytes")
+        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+        line = torch.empty((n_plans, N_c), dtype=torch.float64, device=dev)
+        flag = torch.empty(n_plans, dtype=torch.int32, device=dev)
+        table = torch.empty((n_plans, N_s, 8), dtype=torch.float64, device=dev)
+        t = torch.empty((n_plans, N_s), dtype=torch.float64, device=dev)
+        opts = options if options is not None else default_opts()
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda a: C.c_void_p(a.data_ptr())
+        rc = lib().fsaempc_plan_raceline_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                      n_plans, N_s, N_c, C.c_double(margin), C.c_double(v_cap), C.c_double(grip), C.byref(opts),
+                                                      p(line), p(flag), p(table), p(t), p(ws), C.c_longlong(ws.numel() * 8), st)
+        check(rc, "fsaempc_plan_raceline_batch_device")
+        plan = Plan(table, t, track.L / N_s)
+        plan._blocks, plan._ws = blocks, ws   # (read by launches that may still be queued)
+        plan.line, plan.line_flag = line, flag
         return plan
 
     @staticmethod
@@ -133,3 +227,19 @@ class Plan:
                                                        C.c_void_p(x_ref.data_ptr()), st)
         check(rc, "fsaempc_plan_reference_batch_device")
         return x_ref
+
+
+def raceline_qp(track, N_s, N_c, device="cuda:0", stream=None):
+    """H (N_c, N_c) and g (N_c,) of the line QP of (track, N_s, N_c) on the device (fsaempc_raceline_build_qp_device)."""
+    check_line_args(N_s, N_c)
+    import torch
+    dev = torch.device(device)
+    N_s, N_c = int(N_s), int(N_c)
+    xP, yP = track.device(dev)
+    sp = Spline(track.M, track.dl, C.c_void_p(xP.data_ptr()), C.c_void_p(yP.data_ptr()))
+    H = torch.empty((N_c, N_c), dtype=torch.float64, device=dev)
+    g = torch.empty(N_c, dtype=torch.float64, device=dev)
+    st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+    rc = lib().fsaempc_raceline_build_qp_device(C.byref(sp), C.c_double(track.L), N_s, N_c, C.c_void_p(H.data_ptr()), C.c_void_p(g.data_ptr()), st)
+    check(rc, "fsaempc_raceline_build_qp_device")
+    return H, g

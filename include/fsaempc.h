@@ -498,7 +498,8 @@ int fsaempc_cl_plant_batch_device_p(int model, int N, double dt, int batch, cons
  * The reference's controller is meant to track a planned trajectory: main.m:20 computes an s-domain plan with
  * dynamic_minimum_time_planner (IPOPT; not part of this build) and main.m:115 resamples it in time with obtain_reference.
  * fsaempc_plan is that table as data; fsaempc_plan_profile_batch_device fills one with a stand-in: a quasi-steady-state
- * minimum-time speed profile on the centre line (n = 0: no racing line, no lateral dynamics). */
+ * minimum-time speed profile on the centre line (n = 0, no lateral dynamics); fsaempc_plan_raceline_batch_device further down
+ * chooses a line first. */
 typedef struct {          /* a planner table as obtain_reference.m:7-15 reads it */
   const double* table;    /* device; N_s * 8 per plan (n, mu, x_d, y_d, theta_d, delta, a, delta_d per cell) */
   const double* t;        /* device; N_s per plan: per-cell traversal times (dynamic_minimum_time_planner.m:73-83) */
@@ -542,6 +543,54 @@ int fsaempc_plan_reference_batch_device(int model, const fsaempc_plan* plan, con
 int fsaempc_cl_pre_plan_batch_device(int model, int N, double dt, double L, const fsaempc_spline* sp, const fsaempc_plan* plan,
                                      const double* cart, const double* s_guess, int batch,
                                      double* x0, double* x_ref, int* finished, void* stream);
+
+/* ---- a minimum-curvature racing line for the s-domain plans ----------------------
+ * The lateral offset n(s) of the line from the centre line is a uniform periodic cubic B-spline with N_c control points c (knot
+ * spacing L / N_c), sampled at the N_s cells of a plan: cell i, q = i N_c / N_s, j = floor(q), u = q - j, weights
+ * [(1-u)^3, 3u^3 - 6u^2 + 4, -3u^3 + 3u^2 + 3u + 1, u^3] / 6 on c_{j-1} .. c_{j+2} (cyclic).  The line minimises the summed squared
+ * second difference of its points p_i = c_i + n_i nu_i (centre point, unit left normal: curvilinear_to_cartesian.m:16-26) over c
+ * with |c_j| <= w: the weights are non-negative and sum to one, so the whole line stays within +-w.  That is the bounds-only QP
+ * min 1/2 c'Hc + g'c, H = 2 ds G'G, g = 2 ds G'd (G_i c + d_i: the second difference at cell i over ds^2), solved by
+ * fsaempc_qp_solve_batch_device_s (nC = 0, n_slack = 0, one H for the batch).  Minimum curvature, not minimum time. */
+#define FSAEMPC_LINE_MAX_NS 2048   /* the profile on a line keeps curvature, speed and length of a cell in LDS: 24 bytes per cell */
+#define FSAEMPC_LINE_MIN_NC 8      /* N_c: FSAEMPC_LINE_MIN_NC .. FSAEMPC_MAX_NV, and N_s >= 2 N_c (H is then cyclic-banded) */
+
+/*
+ * H (N_c * N_c, dense, exactly symmetric, zero beyond cyclic distance 4) and g (N_c) of the line QP of (track, N_s, N_c).
+ * Every entry is a sum over cells in ascending order: the same bits on every call.
+ * FSAEMPC_ERR_ARG before any launch: N_c < FSAEMPC_LINE_MIN_NC or > FSAEMPC_MAX_NV, N_s < 2 N_c or > FSAEMPC_LINE_MAX_NS, L not
+ * finite or <= 0, a null pointer.
+ */
+int fsaempc_raceline_build_qp_device(const fsaempc_spline* sp, double L, int N_s, int N_c, double* H, double* g, void* stream);
+
+/*
+ * fsaempc_plan_profile_batch_device on a line: control points `line` (N_c, shared by the plans, or n_plans * N_c with
+ * line_per_plan != 0).  Per cell: n and n' = dn/ds from the basis, kappa of the centre line, a = 1 - n kappa, r = sqrt(a^2 + n'^2),
+ * mu = atan(n' / a), length dl = ds r, curvature k = (kappa + (mu_next - mu_prev) / (2 ds)) / r; then the recurrences of
+ * fsaempc_plan_profile_batch_device with k for the curvature, the predecessor's dl in the forward and the cell's own dl in the
+ * backward pass.  Table: n, mu, x_d = v, y_d = 0, theta_d = v k, delta = atan((LF + LR) k), a = (v_next^2 - v^2) / (2 dl),
+ * delta_d = (delta_next - delta) / t, t = dl / v.  All-zero control points give the bits of fsaempc_plan_profile_batch_device.
+ * A plan is NaN in every entry if its parameter block cannot describe a car or if a < 0.1 in any cell (the line comes too close
+ * to the centre of a corner; NaN control points); the other plans are unaffected.
+ * FSAEMPC_ERR_ARG before any launch: the cases of fsaempc_plan_profile_batch_device and of fsaempc_raceline_build_qp_device.
+ */
+int fsaempc_plan_line_profile_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par,
+                                           int n_plans, int N_s, int N_c, const double* line, int line_per_plan,
+                                           double v_cap, double grip, double* table, double* t, void* stream);
+
+/*
+ * Racing-line plans in one call, asynchronous on `stream`: the line QP, its solve with the bounds of each plan
+ * (w_p = N_MAX_p - margin; N_MAX_p: FSAEMPC_P_N_MAX of the plan's block, default 0.75) and the profile on each plan's line.
+ * line: n_plans * N_c control points, flag: n_plans exit flags of the QPs (fsaempc_qp_solve_batch_device).  A plan whose flag is
+ * not 0 takes the centre line (control points written as zeros); a plan with a bad block, w_p <= 0 or a < 0.1 in a cell is NaN in
+ * table, t and line.  opts: NULL = defaults.  workspace: fsaempc_plan_raceline_workspace_bytes(n_plans, N_c) bytes.
+ * FSAEMPC_ERR_ARG before any launch: the cases of fsaempc_plan_line_profile_batch_device; margin < 0 or not finite.
+ */
+long long fsaempc_plan_raceline_workspace_bytes(int n_plans, int N_c);
+int fsaempc_plan_raceline_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par,
+                                       int n_plans, int N_s, int N_c, double margin, double v_cap, double grip,
+                                       const fsaempc_qp_opts* opts, double* line, int* flag, double* table, double* t,
+                                       void* workspace, long long workspace_bytes, void* stream);
 
 /* ---- move blocking: held inputs --------------------------------------------------
  * The input is held constant over groups of consecutive horizon steps: block j covers steps start_j .. start_j + len_j - 1 and

@@ -4,7 +4,9 @@ one batch of B LTV-MPC QPs (frame transform + reference -> linearise/condense/so
 no per-step read-back (fsae_mpc_amd.monte_carlo).  Prints one JSON line: QP solves/s over the QPs of the cars still
 driving, the exit-flag tally the way main.m:209,222 reports it ("abnormal exits %"), iterations, progress.
 --plan: the cars track a plan of the planner stand-in (fsaempc.Plan.profile) instead of the live ramp to 20 m/s.
-usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--plan [--grip G] [--cells N_s]]"""
+--raceline: the plan is made on a minimum-curvature racing line (fsaempc.Plan.raceline) instead of the centre line.
+usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40]
+                                  [--plan | --raceline [--margin M] [--points N_c]] [--grip G] [--cells N_s]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -25,10 +27,15 @@ def main():
     ap.add_argument("--plan", action="store_true", help="track a speed-profile plan (Plan.profile) instead of the live ramp")
     ap.add_argument("--grip", type=float, default=1.0, help="with --plan: share of the lateral / longitudinal limits the plan uses, (0, 1]")
     ap.add_argument("--cells", type=int, default=500, help="with --plan: cells per lap (N_s)")
+    ap.add_argument("--raceline", action="store_true", help="track a plan on a minimum-curvature racing line (Plan.raceline); takes --grip and --cells too")
+    ap.add_argument("--margin", type=float, default=0.25, help="with --raceline: distance the line keeps from N_MAX, m")
+    ap.add_argument("--points", type=int, default=100, help="with --raceline: control points of the line (N_c)")
     a = ap.parse_args()
     model = fm.KINEMATIC if a.model == "kinematic" else fm.DYNAMIC
     tr = fm.Track.load("fss2019")
     plan = fm.Plan.profile(model, tr, N_s=a.cells, grip=a.grip) if a.plan else None
+    if a.raceline:
+        plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip)
     fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan)          # warm-up (allocations, code load)
     n_max = float(fm.default_params(model)[fm.PARAM_INDEX["N_MAX"]])
     opts = fm.default_opts(max_iter=a.max_iter)
@@ -80,7 +87,8 @@ def main():
                    "mean_ipm_iterations": float(it[ac].mean()) if n_act else 0.0,
                    "cars_past_end_of_track_parameter": int((cl.finished == 1).sum().item()), "cars_lost": int((cl.finished == 2).sum().item()),
                    "mean_speed_end": float(cl.cart[:, 3].mean().item()),
-                   "reference": ("plan: speed profile, N_s = %d, grip %g, lap %.2f s" % (a.cells, a.grip, float(plan.lap_time()[0]))) if a.plan else "live ramp to 20 m/s",
+                   "reference": ("plan: racing line, N_s = %d, N_c = %d, margin %g, grip %g, QP flag %d, lap %.2f s" % (a.cells, a.points, a.margin, a.grip, int(plan.line_flag[0]), float(plan.lap_time()[0]))) if a.raceline
+                                else ("plan: speed profile, N_s = %d, grip %g, lap %.2f s" % (a.cells, a.grip, float(plan.lap_time()[0]))) if a.plan else "live ramp to 20 m/s",
                    "steps_off_track_abs_n_gt_N_MAX": int(off.item()), "mean_distance_covered_m": float(np.nanmean(dist)),
                    "total_distance_covered_m": float(np.nansum(dist)),
                    "median_abs_lateral_offset_end": float(np.nanmedian(np.abs(x0[:, 1]))), "seed": a.seed, "max_iter": a.max_iter, "warm_start": bool(a.warm), "launch_hint": not a.no_launch_hint}}))
