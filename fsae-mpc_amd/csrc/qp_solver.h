@@ -73,6 +73,7 @@ bool qp_runs_wavefront_kernel(const QpDims& d);   // kernel selection of qp_laun
 hipError_t qp_launch(const QpParams& P, int batch, hipStream_t st, hipEvent_t ev_mid = nullptr);
 int qp_selftest_mfma(char* msg, int msglen);
 int qp_selftest_lane_reduce(char* msg, int msglen);   // DPP / lane-swap reductions against zero-filling moves and an LDS tree
+int qp_selftest_diag_factor(char* msg, int msglen);   // diag_factor: the newer forms against the former one on 64 tiles, bit for bit
 // LDS bytes of the workgroup solve kernel (qp_wg.hip); NBk = border width of the kernel variant (0 or 4).  Mirrors the carve at
 // the top of qp_wg_kernel.
 #define QP_WG_NVEC_FIXED 14   /* X G HX P1 P2 P3 DX E R1 R2 + DV W1V W2V LV */

@@ -45,6 +45,17 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 #ifndef QP_SOLVE_PAIR
 #define QP_SOLVE_PAIR 0
 #endif
+// 1: diag_factor builds its MFMA A operand with lane selects on constant masks and updates the diagonal tile first; 0: the former
+// form (divergent regions, diagonal tile last).  Same arithmetic, same bits (profiles/chol_panels/README.md).  The choice is made
+// per instantiation in DiagForm<T, NB>; the former form is always compiled as the reference of fsaempc_selftest_diag_factor().
+#ifndef QP_DIAG_FLAT
+#define QP_DIAG_FLAT 1
+#endif
+// 1: pass 1 forms the scaled operands of both k-steps of a pair ahead of the pair's MFMAs and asks the scheduler to place the
+// VALU work of a k-step between its MFMAs (A/B builds; profiles/chol_panels/README.md)
+#ifndef QP_SYRK_INTERLEAVE
+#define QP_SYRK_INTERLEAVE 0
+#endif
 #ifndef QP_FULL_BARRIERS
 #define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 #else
@@ -818,6 +829,13 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, Stream<T>& st, v4d*
         st.template next_pair<C>(k, b, u == 0 ? C : (tr + 1 < tr_end ? C : (tr + 1 < k.ntr ? k.tcs[tr + 1] : 0)));
         cs.read_pair(k, 4 * tr + 2 * u, cf);
         asm volatile("" ::: "memory");
+#if QP_SYRK_INTERLEAVE
+        double a2[2][C];   // the scaled operands of both k-steps of the pair, formed ahead of the first MFMA
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int t = 0; t < C; ++t) a2[h][t] = cf[0][h] * b[t][h];
+#endif
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           double a[C], ab[NBB];
@@ -825,7 +843,11 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, Stream<T>& st, v4d*
 #pragma unroll
           for (int e = 0; e < NB; ++e) ab[e] = cf[4 + e][h];
 #pragma unroll
+#if QP_SYRK_INTERLEAVE
+          for (int t = 0; t < C; ++t) a[t] = a2[h][t];
+#else
           for (int t = 0; t < C; ++t) a[t] = dd * b[t][h];
+#endif
 #pragma unroll
           for (int I = 0; I < C; ++I)
 #pragma unroll
@@ -844,6 +866,14 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, Stream<T>& st, v4d*
             for (int f = e; f < NB; ++f) sbb[e][f] = fma(dab, ab[f], sbb[e][f]);
             pwb[0][e] = fma(w1, ab[e], pwb[0][e]); pwb[1][e] = fma(w2, ab[e], pwb[1][e]); pwb[2][e] = fma(w3, ab[e], pwb[2][e]);
           }
+#if QP_SYRK_INTERLEAVE
+          // the k-step's VALU work (p1..p3, the border) goes between its MFMAs instead of behind them: 1 MFMA, then up to 2 VALU
+#pragma unroll
+          for (int i = 0; i < C * (C + 1) / 2; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+          }
+#endif
         }
       }
     }
@@ -1091,7 +1121,14 @@ DEVINL v4d tile_load_t(const Ctx& k, const double* slot) {
 // per tile.  No cross-lane data movement besides the readlanes, no LDS.  (The former version walked the 16 rows one
 // by one with three ds_bpermute round trips per row: 12k cycles per tile, 80 % of the whole factorisation.)
 // Only these three tiles see VALU work; every other tile of the factorisation is touched by the matrix cores alone.
-DEVINL int diag_factor(const Ctx& k, v4d& Ud, v4d& Yk, v4d& rk, double floor_abs) {
+// FLAT: each of the ten values of W goes to exactly one lane, and which one is known at compile time, so the operand is a chain of
+// selects on constant lane masks (s_mov + 2 v_cndmask per value, no compare result to keep alive, no exec-mask regions); and the
+// diagonal tile is updated before its companions, so that the readlanes of the next panel can start under their MFMAs.
+DEVINL double on_lanes(unsigned long long mask, double v, double otherwise) {   // mask: wave-uniform (here: constant once unrolled)
+  return __builtin_amdgcn_inverse_ballot_w64(mask) ? v : otherwise;
+}
+template <int FORM> DEVINL int diag_factor(const Ctx& k, v4d& Ud, v4d& Yk, v4d& rk, double floor_abs) {
+  constexpr bool FLAT = FORM >= 1;
   int bad = 0;
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
@@ -1100,7 +1137,16 @@ DEVINL int diag_factor(const Ctx& k, v4d& Ud, v4d& Yk, v4d& rk, double floor_abs
     const double d11 = rl(Ud[p], 16 + 4 * p + 1), d12 = rl(Ud[p], 16 + 4 * p + 2), d13 = rl(Ud[p], 16 + 4 * p + 3);
     const double d22 = rl(Ud[p], 32 + 4 * p + 2), d23 = rl(Ud[p], 32 + 4 * p + 3);
     const double d33 = rl(Ud[p], 48 + 4 * p + 3);
-    auto piv = [&](double t) { if (!(t > floor_abs)) { if (!(fabs(t) < INFINITY)) bad = 1; t = floor_abs; } return rsqrt(t); };
+    auto piv = [&](double t) {
+      if constexpr (FORM >= 2) {   // the same floor and the same flag, written as selects: the four panels of a tile stay one basic block
+        const bool low = !(t > floor_abs);
+        bad |= (low & !(fabs(t) < INFINITY)) ? 1 : 0;
+        t = low ? floor_abs : t;
+      } else {
+        if (!(t > floor_abs)) { if (!(fabs(t) < INFINITY)) bad = 1; t = floor_abs; }
+      }
+      return rsqrt(t);
+    };
     // R'R = D (R upper triangular), i_a = 1/R[a][a]
     const double i0 = piv(d00);
     const double r01 = d01 * i0, r02 = d02 * i0, r03 = d03 * i0;
@@ -1117,22 +1163,46 @@ DEVINL int diag_factor(const Ctx& k, v4d& Ud, v4d& Yk, v4d& rk, double floor_abs
     // ~12 divergent regions per panel and sinks the products above into them.  A branch-free construction -- 0/1 masks times the
     // ten values -- was measured in round 2: 34 % fewer instructions in the factorisation, but 464 instead of 79 spilled
     // registers in the kernel and 17 % slower overall; a leaner rsqrt alone was 2 % slower for the same reason.)
-    const int a_ = k.c - 4 * p;
-    double wa = 0.0;
-    if (k.q == 0) wa = a_ == 0 ? i0 : (a_ == 1 ? w10 : (a_ == 2 ? w20 : (a_ == 3 ? w30 : 0.0)));
-    if (k.q == 1) wa = a_ == 1 ? i1 : (a_ == 2 ? w21 : (a_ == 3 ? w31 : 0.0));
-    if (k.q == 2) wa = a_ == 2 ? i2 : (a_ == 3 ? w32 : 0.0);
-    if (k.q == 3) wa = a_ == 3 ? i3 : 0.0;
     const v4d z = {0.0, 0.0, 0.0, 0.0};
-    const v4d nu = __builtin_amdgcn_mfma_f64_16x16x4f64(wa, Ud[p], z, 0, 0, 0);
-    const v4d ny = __builtin_amdgcn_mfma_f64_16x16x4f64(wa, Yk[p], z, 0, 0, 0);
-    const v4d nr = __builtin_amdgcn_mfma_f64_16x16x4f64(wa, rk[p], z, 0, 0, 0);
-    Ud[p] = nu[p]; Yk[p] = ny[p]; rk[p] = nr[p];
-    if (p < 3) {
-      const double a = (k.c > 4 * p + 3) ? -Ud[p] : 0.0;
-      Yk = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Yk[p], Yk, 0, 0, 0);
-      rk = __builtin_amdgcn_mfma_f64_16x16x4f64(a, rk[p], rk, 0, 0, 0);
-      Ud = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Ud[p], Ud, 0, 0, 0);
+    if constexpr (FLAT) {
+      const unsigned long long L0 = 1ull << (4 * p), L1 = 1ull << (16 + 4 * p), L2 = 1ull << (32 + 4 * p), L3 = 1ull << (48 + 4 * p);
+      double wa = on_lanes(L0, i0, 0.0);
+      wa = on_lanes(L0 << 1, w10, wa); wa = on_lanes(L0 << 2, w20, wa); wa = on_lanes(L0 << 3, w30, wa);
+      wa = on_lanes(L1 << 1, i1, wa); wa = on_lanes(L1 << 2, w21, wa); wa = on_lanes(L1 << 3, w31, wa);
+      wa = on_lanes(L2 << 2, i2, wa); wa = on_lanes(L2 << 3, w32, wa);
+      wa = on_lanes(L3 << 3, i3, wa);
+      const v4d nu = __builtin_amdgcn_mfma_f64_16x16x4f64(wa, Ud[p], z, 0, 0, 0);
+      Ud[p] = nu[p];
+      double a = 0.0;
+      if (p < 3) {
+        a = on_lanes(0x0001000100010001ull * (0xFFFFull & (0xFFFFull << (4 * p + 4))), -Ud[p], 0.0);   // columns c > 4p + 3
+        Ud = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Ud[p], Ud, 0, 0, 0);
+      }
+      const v4d ny = __builtin_amdgcn_mfma_f64_16x16x4f64(wa, Yk[p], z, 0, 0, 0);
+      const v4d nr = __builtin_amdgcn_mfma_f64_16x16x4f64(wa, rk[p], z, 0, 0, 0);
+      Yk[p] = ny[p]; rk[p] = nr[p];
+      if (p < 3) {
+        Yk = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Yk[p], Yk, 0, 0, 0);
+        rk = __builtin_amdgcn_mfma_f64_16x16x4f64(a, rk[p], rk, 0, 0, 0);
+      }
+      if constexpr (FORM >= 2) asm("" : "+v"(bad));   // the flag is settled per panel: no compare mask or pivot outlives its panel
+    } else {
+      const int a_ = k.c - 4 * p;
+      double wa = 0.0;
+      if (k.q == 0) wa = a_ == 0 ? i0 : (a_ == 1 ? w10 : (a_ == 2 ? w20 : (a_ == 3 ? w30 : 0.0)));
+      if (k.q == 1) wa = a_ == 1 ? i1 : (a_ == 2 ? w21 : (a_ == 3 ? w31 : 0.0));
+      if (k.q == 2) wa = a_ == 2 ? i2 : (a_ == 3 ? w32 : 0.0);
+      if (k.q == 3) wa = a_ == 3 ? i3 : 0.0;
+      const v4d nu = __builtin_amdgcn_mfma_f64_16x16x4f64(wa, Ud[p], z, 0, 0, 0);
+      const v4d ny = __builtin_amdgcn_mfma_f64_16x16x4f64(wa, Yk[p], z, 0, 0, 0);
+      const v4d nr = __builtin_amdgcn_mfma_f64_16x16x4f64(wa, rk[p], z, 0, 0, 0);
+      Ud[p] = nu[p]; Yk[p] = ny[p]; rk[p] = nr[p];
+      if (p < 3) {
+        const double a = (k.c > 4 * p + 3) ? -Ud[p] : 0.0;
+        Yk = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Yk[p], Yk, 0, 0, 0);
+        rk = __builtin_amdgcn_mfma_f64_16x16x4f64(a, rk[p], rk, 0, 0, 0);
+        Ud = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Ud[p], Ud, 0, 0, 0);
+      }
     }
   }
 #pragma unroll
@@ -1140,14 +1210,20 @@ DEVINL int diag_factor(const Ctx& k, v4d& Ud, v4d& Yk, v4d& rk, double floor_abs
   return bad;
 }
 
+// Which form of diag_factor an instantiation takes: one that the new form costs registers keeps the former one.  With the shipped
+// flags either new form gives <5,0> 20 instead of 8 spilled vector registers, T = 6 and T = 7 more scratch, and T <= 3 ten more
+// AGPRs, which takes <2,1> from two waves per SIMD to one (profiles/chol_panels/resource_usage.txt); <5,1> and <5,4> are level
+// or better.
+template <int T, int NB> struct DiagForm { static constexpr int form = (T == 5 && NB > 0) ? QP_DIAG_FLAT : 0; };
+
 // Blocked Cholesky of acc (upper tiles) in place.  Yt[K] = U_KK^-T and Wt[K] = U_KK^-1 are kept for the solves;
 // rh rides along and leaves as y = U^-T b.
-template <int T, int K, bool RHS> struct FactorStep {
+template <int T, int NB, int K, bool RHS> struct FactorStep {
   static DEVINL int run(const Ctx& k, v4d* acc, double* YL, v4d* rh, double floor_abs) {
     v4d Yk, none = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int p = 0; p < 4; ++p) Yk[p] = (k.q + 4 * p == k.c) ? 1.0 : 0.0;
-    int bad = diag_factor(k, acc[Tri<T>::idx(K, K)], Yk, RHS ? rh[K] : none, floor_abs);
+    int bad = diag_factor<DiagForm<T, NB>::form>(k, acc[Tri<T>::idx(K, K)], Yk, RHS ? rh[K] : none, floor_abs);
     tile_store(k, YL + K * 272, Yk);          // U_KK^-T stays in LDS for the solves of this iteration
     WAVE_SYNC();
     const v4d Wk = tile_load_t(k, YL + K * 272);   // U_KK^-1
@@ -1175,19 +1251,19 @@ template <int T, int K, bool RHS> struct FactorStep {
       for (int Jt = I; Jt < T; ++Jt) mfma4_sub<T>(UKI, acc[Tri<T>::idx(K, Jt)], acc[Tri<T>::idx(I, Jt)]);
       if (RHS) mfma4_sub<T>(UKI, rh[K], rh[I]);
     }
-    return bad | FactorStep<T, K + 1, RHS>::run(k, acc, YL, rh, floor_abs);
+    return bad | FactorStep<T, NB, K + 1, RHS>::run(k, acc, YL, rh, floor_abs);
   }
 };
-template <int T, bool RHS> struct FactorStep<T, T, RHS> {
+template <int T, int NB, bool RHS> struct FactorStep<T, NB, T, RHS> {
   static DEVINL int run(const Ctx&, v4d*, double*, v4d*, double) { return 0; }
 };
 // with right-hand sides riding along as a tile column (they leave as y = U^-T b) ...
-template <int T> DEVINL int reg_factor(const Ctx& k, v4d* acc, double* YL, v4d* rh, double floor_abs) {
-  return FactorStep<T, 0, true>::run(k, acc, YL, rh, floor_abs);
+template <int T, int NB> DEVINL int reg_factor(const Ctx& k, v4d* acc, double* YL, v4d* rh, double floor_abs) {
+  return FactorStep<T, NB, 0, true>::run(k, acc, YL, rh, floor_abs);
 }
 // ... or the factor alone (the solves then run on the VALU: vec_forward / vec_backward)
-template <int T> DEVINL int reg_factor_only(const Ctx& k, v4d* acc, double* YL, double floor_abs) {
-  return FactorStep<T, 0, false>::run(k, acc, YL, nullptr, floor_abs);
+template <int T, int NB> DEVINL int reg_factor_only(const Ctx& k, v4d* acc, double* YL, double floor_abs) {
+  return FactorStep<T, NB, 0, false>::run(k, acc, YL, nullptr, floor_abs);
 }
 
 // forward solve U'y = b on a fresh right-hand-side tile column: y_K = U_KK^-T (b_K - sum_{I<K} U_IK' y_I)
@@ -1682,9 +1758,9 @@ template <int T, int NB> __global__ __launch_bounds__(64, QP_WAVES_PER_SIMD) voi
       const double* vin[6] = {R1, R2, MB, MB + k.np, MB + 2 * k.np, MB + 3 * k.np};
       rhs_load<T, 2 + NB>(k, rh, vin);
     }
-    int fbad = reg_factor<T>(k, acc, YL, rh, 1e-30 * dmax);
+    int fbad = reg_factor<T, NB>(k, acc, YL, rh, 1e-30 * dmax);
 #else
-    int fbad = reg_factor_only<T>(k, acc, YL, 1e-30 * dmax);
+    int fbad = reg_factor_only<T, NB>(k, acc, YL, 1e-30 * dmax);
     WAVE_SYNC();
     STAMP(5);
 #endif
@@ -2569,6 +2645,47 @@ __global__ __launch_bounds__(64) void lane_reduce_selftest_kernel(const double* 
     if (atomicAdd(&out[0], bad) == 0) { out[1] = first; out[2] = first_round; out[3] = lane; }
   }
 }
+
+// ---------------------------------------------------------------------------------------------
+// diag_factor self test: one wave, all lanes active.  Every tile goes through the former form (FORM 0) and through the two newer
+// ones; the diagonal tile, both companions and the flag must agree bit for bit (also where they are NaN).
+// in: per tile 512 doubles, the diagonal tile and the right-hand-side tile, row-major 16 x 16.  out: {mismatches, first tile, form, lane}.
+// ---------------------------------------------------------------------------------------------
+template <int FORM> DEVINL int diag_factor_bad_vs_old(const Ctx& k, const v4d& U0, const v4d& R0, double floor_abs, const v4d& Uo, const v4d& Yo, const v4d& Ro, int bo) {
+  v4d U = U0, R = R0, Y;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) Y[p] = (k.q + 4 * p == k.c) ? 1.0 : 0.0;
+  const int b = diag_factor<FORM>(k, U, Y, R, floor_abs);
+  int bad = (b != bo) ? 1 : 0;
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+    bad += (__double_as_longlong(U[p]) != __double_as_longlong(Uo[p])) + (__double_as_longlong(Y[p]) != __double_as_longlong(Yo[p])) +
+           (__double_as_longlong(R[p]) != __double_as_longlong(Ro[p]));
+  return bad;
+}
+__global__ __launch_bounds__(64) void diag_factor_selftest_kernel(const double* __restrict__ in, int ntiles, double floor_abs, int* __restrict__ out) {
+  Ctx k = {};
+  k.lane = threadIdx.x; k.c = k.lane & 15; k.q = k.lane >> 4;
+  int bad = 0, first = -1, form = 0;
+  for (int t = 0; t < ntiles; ++t) {   // (uniform trip count: every lane stays active)
+    v4d U0, R0, Uo, Ro, Yo;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      U0[p] = in[(size_t)t * 512 + (k.q + 4 * p) * 16 + k.c];
+      R0[p] = in[(size_t)t * 512 + 256 + (k.q + 4 * p) * 16 + k.c];
+      Yo[p] = (k.q + 4 * p == k.c) ? 1.0 : 0.0;
+    }
+    Uo = U0; Ro = R0;
+    const int bo = diag_factor<0>(k, Uo, Yo, Ro, floor_abs);
+    const int b1 = diag_factor_bad_vs_old<1>(k, U0, R0, floor_abs, Uo, Yo, Ro, bo);
+    const int b2 = diag_factor_bad_vs_old<2>(k, U0, R0, floor_abs, Uo, Yo, Ro, bo);
+    if ((b1 | b2) && first < 0) { first = t; form = b1 ? 1 : 2; }
+    bad += b1 + b2;
+  }
+  if (bad) {
+    if (atomicAdd(&out[0], bad) == 0) { out[1] = first; out[2] = form; out[3] = k.lane; }
+  }
+}
 #endif  // QP_MAIN_TU
 
 }  // namespace
@@ -2621,6 +2738,50 @@ template <int T, int NB> __global__ __launch_bounds__(64) void syrk_probe_kernel
 #endif
 
 #ifdef QP_PROBE
+// Diagnostic build only: does fp64 VALU work run beside fp64 MFMAs of the same wave?  Three loops of `reps` trips: 16 MFMAs (two on
+// each of 8 accumulators); 32 v_fma_f64 (four on each of 8 chains); both, 2 FMAs behind every MFMA.  out[0..2] = cycles per trip of
+// each (block 0), out[3] = checksum.  One wave per SIMD when launched with the batch as the grid, as the solver runs.
+__global__ __launch_bounds__(64) void overlap_probe_kernel(double* out, int reps) {
+  const double x = 1.0 + 1e-9 * threadIdx.x, y = 1e-12 * (threadIdx.x + 1);
+  v4d acc[8]; double f[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { acc[i] = v4d{0.0, 0.0, 0.0, 0.0}; f[i] = 1.0 + i; }
+  __builtin_amdgcn_sched_barrier(0);
+  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+  for (int r = 0; r < reps; ++r) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i & 7] = __builtin_amdgcn_mfma_f64_16x16x4f64(x, y, acc[i & 7], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+  for (int r = 0; r < reps; ++r) {
+#pragma unroll
+    for (int i = 0; i < 32; ++i) f[i & 7] = fma(f[i & 7], x, y);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  const unsigned long long t2 = __builtin_amdgcn_s_memtime();
+  for (int r = 0; r < reps; ++r) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      acc[i & 7] = __builtin_amdgcn_mfma_f64_16x16x4f64(x, y, acc[i & 7], 0, 0, 0);
+      f[(2 * i) & 7] = fma(f[(2 * i) & 7], x, y); f[(2 * i + 1) & 7] = fma(f[(2 * i + 1) & 7], x, y);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 2, 0); }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  const unsigned long long t3 = __builtin_amdgcn_s_memtime();
+  double cs = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) cs += acc[i][0] + acc[i][3] + f[i];
+  cs = wave_sum(cs);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    out[0] = (double)(t1 - t0) / reps; out[1] = (double)(t2 - t1) / reps; out[2] = (double)(t3 - t2) / reps; out[3] = cs;
+  }
+}
+#endif
+
+#ifdef QP_PROBE
 // Diagnostic build only: the register Cholesky alone.  out[b][0..5] = cycles of: whole reg_factor, T diag_factor calls,
 // T LDS round trips (tile_store + tile_load_t), forward+backward solve of one right-hand-side column.
 template <int T> __global__ __launch_bounds__(64) void factor_probe_kernel(QpParams P, int reps) {
@@ -2650,7 +2811,7 @@ template <int T> __global__ __launch_bounds__(64) void factor_probe_kernel(QpPar
     }
     __builtin_amdgcn_sched_barrier(0);
     unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    reg_factor<T>(k, acc, YL, rh, 1e-30);
+    reg_factor<T, 1>(k, acc, YL, rh, 1e-30);   // (the headline instantiation's form)
     __builtin_amdgcn_sched_barrier(0);
     unsigned long long t1 = __builtin_amdgcn_s_memtime();
     tt[0] += t1 - t0;
@@ -2659,7 +2820,7 @@ template <int T> __global__ __launch_bounds__(64) void factor_probe_kernel(QpPar
     for (int K = 0; K < T; ++K) {
 #pragma unroll
       for (int p = 0; p < 4; ++p) { Yk[p] = (k.q + 4 * p == k.c) ? 1.0 : 0.0; if (k.q + 4 * p == k.c) acc[Tri<T>::idx(K, K)][p] += 30.0; }
-      diag_factor(k, acc[Tri<T>::idx(K, K)], Yk, rh[K], 1e-30);
+      diag_factor<DiagForm<T, 1>::form>(k, acc[Tri<T>::idx(K, K)], Yk, rh[K], 1e-30);
       cs += Yk[0];
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -2872,6 +3033,7 @@ hipError_t qp_launch(const QpParams& P, int batch, hipStream_t st, hipEvent_t ev
   if (P.dump && P.dump_stage == 8 && P.d.T == 5 && P.d.NB == 1) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&syrk_probe_kernel<5, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.d.lds_solve);
     hipLaunchKernelGGL((syrk_probe_kernel<5, 1>), dim3(batch), dim3(64), P.d.lds_solve, st, P, 16);
+    hipLaunchKernelGGL(overlap_probe_kernel, dim3(batch), dim3(64), 0, st, P.dump + 2 * (size_t)batch, 2048);   // (the caller leaves 64 doubles there)
     return hipGetLastError();
   }
 #endif
@@ -2953,6 +3115,55 @@ int qp_selftest_lane_reduce(char* msg, int msglen) {
   if (e != hipSuccess) { snprintf(msg, msglen, "lane-reduce selftest: %s", hipGetErrorString(e)); return -1; }
   if (hout[0]) snprintf(msg, msglen, "lane reductions: %d mismatches, first: test %d (1/2/4/8: grp16 single / batched, 16: q, 64: wave, 65: wave_sum batch) op %d (sum/max/min) round %d lane %d",
                         hout[0], hout[1] / 100, hout[1] % 100, hout[2], hout[3]);
+  return hout[0];
+}
+
+int qp_selftest_diag_factor(char* msg, int msglen) {
+  // 64 tiles: 61 SPD tiles D = Q diag(s) Q' with condition numbers 1 .. 1e10 (Q: a product of Householder reflections), then a tile
+  // with a pivot under the floor, one with a NaN and one with +Inf; every tile with a full right-hand-side tile
+  const int ntiles = 64;
+  const double floor_abs = 1e-9;
+  double* h = (double*)malloc(sizeof(double) * ntiles * 512);
+  if (!h) return -1;
+  unsigned long long st = 0xD1B54A32D192ED03ull;   // fixed seed
+  auto rnd = [&]() { st = st * 6364136223846793005ull + 1442695040888963407ull; return ((unsigned)(st >> 33)) / 2147483648.0; };
+  for (int t = 0; t < ntiles; ++t) {
+    double* D = h + (size_t)t * 512; double* R = D + 256;
+    double Q[16][16], sv[16];
+    for (int i = 0; i < 16; ++i) for (int j = 0; j < 16; ++j) Q[i][j] = i == j ? 1.0 : 0.0;
+    for (int r = 0; r < 3; ++r) {   // Q <- Q (I - 2 v v' / v'v)
+      double v[16], vv = 0;
+      for (int i = 0; i < 16; ++i) { v[i] = 2.0 * rnd() - 1.0; vv += v[i] * v[i]; }
+      for (int i = 0; i < 16; ++i) {
+        double qv = 0;
+        for (int j = 0; j < 16; ++j) qv += Q[i][j] * v[j];
+        for (int j = 0; j < 16; ++j) Q[i][j] -= 2.0 * qv * v[j] / vv;
+      }
+    }
+    const double lc = 10.0 * (t < 61 ? t / 60.0 : 0.3);   // log10 of the condition number
+    for (int i = 0; i < 16; ++i) sv[i] = pow(10.0, -lc * i / 15.0);
+    for (int i = 0; i < 16; ++i) for (int j = 0; j < 16; ++j) {
+      double a = 0;
+      for (int l = 0; l < 16; ++l) a += Q[i][l] * sv[l] * Q[j][l];
+      D[i * 16 + j] = a;
+    }
+    for (int i = 0; i < 16; ++i) for (int j = 0; j < i; ++j) D[i * 16 + j] = D[j * 16 + i];   // exactly symmetric
+    for (int i = 0; i < 256; ++i) R[i] = 20.0 * rnd() - 10.0;
+    if (t == 61) for (int j = 0; j < 16; ++j) { D[6 * 16 + j] *= 1e-6; D[j * 16 + 6] *= 1e-6; }   // pivot 6 falls under the floor
+    if (t == 62) { D[5 * 16 + 9] = NAN; D[9 * 16 + 5] = NAN; }
+    if (t == 63) D[10 * 16 + 10] = INFINITY;
+  }
+  double* d = 0; int* dout = 0; int hout[4] = {0, 0, 0, 0};
+  if (hipMalloc(&d, sizeof(double) * ntiles * 512) != hipSuccess || hipMalloc(&dout, sizeof(hout)) != hipSuccess) { free(h); if (d) (void)hipFree(d); return -1; }
+  (void)hipMemcpy(d, h, sizeof(double) * ntiles * 512, hipMemcpyHostToDevice);
+  (void)hipMemset(dout, 0, sizeof(hout));
+  free(h);
+  hipLaunchKernelGGL(diag_factor_selftest_kernel, dim3(1), dim3(64), 0, 0, d, ntiles, floor_abs, dout);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(hout, dout, sizeof(hout), hipMemcpyDeviceToHost);
+  (void)hipFree(d); (void)hipFree(dout);
+  if (e != hipSuccess) { snprintf(msg, msglen, "diag_factor selftest: %s", hipGetErrorString(e)); return -1; }
+  if (hout[0]) snprintf(msg, msglen, "diag_factor forms: %d mismatches with the former form, first: tile %d form %d lane %d", hout[0], hout[1], hout[2], hout[3]);
   return hout[0];
 }
 #endif  // QP_MAIN_TU

@@ -679,6 +679,10 @@ int fsaempc_selftest_mfma(void);
  * +-Inf and NaN: bit for bit against the zero-filling lane moves and against a tree through LDS with the same pairing.
  * Returns 0 if all agree, >0 number of mismatches, <0 without a device. */
 int fsaempc_selftest_lane_reduce(void);
+/* Runs the on-device self-test of the diagonal-tile factorisation of the solve kernel's register Cholesky: 64 tiles (SPD with condition
+ * numbers 1..1e10, a pivot under the floor, a NaN, +Inf) through the former form of diag_factor and through the newer ones; the
+ * factor, both companion tiles and the flag are compared bit for bit.  Returns 0 if all agree, >0 number of mismatches, <0 without a device. */
+int fsaempc_selftest_diag_factor(void);
 /* Debug hook of the diagnostic builds only (libfsaempc_dbg.so, -DQP_DEBUG_DUMP; the shipped kernels carry no dump
  * branches and ignore it): dumps solver internals of instance 0 after `stage` (see qp_solver.hip) into `out` (device
  * pointer, >= 4*nV*nV+8*(nV+nC) doubles).  Process-global, not thread-safe. */

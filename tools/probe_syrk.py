@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Diagnostic (QP_PROBE build): cycles of pass 1 alone vs inside the solver (compare with tools/phase_profile.py)."""
+"""Diagnostic (QP_PROBE build): cycles of pass 1 alone vs inside the solver (compare with tools/phase_profile.py), and whether fp64
+VALU work runs beside the fp64 MFMAs of the same wave (overlap_probe_kernel: 16 MFMAs; 32 v_fma_f64; both interleaved)."""
 import ctypes as C, os, sys
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -19,3 +20,6 @@ for _ in range(2):
 fm.lib().fsaempc_debug_set_dump(None, 0)
 d = dump.cpu().numpy()
 print("pass 1 alone: %.0f cycles/pass (mean over %d QPs), min %.0f max %.0f ; checksum[0] %.6e" % (d[:B].mean(), B, d[:B].min(), d[:B].max(), d[B]))
+o = d[2 * B:2 * B + 4]
+print("overlap probe, cycles per trip (block 0): 16 MFMA %.0f | 32 v_fma_f64 %.0f | 16 MFMA + 32 v_fma_f64 interleaved %.0f (sum of the parts %.0f) ; checksum %.6e"
+      % (o[0], o[1], o[2], o[0] + o[1], o[3]))
