@@ -22,15 +22,17 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/qp_solver.h $(CSRC)/qp_sens.h $(CSRC)/ltv_b
 # bytes per lane before): hoisted address arithmetic no longer lives across the whole iteration loop.
 WGFLAGS := -mllvm -disable-machine-licm -mllvm -sink-insts-to-avoid-spills=1
 
-# qp_solver.hip is compiled as six translation units (see the note in the file): main + the tile counts T = 1..4, 5, 6, 7
+# qp_solver.hip is compiled as five translation units (see the note in the file): main + the tile counts T = 1..4, 5, 6, 7
+QPHDRS := $(CSRC)/qp_solver.h $(CSRC)/qp_lane.h $(CSRC)/qp_solve_kernel.h $(CSRC)/qp_selftest.h $(CSRC)/qp_probe.h
+WGHDRS := $(CSRC)/qp_solver.h $(CSRC)/qp_lane.h
 QPOBJ := $(LIBDIR)/qp_solver_tu0.o $(LIBDIR)/qp_solver_tu1.o $(LIBDIR)/qp_solver_tu2.o $(LIBDIR)/qp_solver_tu3.o $(LIBDIR)/qp_solver_tu4.o
-$(LIBDIR)/qp_solver_tu%.o: $(CSRC)/qp_solver.hip $(CSRC)/qp_solver.h include/fsaempc.h $(CHECKDEPS)
+$(LIBDIR)/qp_solver_tu%.o: $(CSRC)/qp_solver.hip $(QPHDRS) include/fsaempc.h $(CHECKDEPS)
 	@mkdir -p $(LIBDIR)
 	$(CC_CHECKED) $@ $< $(HIPFLAGS) $(WGFLAGS) -DQP_TU=$*
 
 # qp_wg.hip (workgroup-per-QP solve kernel, tile counts T = 1..12) is compiled once per range of tile counts (lo_hi)
 WGOBJ := $(LIBDIR)/qp_wg_1_5.o $(LIBDIR)/qp_wg_6_6.o $(LIBDIR)/qp_wg_7_7.o $(LIBDIR)/qp_wg_8_8.o $(LIBDIR)/qp_wg_9_9.o $(LIBDIR)/qp_wg_10_10.o $(LIBDIR)/qp_wg_11_11.o $(LIBDIR)/qp_wg_12_12.o
-$(LIBDIR)/qp_wg_%.o: $(CSRC)/qp_wg.hip $(CSRC)/qp_solver.h include/fsaempc.h $(CHECKDEPS)
+$(LIBDIR)/qp_wg_%.o: $(CSRC)/qp_wg.hip $(WGHDRS) include/fsaempc.h $(CHECKDEPS)
 	@mkdir -p $(LIBDIR)
 	$(CC_CHECKED) $@ $< $(HIPFLAGS) $(WGFLAGS) -DQP_WG_TLO=$(word 1,$(subst _, ,$*)) -DQP_WG_THI=$(word 2,$(subst _, ,$*))
 
@@ -46,10 +48,10 @@ $(LIBDIR)/libfsaempc.so: $(QPOBJ) $(WGOBJ) $(COMMON)
 # development builds of the workgroup kernel: ONE instantiation (T = 8 + slack border: BASELINE configs[2], dynamic N = 60) linked with the
 # shipped objects of everything else; plain and with phase stamps.  Select with FSAEMPC_LIB.
 WGDEVFLAGS := $(WGFLAGS) -DQP_WG_TLO=8 -DQP_WG_THI=8 -DQP_WG_ONLY_NB=4
-$(LIBDIR)/wgdev_qp_wg.o: $(CSRC)/qp_wg.hip $(CSRC)/qp_solver.h include/fsaempc.h
+$(LIBDIR)/wgdev_qp_wg.o: $(CSRC)/qp_wg.hip $(WGHDRS) include/fsaempc.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) $(WGDEVFLAGS) -c $< -o $@
-$(LIBDIR)/wgdevst_qp_wg.o: $(CSRC)/qp_wg.hip $(CSRC)/qp_solver.h include/fsaempc.h
+$(LIBDIR)/wgdevst_qp_wg.o: $(CSRC)/qp_wg.hip $(WGHDRS) include/fsaempc.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) $(WGDEVFLAGS) -DQP_STAMPS=1 -c $< -o $@
 WGDEVREST := $(QPOBJ) $(filter-out $(LIBDIR)/qp_wg_8_8.o,$(WGOBJ)) $(COMMON)
@@ -61,10 +63,10 @@ $(LIBDIR)/libfsaempc_wgdevst.so: $(LIBDIR)/wgdevst_qp_wg.o $(WGDEVREST)
 
 # diagnostic library with the in-kernel dump hooks of both kernels (tests/test_gpu_parity.py::test_01_normal_matrix_dump_matches_numpy); T <= 5
 DBGOBJ := $(LIBDIR)/dbg_qp_solver_tu0.o $(LIBDIR)/dbg_qp_solver_tu1.o $(LIBDIR)/dbg_qp_solver_tu2.o $(LIBDIR)/dbg_qp_wg_1_5.o
-$(LIBDIR)/dbg_qp_wg_%.o: $(CSRC)/qp_wg.hip $(CSRC)/qp_solver.h include/fsaempc.h $(CHECKDEPS)
+$(LIBDIR)/dbg_qp_wg_%.o: $(CSRC)/qp_wg.hip $(WGHDRS) include/fsaempc.h $(CHECKDEPS)
 	@mkdir -p $(LIBDIR)
 	$(CC_CHECKED) $@ $< $(HIPFLAGS) $(WGFLAGS) -DQP_DEBUG_DUMP -DQP_WG_TLO=$(word 1,$(subst _, ,$*)) -DQP_WG_THI=$(word 2,$(subst _, ,$*))
-$(LIBDIR)/dbg_qp_solver_tu%.o: $(CSRC)/qp_solver.hip $(CSRC)/qp_solver.h include/fsaempc.h $(CHECKDEPS)
+$(LIBDIR)/dbg_qp_solver_tu%.o: $(CSRC)/qp_solver.hip $(QPHDRS) include/fsaempc.h $(CHECKDEPS)
 	@mkdir -p $(LIBDIR)
 	$(CC_CHECKED) $@ $< $(HIPFLAGS) $(WGFLAGS) -DQP_DEBUG_DUMP -DQP_TU=$*
 dbg: $(LIBDIR)/libfsaempc_dbg.so
@@ -77,12 +79,12 @@ O1FLAGS := --offload-arch=$(ARCH) -O1 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wno-
 O1OBJ := $(LIBDIR)/o1_qp_solver_tu0.o $(LIBDIR)/o1_qp_solver_tu1.o $(LIBDIR)/o1_qp_solver_tu2.o $(LIBDIR)/o1_qp_solver_tu3.o $(LIBDIR)/o1_qp_solver_tu4.o \
          $(LIBDIR)/o1_qp_wg_1_5.o $(LIBDIR)/o1_qp_wg_6_6.o $(LIBDIR)/o1_qp_wg_7_7.o $(LIBDIR)/o1_qp_wg_8_8.o $(LIBDIR)/o1_qp_wg_9_9.o $(LIBDIR)/o1_qp_wg_10_10.o \
          $(LIBDIR)/o1_qp_wg_11_11.o $(LIBDIR)/o1_qp_wg_12_12.o
-$(LIBDIR)/o1_qp_solver_tu%.o: $(CSRC)/qp_solver.hip $(CSRC)/qp_solver.h include/fsaempc.h $(CHECKDEPS)
+$(LIBDIR)/o1_qp_solver_tu%.o: $(CSRC)/qp_solver.hip $(QPHDRS) include/fsaempc.h $(CHECKDEPS)
 	@mkdir -p $(LIBDIR)
 	$(CC_CHECKED) $@ $< $(O1FLAGS) -DQP_TU=$*
 # (the guard's workgroup kernels take the unpipelined variant of pass 1, -DQP_WG_NOPIPE: an independent code path for the check,
 #  and the -O1 build of the pipelined one walks wrong iterates on kinematic N = 64 -- DESIGN.md 5c, open)
-$(LIBDIR)/o1_qp_wg_%.o: $(CSRC)/qp_wg.hip $(CSRC)/qp_solver.h include/fsaempc.h $(CHECKDEPS)
+$(LIBDIR)/o1_qp_wg_%.o: $(CSRC)/qp_wg.hip $(WGHDRS) include/fsaempc.h $(CHECKDEPS)
 	@mkdir -p $(LIBDIR)
 	$(CC_CHECKED) $@ $< $(O1FLAGS) -DQP_WG_NOPIPE -DQP_WG_TLO=$(word 1,$(subst _, ,$*)) -DQP_WG_THI=$(word 2,$(subst _, ,$*))
 o1: $(LIBDIR)/libfsaempc_O1.so

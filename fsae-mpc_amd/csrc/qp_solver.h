@@ -1,4 +1,4 @@
-// qp_solver.h -- internal interface between the C ABI (capi.hip) and the QP kernels (qp_solver.hip)
+// qp_solver.h -- internal interface between the C ABI (capi.hip) and the QP kernels (qp_solver.hip, qp_wg.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -43,7 +43,6 @@ struct QpParams {
   int *exitflag, *iter;
   double tol, tol_loose, tol_x, inf_bound;
   int max_iter, shared_HA, polish;
-  int reserved0;
   int* polished;   // optional per-instance output: >0 if the active-set refinement was accepted (attempt count), <0 reason of rejection
   double* kkt;     // optional per-instance output: relative KKT residual of the returned point as the kernel measured it
   double* dump; int dump_stage, dump_iter;
@@ -74,6 +73,18 @@ hipError_t qp_launch(const QpParams& P, int batch, hipStream_t st, hipEvent_t ev
 int qp_selftest_mfma(char* msg, int msglen);
 int qp_selftest_lane_reduce(char* msg, int msglen);   // DPP / lane-swap reductions against zero-filling moves and an LDS tree
 int qp_selftest_diag_factor(char* msg, int msglen);   // diag_factor: the newer forms against the former one on 64 tiles, bit for bit
+// LDS of the one-wavefront solve kernel (qp_solve_kernel.h): the sizes, in doubles, of its regions in their order -- QP_SOLVE_NVEC
+// n-vectors of np | one vector per border column (at least one) | T resident tiles U_KK^-T of 272 | operand ring, QP_SOLVE_RING(T)
+// records of 128 | coefficient staging, (6 + NB) arrays of 64.  The kernel carves its LDS with this, qp_make_dims sizes the launch.
+#define QP_SOLVE_NVEC 10          /* X G HX R1 R2 P1 P2 P3 DX E (enum VecArr) */
+#define QP_SOLVE_RING(T) (3 * (T))   /* lead of two pairs of k-steps + the pair being consumed (StreamCfg<T>::R) */
+struct QpSolveLds {
+  size_t vecs, border, tiles, ring, cof;
+  __host__ __device__ size_t total() const { return vecs + border + tiles + ring + cof; }
+};
+__host__ __device__ inline QpSolveLds qp_solve_lds(int T, int NB, int np) {
+  return {(size_t)QP_SOLVE_NVEC * np, (size_t)(NB > 0 ? NB : 1) * np, (size_t)T * 272, (size_t)QP_SOLVE_RING(T) * 128, (size_t)(6 + NB) * 64};
+}
 // LDS bytes of the workgroup solve kernel (qp_wg.hip); NBk = border width of the kernel variant (0 or 4).  Mirrors the carve at
 // the top of qp_wg_kernel.
 #define QP_WG_NVEC_FIXED 14   /* X G HX P1 P2 P3 DX E R1 R2 + DV W1V W2V LV */

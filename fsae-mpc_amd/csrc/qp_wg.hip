@@ -31,10 +31,8 @@
 #include <math.h>
 #include <stdint.h>
 #include "qp_solver.h"
+#include "qp_lane.h"
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef double v2d __attribute__((ext_vector_type(2)));
-#define DEVINL __device__ __forceinline__
 #define AINL __attribute__((always_inline))
 
 extern __shared__ __attribute__((aligned(16))) double slds[];
@@ -42,46 +40,15 @@ extern __shared__ __attribute__((aligned(16))) double slds[];
 // the compiler must be told -- from a single thread's point of view a location another lane writes never changes, and load
 // elimination / PRE across a predicated store hands lanes their own stale value (seen: the last block of the single-wave forward
 // solve, right in lane group 0 and wrong in groups 1..3).  Every such hand-off gets this fence.
-#define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
+// (WAVE_SYNC: qp_lane.h)
 
 namespace {
 
-DEVINL double rl(double v, int src) {  // wave-uniform broadcast of lane `src`
-  int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-  int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
-template <int CTRL> DEVINL double dpp_f64(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-// reductions over the 16 lanes sharing l>>4 (one DPP row); every lane gets the result
-DEVINL double grp16_sum(double v) { v += dpp_f64<0xB1>(v); v += dpp_f64<0x4E>(v); v += dpp_f64<0x141>(v); v += dpp_f64<0x140>(v); return v; }
-DEVINL double grp16_max(double v) { v = fmax(v, dpp_f64<0xB1>(v)); v = fmax(v, dpp_f64<0x4E>(v)); v = fmax(v, dpp_f64<0x141>(v)); v = fmax(v, dpp_f64<0x140>(v)); return v; }
-DEVINL double grp16_min(double v) { v = fmin(v, dpp_f64<0xB1>(v)); v = fmin(v, dpp_f64<0x4E>(v)); v = fmin(v, dpp_f64<0x141>(v)); v = fmin(v, dpp_f64<0x140>(v)); return v; }
-// whole-wave reductions (all 64 lanes active at the call): DPP within the four rows, then four scalar lane reads
-DEVINL double wave_sum(double v) { v = grp16_sum(v); return (rl(v, 0) + rl(v, 16)) + (rl(v, 32) + rl(v, 48)); }
-DEVINL double wave_max(double v) { v = grp16_max(v); return fmax(fmax(rl(v, 0), rl(v, 16)), fmax(rl(v, 32), rl(v, 48))); }
-DEVINL double wave_min(double v) { v = grp16_min(v); return fmin(fmin(rl(v, 0), rl(v, 16)), fmin(rl(v, 32), rl(v, 48))); }
-// exchange between the four 16-lane rows with the gfx950 lane-swap instructions (see qp_solver.hip)
-struct RowPair { double a, b; };
-DEVINL RowPair rows_xor16(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  return {__hiloint2double(h[0], l[0]), __hiloint2double(h[1], l[1])};
-}
-DEVINL RowPair rows_xor32(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return {__hiloint2double(h[0], l[0]), __hiloint2double(h[1], l[1])};
-}
-DEVINL double q_sum(double v) {  // sum over the 4 lane groups (same l&15); every lane gets the total
-  RowPair r = rows_xor16(v); v = r.a + r.b;
-  r = rows_xor32(v); return r.a + r.b;
-}
+// Whole-wave reductions of this kernel (all 64 lanes active at the call): the zero-filling DPP chain within the four rows, then four
+// scalar lane reads -- not the lane-swap forms of qp_lane.h, hence the names.
+DEVINL double wave_sum_rl(double v) { v = grp16_sum_zf(v); return (rl(v, 0) + rl(v, 16)) + (rl(v, 32) + rl(v, 48)); }
+DEVINL double wave_max_rl(double v) { v = grp16_max_zf(v); return fmax(fmax(rl(v, 0), rl(v, 16)), fmax(rl(v, 32), rl(v, 48))); }
+DEVINL double wave_min_rl(double v) { v = grp16_min_zf(v); return fmin(fmin(rl(v, 0), rl(v, 16)), fmin(rl(v, 32), rl(v, 48))); }
 
 // LDS n-vectors (np doubles each).  R1, R2 and the NB border-column vectors MB are contiguous: they are the
 // right-hand-side columns 0..NB+1 of the factorisation.  Behind them: NB border columns of H~ (constant) and four
@@ -333,7 +300,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       }
     }
   }
-  red_put(0, wave_sum((double)cnt_local)); red_put(1, wave_max((double)infeas_l));
+  red_put(0, wave_sum_rl((double)cnt_local)); red_put(1, wave_max_rl((double)infeas_l));
   __syncthreads();
   const double cnt = fmax(1.0, red_sum(0));
   const int infeas = red_max(1) > 0;
@@ -402,7 +369,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
             double dsum = 0.0;
 #pragma unroll
             for (int t = 0; t < T; ++t) dsum = fma(bq[t][h], v[t], dsum);
-            dsum = grp16_sum(dsum);
+            dsum = grp16_sum_zf(dsum);
 #pragma unroll
             for (int f = 0; f < NB; ++f) dsum = fma(AB_(f, rix + h), vb[f], dsum);
             if (c == ((s0 + h) & 15)) keep = dsum;
@@ -469,7 +436,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
         double colsum = 0.0;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-          const double rs = grp16_sum(h[p] * zc);                            // row 16I + q + 4p of H_IJ z_J
+          const double rs = grp16_sum_zf(h[p] * zc);                         // row 16I + q + 4p of H_IJ z_J
           if (c == 0) slds[oPB + w * np + 16 * I + q + 4 * p] += rs;
           colsum = fma(h[p], slds[oZ + 16 * I + q + 4 * p], colsum);
         }
@@ -497,7 +464,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       for (int e = 0; e < NB; ++e) {
         double sb = 0.0;
         for (int i = lane; i < n; i += 64) sb = fma(HB_(e, i), slds[oZ + i], sb);
-        sb = wave_sum(sb);
+        sb = wave_sum_rl(sb);
         if (lane == 0) slds[VEC(V_HX) + nc + e] = sb;
       }
     }
@@ -648,14 +615,14 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       const v4d Ukk = row[0];
       double y[4];
 #pragma unroll
-      for (int p = 0; p < 4; ++p) y[p] = grp16_sum(Yt[p] * tk);                       // y_K[q+4p] = sum_c Y[q+4p][c] t[c]
+      for (int p = 0; p < 4; ++p) y[p] = grp16_sum_zf(Yt[p] * tk);                    // y_K[q+4p] = sum_c Y[q+4p][c] t[c]
       {
         double r = 0.0;
 #pragma unroll
         for (int p = 0; p < 4; ++p) r = fma(Ukk[p], y[p], r);
         r = tk - q_sum(r);                                                             // t - U_KK' y  (by column)
 #pragma unroll
-        for (int p = 0; p < 4; ++p) y[p] += grp16_sum(Yt[p] * r);
+        for (int p = 0; p < 4; ++p) y[p] += grp16_sum_zf(Yt[p] * r);
       }
       WAVE_SYNC();                                                                     // every lane has read its t[c] of block K
       if (c == 0) {
@@ -702,14 +669,14 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       double s2 = 0.0;
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
-        wv[p] = slds[oV + 16 * K + q + 4 * p] - (K < T - 1 ? grp16_sum(sp[p]) : 0.0);
+        wv[p] = slds[oV + 16 * K + q + 4 * p] - (K < T - 1 ? grp16_sum_zf(sp[p]) : 0.0);
         s2 = fma(Yt[p], wv[p], s2);
       }
       x[K] = q_sum(s2);                                                                // (U_KK^-T)' w
       {
         double dcor = 0.0;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) dcor = fma(Yt[p], wv[p] - grp16_sum(Ukk[p] * x[K]), dcor);
+        for (int p = 0; p < 4; ++p) dcor = fma(Yt[p], wv[p] - grp16_sum_zf(Ukk[p] * x[K]), dcor);
         x[K] += q_sum(dcor);
       }
       WAVE_SYNC();                                                                     // every lane has read its y[q+4p] of block K
@@ -727,7 +694,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       for (int e = 0; e < NB; ++e) {
         double dsum = 0.0;
         for (int i = lane; i < nc; i += 64) dsum = fma(MB_(e, i), slds[oR + i], dsum);
-        double tt = slds[oR + nc + e] - wave_sum(dsum);
+        double tt = slds[oR + nc + e] - wave_sum_rl(dsum);
 #pragma unroll
         for (int g2 = 0; g2 < e; ++g2) tt -= UBB_(g2, e) * yb[g2];
         yb[e] = tt / UBB_(e, e);
@@ -779,7 +746,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
         }
       }
     }
-    red_put(0, wave_max(dmax_l));
+    red_put(0, wave_max_rl(dmax_l));
     __syncthreads();
     const double dmax = red_max(0);
     red_next();
@@ -851,7 +818,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
           for (int f = e; f < NB; ++f) {
             double dsum = 0.0;
             for (int i = lane; i < nc; i += 64) dsum = fma(MB_(e, i), MB_(f, i), dsum);
-            S[e][f] = MB_(e, nc + f) - wave_sum(dsum);
+            S[e][f] = MB_(e, nc + f) - wave_sum_rl(dsum);
           }
 #pragma unroll
         for (int e = 0; e < NB; ++e) {
@@ -927,7 +894,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
         for (int e = 0; e < NB; ++e) { sm[k_] = fma(w1, ab[e], sm[k_]); ++k_; sm[k_] = fma(w2, ab[e], sm[k_]); ++k_; sm[k_] = fma(w3, ab[e], sm[k_]); ++k_; }
       }
 #pragma unroll
-      for (int k_ = 0; k_ < NSUM; ++k_) { const double t_ = wave_sum(sm[k_]); if (lane == 0) slds[oScr + w * 96 + k_] = t_; }
+      for (int k_ = 0; k_ < NSUM; ++k_) { const double t_ = wave_sum_rl(sm[k_]); if (lane == 0) slds[oScr + w * 96 + k_] = t_; }
     }
     {
       // Lane and wave id are re-made at the places that use them (two v_mbcnt / one s_mov, opaque to the compiler), and the stream
@@ -1129,7 +1096,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
     if (it == 0) {
       double s_gap = 0, m_rp = 0;
       for (int js = w; js < JT; js += W) row_weights(js, ld_row(js * 64 + lane), s_gap, m_rp);
-      red_put(0, wave_sum(s_gap)); red_put(1, wave_max(m_rp));
+      red_put(0, wave_sum_rl(s_gap)); red_put(1, wave_max_rl(m_rp));
       __syncthreads();
       gap = red_sum(0); rp_rel = red_max(1);
       red_next();
@@ -1150,8 +1117,8 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       const double sc = fmax(1.0, fmax(fabs(G_(i)), fmax(fabs(HX_(i)), fabs(gz))));
       m_rd = fmax(m_rd, fabs(HX_(i) + G_(i) - gz) / sc);
     }
-    const double fval = wave_sum(fl);
-    const double rd_rel = wave_max(m_rd);
+    const double fval = wave_sum_rl(fl);
+    const double rd_rel = wave_max_rl(m_rd);
     const double gap_rel = gap / fmax(1.0, fabs(fval));
     // (fmax drops NaN operands: an iterate with NaN in it -- a step along a direction from a broken-down factorisation, 0 * NaN --
     //  would read as merit 0.  Its objective is NaN, and so must the merit be: the best saved iterate is returned then.)
@@ -1184,7 +1151,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
           }
         }
       }
-      red_put(0, wave_sum(dgap_l)); red_put(1, wave_max(m_rd2_l));
+      red_put(0, wave_sum_rl(dgap_l)); red_put(1, wave_max_rl(m_rd2_l));
       __syncthreads();
       const double merit2 = fmax(red_max(1), fmax(rp_rel, (gap + red_sum(0)) / fmax(1.0, fabs(fval))));
       red_next();
@@ -1258,7 +1225,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
     if (res_ok) {  // Newton-decrement test in the caller's coordinates
       double dm = 0, xm = 1.0;
       for (int i = lane; i < n; i += 64) { dm = fmax(dm, fabs(R1_(i) * EV_(i))); xm = fmax(xm, fabs(X_(i) * EV_(i))); }
-      dm = wave_max(dm); xm = wave_max(xm);
+      dm = wave_max_rl(dm); xm = wave_max_rl(xm);
       if (dm <= P.tol_x * xm) { flag = 0; break; }
     }
     if (it >= P.max_iter) { flag = have_saved ? 2 : 1; break; }
@@ -1292,7 +1259,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
               double ds0 = 0.0, ds1 = 0.0;
 #pragma unroll
               for (int t = 0; t < T; ++t) { ds0 = fma(bq[t][h], v[0][t], ds0); ds1 = fma(bq[t][h], v[1][t], ds1); }
-              ds0 = grp16_sum(ds0); ds1 = grp16_sum(ds1);
+              ds0 = grp16_sum_zf(ds0); ds1 = grp16_sum_zf(ds1);
 #pragma unroll
               for (int f = 0; f < NB; ++f) { const double a_ = AB_(f, rix + h); ds0 = fma(a_, vb[0][f], ds0); ds1 = fma(a_, vb[1][f], ds1); }
               if (c == ((s0 + h) & 15)) { ka = ds0; kc = ds1; }
@@ -1343,7 +1310,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       }
       if (js >= J) { const int i = (js - J) * 64 + lane; if (i < np) W1V_(i) = wv; }   // (A rows: fused in pass 2)
     }
-    red_put(0, wave_min(a_aff)); red_put(1, wave_sum(s1)); red_put(2, wave_sum(s2));
+    red_put(0, wave_min_rl(a_aff)); red_put(1, wave_sum_rl(s1)); red_put(2, wave_sum_rl(s2));
     __syncthreads();
     a_aff = red_min(0); s1 = red_sum(1); s2 = red_sum(2);
     red_next();
@@ -1401,13 +1368,13 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       }
     }
     {
-      const double amax_w = wave_min(amax);
+      const double amax_w = wave_min_rl(amax);
       if (amax_w < 1e299) {
         const unsigned long long msk = __ballot(amax == amax_w);
         const int src = __ffsll((long long)msk) - 1;
         bp = rl(bp, src); bdp = rl(bdp, src); bd = rl(bd, src); bdd = rl(bdd, src);
       }
-      red_put(0, amax_w); red_put(1, bp); red_put(2, bdp); red_put(3, bd); red_put(4, bdd); red_put(5, wave_sum(q1)); red_put(6, wave_sum(q2));
+      red_put(0, amax_w); red_put(1, bp); red_put(2, bdp); red_put(3, bd); red_put(4, bdd); red_put(5, wave_sum_rl(q1)); red_put(6, wave_sum_rl(q2));
     }
     __syncthreads();
     double alpha = 1.0;
@@ -1459,7 +1426,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
     // full direction dx = dxa + smu*dxc + dxcor (R1, R2, DX are stable since the last barrier)
     for (int i = tid; i < n; i += NTH) { const double xv = X_(i) + alpha * (R1_(i) + smu * R2_(i) + DX_(i)); X_(i) = xv; xn = fmax(xn, fabs(xv)); }
     const double rp_prev = rp_rel;
-    red_put(0, wave_sum(s_gap)); red_put(1, wave_max(m_rp)); red_put(2, wave_max(xn)); red_put(3, wave_max(zn));
+    red_put(0, wave_sum_rl(s_gap)); red_put(1, wave_max_rl(m_rp)); red_put(2, wave_max_rl(xn)); red_put(3, wave_max_rl(zn));
     __syncthreads();
     gap = red_sum(0); rp_rel = red_max(1); xn = red_max(2); zn = red_max(3);
     red_next();
@@ -1537,7 +1504,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
             double dsum = 0.0;
 #pragma unroll
             for (int t = 0; t < T; ++t) dsum = fma(bq[t][h], v[t], dsum);
-            dsum = grp16_sum(dsum);
+            dsum = grp16_sum_zf(dsum);
 #pragma unroll
             for (int f = 0; f < NB; ++f) dsum = fma(AB_(f, rix + h), vb[f], dsum);
             const double pen = c0[h] * (dsum - c1[h]);
@@ -1607,7 +1574,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
         const double cc_ = PA[ix] != 0.0 ? QV[ix] - PB[ix] : 0.0;
         PC[ix] = cc_; PP[ix] = -cc_; rs_l = fma(cc_, cc_, rs_l);
       }
-      red_put(0, wave_sum(rs_l));
+      red_put(0, wave_sum_rl(rs_l));
       for (int i = tid; i < np; i += NTH) { const double a_ = -P2_(i) * rinv; R1_(i) = a_; P3_(i) = a_; }   // ATR, ATP
       __syncthreads();
       double rs = red_sum(0);
@@ -1620,7 +1587,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
           m_eq = fmax(m_eq, fabs(pc_) / fmax(1.0, fabs(PB[ix])));
           m_cy = fmax(m_cy, fabs(pc_ * PY[ix]));
         }
-        red_put(0, wave_max(m_eq)); red_put(1, wave_max(m_cy));
+        red_put(0, wave_max_rl(m_eq)); red_put(1, wave_max_rl(m_cy));
         __syncthreads();
         m_eq = red_max(0); m_cy = red_max(1);
         red_next();
@@ -1632,7 +1599,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
         pass_fused(VEC(V_DX), 1);                     // QV = A~w; P2 = rho A_W'(A_W w)
         double pq_l = 0.0;
         for (int js = w; js < J; js += W) { const int ix = js * 64 + lane; if (PA[ix] != 0.0) pq_l = fma(PP[ix], QV[ix], pq_l); }
-        red_put(0, wave_sum(pq_l));
+        red_put(0, wave_sum_rl(pq_l));
         __syncthreads();
         const double pq = red_sum(0);
         red_next();
@@ -1641,7 +1608,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
           if (attempt < QP_REFINE_ATTEMPTS - 1) {
             double my = 0.0; int myix = -1;
             for (int js = w; js < J; js += W) { const int ix = js * 64 + lane; if (PA[ix] != 0.0 && fabs(PP[ix]) > my) { my = fabs(PP[ix]); myix = ix; } }
-            red_put(0, wave_max(my));
+            red_put(0, wave_max_rl(my));
             __syncthreads();
             const double mx = red_max(0);
             red_next();
@@ -1662,7 +1629,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
             PC[ix] = cc_; rsn_l = fma(cc_, cc_, rsn_l);
           }
         }
-        red_put(0, wave_sum(rsn_l));
+        red_put(0, wave_sum_rl(rsn_l));
         __syncthreads();
         const double rsn = red_sum(0);
         red_next();
@@ -1711,7 +1678,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
             fl2 += 0.0 * (v + y);
           }
         }
-        red_put(0, wave_max(m_rd)); red_put(1, wave_max(m_rp)); red_put(2, wave_max(m_sg)); red_put(3, wave_max(m_cp)); red_put(4, wave_sum(fl2));
+        red_put(0, wave_max_rl(m_rd)); red_put(1, wave_max_rl(m_rp)); red_put(2, wave_max_rl(m_sg)); red_put(3, wave_max_rl(m_cp)); red_put(4, wave_sum_rl(fl2));
         __syncthreads();
         m_rd = red_max(0); m_rp = red_max(1); m_sg = red_max(2); m_cp = red_max(3);
         const double f2 = red_sum(4);
@@ -1745,7 +1712,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
               if (sg > my) { my = sg; myix = ix; myside = 0.0; }
             }
           }
-          red_put(0, wave_max(my));
+          red_put(0, wave_max_rl(my));
           __syncthreads();
           const double mx = red_max(0);
           red_next();
@@ -1802,7 +1769,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
     hx_keep(VEC(V_X));
     double fl = 0;
     for (int i = lane; i < n; i += 64) fl += 0.5 * X_(i) * HX_(i) + G_(i) * X_(i);
-    fval_s = wave_sum(fl);
+    fval_s = wave_sum_rl(fl);
   }
   STAMP(14);
   STAMP_OUT;
@@ -1851,11 +1818,7 @@ template <int T> static hipError_t launch_wg_sel(const QpParams& P, int batch, h
 }
 #define QP_WG_CAT2(a, b) a##b
 #define QP_WG_CAT(a, b) QP_WG_CAT2(a, b)
-#ifdef QP_WG_ONE_TU
-hipError_t qp_wg_launch_1(const QpParams& P, int batch, hipStream_t st) { return launch_wg_sel<1>(P, batch, st); }
-#else
 #ifndef QP_WG_SYM
 #define QP_WG_SYM QP_WG_TLO
 #endif
 hipError_t QP_WG_CAT(qp_wg_launch_, QP_WG_SYM)(const QpParams& P, int batch, hipStream_t st) { return launch_wg_sel<1>(P, batch, st); }
-#endif

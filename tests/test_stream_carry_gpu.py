@@ -1,6 +1,6 @@
-"""The operand stream of the one-wavefront solve kernel (csrc/qp_solver.hip, `Stream`): one object per kernel invocation, its
-producer state lives across the passes (restarted per pass in the shipped build, carried and wrapped at the end of A~ under
--DQP_STREAM_CARRY).  What can go wrong is a record read before it has landed, or a consumer that finds another record than the one
+"""The operand stream of the one-wavefront solve kernel (csrc/qp_solve_kernel.h, `Stream`): one object per kernel invocation, its
+producer state lives across the passes and is restarted at the top of each (a producer carried across passes and wrapped at the end
+of A~ was measured and removed: profiles/stream_carry/README.md).  What can go wrong is a record read before it has landed, or a consumer that finds another record than the one
 it expects at its slot.  Either shows up as wrong numbers (against the CPU oracle), as run-to-run differences (two solves of one
 batch in one process) or as a dependence on the neighbours (the batch in reversed order).  Shapes:
   * kinematic N = 2, 3, 4: fewer records than the lead of the stream (a carried producer wraps several times per pass);
