@@ -210,7 +210,9 @@ static void apply_Gt(const qp_work* w, const double* y, double* out) { /* out = 
  *      [ G_W   0  ] [y] = [ b_W ]
  * by dense LU with partial pivoting, followed by single add / drop corrections of the working set (add the most violated
  * inactive side, else drop the multiplier of the wrong sign) until the point is a KKT point of the full QP -- the vertex
- * an active-set solver such as qpOASES stops at.  Returns 1 and overwrites (x, lambda) on success. */
+ * an active-set solver such as qpOASES stops at.  A candidate that passes is accepted only if orc_qp_kkt() of it, all four
+ * residuals, is <= POLISH_ACCEPT.  Returns 1 and overwrites (x, lambda) on success. */
+#define POLISH_ACCEPT 1e-8
 static int polish(int n, int m, const double* H, const double* g, const double* A,
                   const double* lb, const double* ub, const double* lbA, const double* ubA,
                   double inf_bound, double* x, double* lambda) {
@@ -220,7 +222,8 @@ static int polish(int n, int m, const double* H, const double* g, const double* 
   int* act = (int*)malloc(sizeof(int) * mt);
   double* v = (double*)calloc(mt, sizeof(double));
   double* xs = (double*)malloc(sizeof(double) * n);
-  int ok = 0;
+  double* lcand = (double*)malloc(sizeof(double) * mt);
+  int ok = 0, rejected = 0;
   for (int i = 0; i < n; ++i) v[i] = x[i];
   for (int j = 0; j < n; ++j) for (int r = 0; r < m; ++r) v[n + r] += A[IDX(r, j, m)] * x[j];
   for (int i = 0; i < mt; ++i) {
@@ -268,20 +271,31 @@ static int polish(int n, int m, const double* H, const double* g, const double* 
         if (sg > worst_s) { worst_s = sg; is = act[a]; }
       }
       if (worst_v <= ftol && worst_s <= stol) {
-        for (int i = 0; i < n; ++i) x[i] = xs[i];
-        for (int i = 0; i < mt; ++i) lambda[i] = 0;
+        /* feasibility and multiplier signs say nothing about stationarity: the LU solution of a working set with (nearly)
+         * dependent rows can be far from a KKT point.  Evaluate the candidate afresh -- the caller's coordinates, the clipped
+         * multipliers that would be returned -- and accept it at the level the HIP refinement accepts at; otherwise the
+         * refinement ends here and the interior-point iterate stays */
+        for (int i = 0; i < mt; ++i) lcand[i] = 0;
         for (int a = 0; a < na; ++a) {
           const double y = r[n + a];
-          lambda[act[a]] = side[act[a]] > 0 ? fmax(y, 0.0) : fmin(y, 0.0);
+          lcand[act[a]] = side[act[a]] > 0 ? fmax(y, 0.0) : fmin(y, 0.0);
         }
-        ok = 1;
+        int fin = 1;   /* (orc_qp_kkt takes its maxima with fmax, which drops a NaN) */
+        for (int i = 0; i < n; ++i) fin &= isfinite(xs[i]) != 0;
+        for (int i = 0; i < mt; ++i) fin &= isfinite(lcand[i]) != 0;
+        const double cert = fin ? orc_qp_kkt(n, m, H, g, A, lb, ub, lbA, ubA, xs, lcand, inf_bound, 0) : INFINITY;
+        if (cert <= POLISH_ACCEPT) {
+          for (int i = 0; i < n; ++i) x[i] = xs[i];
+          for (int i = 0; i < mt; ++i) lambda[i] = lcand[i];
+          ok = 1;
+        } else rejected = 1;
       } else if (worst_v > ftol && iv >= 0) side[iv] = sv;
       else if (is >= 0) side[is] = 0;
     }
     free(KK); free(r);
-    if (sing) break;
+    if (sing || rejected) break;
   }
-  free(side); free(act); free(v); free(xs);
+  free(side); free(act); free(v); free(xs); free(lcand);
   return ok;
 }
 
