@@ -45,6 +45,16 @@ COMMON := $(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o $(LIBDIR)/sqp.o $(
 $(LIBDIR)/libfsaempc.so: $(QPOBJ) $(WGOBJ) $(COMMON)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
+# development: qp_solver.hip as ONE unit for a single tile count (EXP_T) with extra flags (EXP_FLAGS: -DQP_STAMPS=1, -DQP_PROBE, ...)
+# through the checked pipeline, linked with the shipped objects of everything else -> libfsaempc_$(EXP_NAME).so (FSAEMPC_LIB selects
+# it).  tools/build_exp.sh is the front end.  Always rebuilt: the flags are not part of the target's name.
+EXP_T ?= 5
+EXP_FLAGS ?=
+EXP_NAME ?= exp
+exp: $(WGOBJ) $(COMMON)
+	$(CC_CHECKED) $(LIBDIR)/$(EXP_NAME)_qp_solver.o $(CSRC)/qp_solver.hip $(filter-out -Wall,$(HIPFLAGS)) -DQP_ONLY_T=$(EXP_T) $(EXP_FLAGS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/libfsaempc_$(EXP_NAME).so $(LIBDIR)/$(EXP_NAME)_qp_solver.o $(WGOBJ) $(COMMON)
+
 # development builds of the workgroup kernel: ONE instantiation (T = 8 + slack border: BASELINE configs[2], dynamic N = 60) linked with the
 # shipped objects of everything else; plain and with phase stamps.  Select with FSAEMPC_LIB.
 WGDEVFLAGS := $(WGFLAGS) -DQP_WG_TLO=8 -DQP_WG_THI=8 -DQP_WG_ONLY_NB=4
@@ -100,4 +110,4 @@ oracle:
 clean:
 	rm -rf $(LIBDIR)/*.o $(LIBDIR)/*.so $(LIBDIR)/*.isa.log $(LIBDIR)/*.s
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean o1 wgdev dbg isa-report
+.PHONY: all oracle clean o1 wgdev dbg isa-report exp

@@ -1129,6 +1129,16 @@ int fsaempc_selftest_diag_factor(void) {
   return bad;
 }
 
+int fsaempc_selftest_initial_point(void) {
+  int cnt = 0;
+  hipError_t e = hipGetDeviceCount(&cnt);
+  if (e != hipSuccess || cnt == 0) return fail(FSAEMPC_ERR_NODEVICE, "no HIP device");
+  char msg[256] = "";
+  int bad = qp_selftest_initial_point(msg, sizeof(msg));
+  if (bad != 0) snprintf(g_err, sizeof(g_err), "%s", msg);
+  return bad;
+}
+
 int fsaempc_debug_set_dump(double* out, int stage) { g_dump.store(out); g_dump_stage.store(stage); return 0; }
 
 int fsaempc_qp_set_timing(int enable) {

@@ -1,5 +1,5 @@
 // qp_selftest.h -- device self tests of the QP kernels' building blocks (main unit of qp_solver.hip only): fp64 MFMA lane maps, the
-// lane reductions of qp_lane.h, the forms of diag_factor.  Kernels and their host entry points.
+// lane reductions of qp_lane.h, the forms of diag_factor, the start-up pass.  Kernels and their host entry points.
 #pragma once
 #include <stdlib.h>
 #include <stdio.h>
@@ -163,6 +163,62 @@ __global__ __launch_bounds__(64) void diag_factor_selftest_kernel(const double* 
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Initial-point self test: one wave on one QP that qp_prep_kernel has prepared.  aV = A~ x and P3 = A~'w of the initial multipliers
+// are computed the former way (pass_Av<.., 1, 0>, then pass_Atw) and by the start-up pass of the solve kernel (pass_Av<.., 1, -1>);
+// both vectors must agree bit for bit (also where they are NaN).  out: {mismatches, first kind (0: aV, 1: P3), index, lane, nonzeros}.
+// ---------------------------------------------------------------------------------------------
+template <int T, int NB> __global__ __launch_bounds__(64) void initial_point_selftest_kernel(QpParams P, int* __restrict__ out) {
+  extern __shared__ double lds[];
+  Ctx k;
+  (void)ctx_setup<T>(k, P, 0, lds);
+  const QpSolveLds L = qp_solve_lds(T, NB, P.d.np);
+  k.ring = lds + L.vecs + L.border + L.tiles;
+  k.cof = k.ring + L.ring;
+  const int lane = k.lane, J = k.J, JT = k.JT;
+  double* Xv = vecp(k, V_X); double* P3o = vecp(k, V_P1); double* P3n = vecp(k, V_P3);
+  double* W3 = rowp(k, R_W3); double* Vo = rowp(k, R_VA); double* Vn = rowp(k, R_V);
+  const double* Lb = rowp(k, R_L); const double* Ub = rowp(k, R_U);
+  Stream<T> st;
+  st.open(k);
+  for (int js = 0; js < JT; ++js) {   // the weights as the solve kernel sets them: by the finiteness of the bounds; x inside its bounds
+    const int ix = js * 64 + lane;
+    const bool valid = row_valid(k, js);
+    const double l = Lb[ix], u = Ub[ix];
+    W3[ix] = (valid && js < J) ? ((l > -INFINITY ? 100.0 : 0.0) - (u < INFINITY ? 100.0 : 0.0)) : 0.0;
+    if (js >= J) {
+      const int i = (js - J) * 64 + lane;
+      if (i < k.np) {
+        double xi = i < k.n ? 0.375 * ((i * 7) % 5 - 2) + 0.01 * i : 0.0;
+        if (valid) { if (l > -INFINITY && xi < l) xi = l; if (u < INFINITY && xi > u) xi = u; }
+        Xv[i] = xi;
+      }
+    }
+  }
+  WAVE_SYNC();
+  const double* vin[1] = {Xv};
+  { double* rout[1] = {Vo}; pass_Av<T, NB, 1, 0>(k, st, vin, rout, nullptr); }
+  pass_Atw<T, NB>(k, W3, P3o);
+  WAVE_SYNC();
+  { double* rout[1] = {Vn}; pass_Av<T, NB, 1, -1>(k, st, vin, rout, P3n); }
+  WAVE_SYNC();
+  st.close();
+  int bad = 0, kind = -1, at = -1, nz = 0;
+  for (int js = 0; js < J; ++js) {
+    const int ix = js * 64 + lane;
+    if (!same_bits(Vo[ix], Vn[ix])) { if (!bad) { kind = 0; at = ix; } ++bad; }
+    nz += Vo[ix] != 0.0;
+  }
+  for (int i = lane; i < k.nc + NB; i += 64) {
+    if (!same_bits(P3o[i], P3n[i])) { if (!bad) { kind = 1; at = i; } ++bad; }
+    nz += P3o[i] != 0.0;
+  }
+  if (nz) atomicAdd(&out[4], nz);
+  if (bad) {
+    if (atomicAdd(&out[0], bad) == 0) { out[1] = kind; out[2] = at; out[3] = lane; }
+  }
+}
+
 }  // namespace
 
 int qp_selftest_mfma(char* msg, int msglen) {
@@ -266,4 +322,99 @@ int qp_selftest_diag_factor(char* msg, int msglen) {
   if (e != hipSuccess) { snprintf(msg, msglen, "diag_factor selftest: %s", hipGetErrorString(e)); return -1; }
   if (hout[0]) snprintf(msg, msglen, "diag_factor forms: %d mismatches with the former form, first: tile %d form %d lane %d", hout[0], hout[1], hout[2], hout[3]);
   return hout[0];
+}
+
+// One shape of the initial-point self test: a QP with staircase sparsity (row r reaches the core columns up to its own stage, so the
+// tile count of the trips varies; the border columns are dense), infinite, one-sided, two-sided and equality bounds.
+template <int T, int NB> static hipError_t initial_point_launch(const QpParams& P, int* dout) {
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&initial_point_selftest_kernel<T, NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.d.lds_solve);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((initial_point_selftest_kernel<T, NB>), dim3(1), dim3(64), P.d.lds_solve, 0, P, dout);
+  return hipGetLastError();
+}
+static int initial_point_shape(int nV, int nC, char* msg, int msglen) {
+  QpDims d;
+  qp_make_dims(nV, nC, &d);
+  const int nb = d.nb, ncu = nV - nb;   // the caller's core columns
+  const double inf = 1e20;
+  const size_t nH = (size_t)nV * nV, nA = (size_t)nC * nV, nin = nH + nA + 3 * (size_t)nV + 2 * (size_t)nC;
+  double* h = (double*)calloc(nin, sizeof(double));
+  if (!h) return -1;
+  double *H = h, *A = H + nH, *g = A + nA, *lb = g + nV, *ub = lb + nV, *lbA = ub + nV, *ubA = lbA + nC;
+  unsigned long long st = 0xA0761D6478BD642Full + (unsigned)nV * 1000003u + (unsigned)nC;   // fixed seed per shape
+  auto rnd = [&]() { st = st * 6364136223846793005ull + 1442695040888963407ull; return ((unsigned)(st >> 33)) / 2147483648.0; };
+  for (int j = 0; j < nV; ++j) {   // column-major, symmetric, diagonally dominant; a slack column without curvature takes the column-max scale
+    for (int i = 0; i < j; ++i) if ((i + j) % 3 == 0) { const double v = 0.1 * (rnd() - 0.5); H[(size_t)j * nV + i] = v; H[(size_t)i * nV + j] = v; }
+    H[(size_t)j * nV + j] = (nb > 0 && j == nV - 1) ? 0.0 : 1.0 + 3.0 * rnd();
+    g[j] = 2.0 * rnd() - 1.0;
+  }
+  for (int r = 0; r < nC; ++r) {
+    const int reach = ncu > 0 ? 1 + (int)(((long long)(r + 1) * ncu) / nC) : 0;   // staircase: the last core column of the row
+    for (int j = 0; j < ncu && j < reach; ++j) if ((r + j) % 4 != 1) A[(size_t)j * nC + r] = 4.0 * rnd() - 2.0;
+    for (int j = ncu; j < nV; ++j) A[(size_t)j * nC + r] = -1.0 + 0.5 * rnd();
+    const double mid = rnd() - 0.5;
+    switch (r % 5) {
+      case 0: lbA[r] = mid - 1.0; ubA[r] = mid + 1.0; break;
+      case 1: lbA[r] = mid; ubA[r] = 1e30; break;       // lower side only
+      case 2: lbA[r] = -1e30; ubA[r] = mid; break;      // upper side only
+      case 3: lbA[r] = mid; ubA[r] = mid; break;        // equality
+      default: lbA[r] = -1e30; ubA[r] = 1e30; break;    // free row
+    }
+  }
+  for (int j = 0; j < nV; ++j) {
+    switch (j % 4) {
+      case 0: lb[j] = -1.0; ub[j] = 1.0; break;
+      case 1: lb[j] = 0.25; ub[j] = 1e30; break;
+      case 2: lb[j] = -1e30; ub[j] = -0.125; break;
+      default: lb[j] = -1e30; ub[j] = 1e30; break;
+    }
+  }
+  double *din = 0, *ws = 0; int* dout = 0; int hout[5] = {0, 0, 0, 0, 0};
+  hipError_t e = hipMalloc(&din, sizeof(double) * nin);
+  if (e == hipSuccess) e = hipMalloc(&ws, sizeof(double) * d.ws_per_qp);
+  if (e == hipSuccess) e = hipMalloc(&dout, sizeof(hout));
+  if (e == hipSuccess) e = hipMemcpy(din, h, sizeof(double) * nin, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(ws, 0, sizeof(double) * d.ws_per_qp);
+  if (e == hipSuccess) e = hipMemset(dout, 0, sizeof(hout));
+  free(h);
+  if (e == hipSuccess) {
+    QpParams P = {};
+    P.d = d;
+    P.H = din; P.A = din + nH; P.g = P.A + nA; P.lb = P.g + nV; P.ub = P.lb + nV; P.lbA = P.ub + nV; P.ubA = P.lbA + nC;
+    P.ws = ws; P.inf_bound = inf;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qp_prep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)d.lds_prep);
+    if (e == hipSuccess) { hipLaunchKernelGGL(qp_prep_kernel, dim3(1), dim3(256), d.lds_prep, 0, P); e = hipGetLastError(); }
+    if (e == hipSuccess) {
+      if (d.T == 1 && d.NB == 4) e = initial_point_launch<1, 4>(P, dout);
+      else if (d.T == 2 && d.NB == 4) e = initial_point_launch<2, 4>(P, dout);
+      else if (d.T == 2 && d.NB == 0) e = initial_point_launch<2, 0>(P, dout);
+      else if (d.T == 2 && d.NB == 1) e = initial_point_launch<2, 1>(P, dout);
+      else if (d.T == 5 && d.NB == 1) e = initial_point_launch<5, 1>(P, dout);
+      else { snprintf(msg, msglen, "initial-point selftest: shape (%d, %d) has T = %d, NB = %d, which the self test does not instantiate (FSAEMPC_SLACK_BORDER set?)", nV, nC, d.T, d.NB); e = hipErrorInvalidValue; }
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(hout, dout, sizeof(hout), hipMemcpyDeviceToHost);
+  }
+  if (din) (void)hipFree(din);
+  if (ws) (void)hipFree(ws);
+  if (dout) (void)hipFree(dout);
+  if (e != hipSuccess) { if (!msg[0]) snprintf(msg, msglen, "initial-point selftest (%d, %d): %s", nV, nC, hipGetErrorString(e)); return -1; }
+  if (hout[0]) { snprintf(msg, msglen, "initial point (%d, %d): %d mismatches between the start-up pass and pass_Av + pass_Atw, first: %s index %d lane %d", nV, nC, hout[0], hout[1] ? "P3" : "aV", hout[2], hout[3]); return hout[0]; }
+  if (!hout[4]) { snprintf(msg, msglen, "initial point (%d, %d): both ways gave all zeros, nothing was compared", nV, nC); return 1; }
+  return 0;
+}
+
+int qp_selftest_initial_point(char* msg, int msglen) {
+  // (nV, nC): T = 1 with a four-column border and one padded trip; T = 2 with three border columns and padded k-steps in the last trip;
+  // no border; a core padded with dummy variables (one slack column); the headline instantiation
+  const int shapes[5][2] = {{20, 5}, {35, 70}, {32, 64}, {25, 72}, {81, 240}};
+  int bad = 0;
+  msg[0] = 0;
+  for (int i = 0; i < 5; ++i) {
+    const int rc = initial_point_shape(shapes[i][0], shapes[i][1], msg, msglen);
+    if (rc < 0) return rc;
+    bad += rc;
+    if (rc) break;
+  }
+  return bad;
 }

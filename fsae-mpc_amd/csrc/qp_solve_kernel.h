@@ -20,6 +20,10 @@
 #ifndef QP_SYRK_INTERLEAVE
 #define QP_SYRK_INTERLEAVE 0
 #endif
+// 1: the former start-up, v = G x and A~'w of the initial multipliers as two passes (A/B and stamp builds: profiles/startup/README.md)
+#ifndef QP_STARTUP_ATW
+#define QP_STARTUP_ATW 0
+#endif
 
 namespace {
 
@@ -350,14 +354,17 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, Stream<T>& st, v4d*
 // direction; as soon as a row's va = a_r' dxa is reduced, the second-order weight
 //   w_r = (va+a1)(b1 + c1 (va+a1)) - (a2-va)(b2 + c2 (a2-va))      (a,b,c: per-row coefficients of row phase 1)
 // is formed and p_cor += w_r a_r is accumulated in the same pass (saves one full stream over A per iteration).
-// FUSE 3 is the polish step (see the kernel).  Same operand stream and phase structure as pass 1.
+// FUSE 3 is the polish step (see the kernel).  FUSE -1 is the start-up pass: beside y it accumulates Pcor = A~' w for the row array
+// R_W3 (the initial multipliers), with the FMAs of a lane in the order of pass_Atw below, so the initial point costs one pass over
+// A~ instead of two.  Same operand stream and phase structure as pass 1.
 template <int T, int NB, int NVEC, int FUSE> DEVINL void pass_Av(const Ctx& k, Stream<T>& st, const double* const* vin, double* const* rout, double* Pcor, double* Pcor2 = nullptr, const double* const* cfarr = nullptr) {
   constexpr int NBB = NB > 0 ? NB : 1;
-  constexpr int NC = FUSE == 1 ? 6 : (FUSE >= 2 ? 3 : 0);   // per-row coefficient arrays of the fused part
+  constexpr int NC = FUSE == 1 ? 6 : (FUSE >= 2 ? 3 : (FUSE == -1 ? 1 : 0));   // per-row coefficient arrays of the fused part
   constexpr int NA = NC + NB;
   const int JS = k.J * 64;
   const double* arr[NA > 0 ? NA : 1];
   if (FUSE == 1) { arr[0] = rowp(k, R_RPL); arr[1] = rowp(k, R_CB1); arr[2] = rowp(k, R_CC1); arr[3] = rowp(k, R_RPU); arr[4] = rowp(k, R_CB2); arr[5] = rowp(k, R_CC2); }
+  if (FUSE == -1) arr[0] = rowp(k, R_W3);
   if (FUSE >= 2) { arr[0] = cfarr ? cfarr[0] : rowp(k, R_CB1); arr[1] = cfarr ? cfarr[1] : rowp(k, R_RPL); arr[2] = cfarr ? cfarr[2] : rowp(k, R_CC1); }   // refinement: rho*act, target b, multiplier y
 #pragma unroll
   for (int f = 0; f < NB; ++f) arr[NC + f] = k.Ab + (size_t)f * JS;
@@ -431,6 +438,13 @@ template <int T, int NB, int NVEC, int FUSE> DEVINL void pass_Av(const Ctx& k, S
 #pragma unroll
               for (int f = 0; f < NB; ++f) pcb[f] = fma(w, cf[NC + f][h], pcb[f]);
             }
+            if (FUSE == -1 && e == 0) {
+              const double w = cf[0][h];
+#pragma unroll
+              for (int t = 0; t < C; ++t) pc[t] = fma(w, b[t][h], pc[t]);
+#pragma unroll
+              for (int f = 0; f < NB; ++f) pcb[f] = fma(w, cf[NC + f][h], pcb[f]);
+            }
           }
           if (cc == 15 || s + 1 == 4 * k.ntr) {
             const int js = s >> 4;
@@ -471,7 +485,8 @@ template <int T, int NB, int NVEC, int FUSE> DEVINL void pass_Av(const Ctx& k, S
   }
 }
 
-// p = A~' w (w: owner-layout row array) -> LDS n-vector (only used by the initial point)
+// p = A~' w (w: owner-layout row array) -> LDS n-vector.  The kernel no longer calls it (the start-up pass, pass_Av with FUSE -1,
+// produces the same bits); it stays as the reference of fsaempc_selftest_initial_point().
 template <int T, int NB> DEVINL void pass_Atw(const Ctx& k, const double* W, double* Pout) {
   constexpr int NBB = NB > 0 ? NB : 1;
   const int JS = k.J * 64;
@@ -824,13 +839,22 @@ template <int T> DEVINL void vec_rows_load(const Ctx& k, const double* V, double
 #ifndef QP_STAMPS
 #define QP_STAMPS 0
 #endif
+// QP_STAMPS=2 splits the start-up instead of the loop: ids 2, 3, 4 = the v = G x pass, the row initialisation, hx_full; id 0 keeps
+// what follows them (the former pass_Atw, the multiplier fix-up) and id 1 takes the whole iteration loop and the epilogue.
+#if QP_STAMPS >= 2
+#define STAMP(id) STAMP_AT(((id) >= 1) ? 1 : 0)
+#define STAMP_SETUP(id) STAMP_AT(id)
+#else
+#define STAMP(id) STAMP_AT(id)
+#define STAMP_SETUP(id) do { } while (0)
+#endif
 #if QP_STAMPS
 #define STAMP_DECL unsigned long long st_acc[16]; for (int i_ = 0; i_ < 16; ++i_) st_acc[i_] = 0; unsigned long long st_t0 = __builtin_amdgcn_s_memtime();
-#define STAMP(id) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[id] += t_ - st_t0; st_t0 = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#define STAMP_AT(id) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[id] += t_ - st_t0; st_t0 = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
 #define STAMP_OUT do { if (P.dump && P.dump_stage == 9 && lane == 0) for (int i_ = 0; i_ < 16; ++i_) P.dump[(size_t)b * 16 + i_] = (double)st_acc[i_]; } while (0)
 #else
 #define STAMP_DECL
-#define STAMP(id) do { } while (0)
+#define STAMP_AT(id) do { } while (0)
 #define STAMP_OUT do { } while (0)
 #endif
 
@@ -925,6 +949,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
   st.open(k);
 
   // ---- load n-vectors, initial x = clamp(0, l, u) (scaled), count finite sides ----
+  const double T0 = 10.0, Z0 = 100.0;   // initial slacks / multipliers (below)
   for (int i = lane; i < k.np; i += 64) { G[i] = gw[i]; EV[i] = Es[i]; R1[i] = 0; R2[i] = 0; DX[i] = 0; }
   int cnt_local = 0, infeas = 0;
   for (int js = 0; js < JT; ++js) {
@@ -941,6 +966,8 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
       }
       cnt_local += (l > -INFINITY) + (u < INFINITY);
     }
+    // the multipliers of the initial point, z = Z0 on every finite side: the weights of the A~'w that rides on the v = G x pass
+    aW3[ix] = (valid && js < J) ? ((l > -INFINITY ? Z0 : 0.0) - (u < INFINITY ? Z0 : 0.0)) : 0.0;
     if (js >= J) {
       const int i = (js - J) * 64 + lane;
       if (i < k.np) {
@@ -961,15 +988,19 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
   if (infeas) { flag = -2; }
   if (ws[d.off_bad] != 0.0) flag = -1;   // NaN / Inf in this QP's data (found by the prep kernel): -1 after 0 iterations, x = clamp(0, lb, ub)
 
-  // ---- v = G x ----
+  // ---- v = G x, and P3 = A~'(zl - zu) of the initial multipliers in the same pass ----
   {
     const double* vin[1] = {X}; double* rout[1] = {aV};
+#if QP_STARTUP_ATW
     pass_Av<T, NB, 1, 0>(k, st, vin, rout, nullptr);
+#else
+    pass_Av<T, NB, 1, -1>(k, st, vin, rout, P3);
+#endif
     for (int jb = 0; jb < k.JB; ++jb) { const int i = jb * 64 + lane; aV[(J + jb) * 64 + lane] = i < n ? X[i] : 0.0; }
   }
   // ---- initial slacks / multipliers in the equilibrated problem: t = max(resid, T0), z = Z0 (a scan over the
   //      synthetic LTV-MPC families: (10,100) needs 8-16 % fewer iterations than (1,1)) ----
-  const double T0 = 10.0, Z0 = 100.0;
+  STAMP_SETUP(2);
   for (int js = 0; js < JT; ++js) {
     const int ix = js * 64 + lane;
     const bool valid = row_valid(k, js);
@@ -979,13 +1010,16 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     aTU[ix] = hu ? fmax(u - v, T0) : 1.0;
     aZL[ix] = hl ? Z0 : 0.0;
     aZU[ix] = hu ? Z0 : 0.0;
-    aW3[ix] = (js < J) ? ((hl ? Z0 : 0.0) - (hu ? Z0 : 0.0)) : 0.0;
   }
   WAVE_SYNC();
+  STAMP_SETUP(3);
   // bound multipliers absorb the initial dual residual r = Hx + g - A'(zl - zu)
   {
     hx_full(X);
+    STAMP_SETUP(4);
+#if QP_STARTUP_ATW   // (A/B and stamp builds of the former start-up: a pass of its own for A~'w)
     pass_Atw<T, NB>(k, aW3, P3);
+#endif
     WAVE_SYNC();
     for (int jb = 0; jb < k.JB; ++jb) {
       const int i = jb * 64 + lane, ix = (J + jb) * 64 + lane;

@@ -73,6 +73,7 @@ hipError_t qp_launch(const QpParams& P, int batch, hipStream_t st, hipEvent_t ev
 int qp_selftest_mfma(char* msg, int msglen);
 int qp_selftest_lane_reduce(char* msg, int msglen);   // DPP / lane-swap reductions against zero-filling moves and an LDS tree
 int qp_selftest_diag_factor(char* msg, int msglen);   // diag_factor: the newer forms against the former one on 64 tiles, bit for bit
+int qp_selftest_initial_point(char* msg, int msglen); // start-up pass of the solve kernel against pass_Av + pass_Atw on five prepared QPs, bit for bit
 // LDS of the one-wavefront solve kernel (qp_solve_kernel.h): the sizes, in doubles, of its regions in their order -- QP_SOLVE_NVEC
 // n-vectors of np | one vector per border column (at least one) | T resident tiles U_KK^-T of 272 | operand ring, QP_SOLVE_RING(T)
 // records of 128 | coefficient staging, (6 + NB) arrays of 64.  The kernel carves its LDS with this, qp_make_dims sizes the launch.

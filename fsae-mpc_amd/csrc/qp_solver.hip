@@ -46,12 +46,21 @@
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// qp_prep_kernel: scaling (E columns, F rows), repack of A and H, scaled g / bounds.  One wave per QP.
+// qp_prep_kernel: scaling (E columns, F rows), repack of A and H, scaled g / bounds.  One workgroup per QP.
 // ---------------------------------------------------------------------------------------------
+// -DQP_PREP_STAMPS: diagnostic build; lane 0 of every workgroup leaves the cycles of its phases in the dump buffer (stage 10, eight
+// doubles per QP: column scale, row pass, sort, trips, rows / bounds, A repack, H repack, tail).  tools/prep_phase_profile.py prints them.
+#ifdef QP_PREP_STAMPS
+#define PSTAMP(id) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pst[id] += t_ - pst_t0; pst_t0 = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define PSTAMP(id) do { } while (0)
+#endif
 __global__ __launch_bounds__(1024) void qp_prep_kernel(QpParams P) {
-  // one workgroup per QP: 256 threads for small row counts, 1024 for large ones (qp_launch_prep) -- the staging tile allows one
-  // workgroup per CU there, and with four wavefronts the dependent LDS -> global chains of the repack ran at a tenth of the
-  // memory rate (11 ms of a 145 ms dynamic N = 60 batch)
+  // one workgroup per QP: 256 threads up to 512 rows, 1024 above (qp_launch, prep_thr) -- the staging tile allows one workgroup per
+  // CU at the large shapes, and with four wavefronts the dependent LDS -> global chains of the repack ran at a tenth of the memory
+  // rate (11 ms of a 145 ms dynamic N = 60 batch).  Up to about 500 rows two or more 256-thread workgroups share a CU and beat one
+  // of 1024 threads (profiles/startup/prep_threads_sweep.txt: 288 rows 0.80 vs 1.13 ms per 4096, 500 rows 0.89 vs 0.96, 600 rows
+  // 1.96 vs 1.20)
   const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, c = lane & 15, q = lane >> 4;
   const int NTH = blockDim.x, NW = NTH >> 6;
   const QpDims& d = P.d;
@@ -91,6 +100,9 @@ __global__ __launch_bounds__(1024) void qp_prep_kernel(QpParams P) {
   int* aoff_sh = tcs_sh + ntr;
   int* chc_sh = aoff_sh + ntr + 1;                                   // [ceil(m/64)][16] rows of each class per 64-row chunk, then their starts
   double* Fr_sh = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(chc_sh + ((m + 63) >> 6) * 16) + 7) & ~(uintptr_t)7);   // [m] row scale of every original row
+#ifdef QP_PREP_STAMPS
+  unsigned long long pst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pst_t0 = __builtin_amdgcn_s_memtime();
+#endif
 
   // ---- column scaling E_j = 1/sqrt(H_jj), or 1/max|A_:j| where H_jj ~ 0 (slack columns) ----
   for (int j = tid; j < np; j += NTH) {
@@ -118,6 +130,7 @@ __global__ __launch_bounds__(1024) void qp_prep_kernel(QpParams P) {
                  // reference's MEX gateway rejects such a call; a device entry cannot look at the data before the launch)
   for (int j = tid; j < np; j += NTH) { const int uj = j < n ? U(j) : -1; const double gj = uj >= 0 ? g[uj] : 0.0; Es[j] = Esh[j]; gw[j] = gj * Esh[j]; bad |= !(fabs(gj) < INFINITY); }
 
+  PSTAMP(0);
   // ---- one pass over A, thread = row (coalesced: consecutive threads read consecutive rows of a column, the loads of a thread are
   //      independent): row scaling F_r = 1 / max_j |A[r][j] E_j| and the row's class = last core column tile with a nonzero.
   //      (Round 2 scanned every row twice with dependent / uncoalesced loads and ranked the rows with an O(m^2) loop: 14 ms of
@@ -156,6 +169,7 @@ __global__ __launch_bounds__(1024) void qp_prep_kernel(QpParams P) {
     }
   }
   __syncthreads();
+  PSTAMP(1);
   if (tid < T) {   // per class: running start of every chunk (after the total of the lower classes is known: two steps)
     int tot = 0;
     for (int ch = 0; ch < nchunk; ++ch) tot += chc_sh[ch * 16 + tid];
@@ -178,6 +192,7 @@ __global__ __launch_bounds__(1024) void qp_prep_kernel(QpParams P) {
     }
   }
   __syncthreads();
+  PSTAMP(2);
   // tiles per trip (16 sorted positions), stream offsets, phase ends
   for (int tr = tid; tr < ntr; tr += NTH) {
     int tc = 1;
@@ -193,6 +208,7 @@ __global__ __launch_bounds__(1024) void qp_prep_kernel(QpParams P) {
   }
   __syncthreads();
   for (int tr = tid; tr <= ntr; tr += NTH) { aoff_g[tr] = aoff_sh[tr]; if (tr < ntr) tcs_g[tr] = tcs_sh[tr]; }
+  PSTAMP(3);
 
   // ---- row scaling F_r = 1/max_j |A[r][j] E_j| ; rows handled in owner layout, one slot per wavefront and trip ----
   int nexcl = 0;   // rows / bounds that exclude x = 0: the difficulty estimate behind the launch order (QpParams::order)
@@ -203,11 +219,15 @@ __global__ __launch_bounds__(1024) void qp_prep_kernel(QpParams P) {
     const double f = valid ? Fr_sh[r] : 0.0;
     Fs[js * 64 + lane] = f;
     perm_g[js * 64 + lane] = r;
+    double ab[4], lr = 0.0, ur = 0.0;   // (the slot's loads -- border columns, bounds -- are issued together, ahead of the stores)
+#pragma unroll
+    for (int bb = 0; bb < 4; ++bb) ab[bb] = (valid && bb < nb) ? Aat(r, nc + bb) : 0.0;
+    if (valid) { lr = P.lbA[(size_t)b * m + r]; ur = P.ubA[(size_t)b * m + r]; }
+#pragma unroll
     for (int bb = 0; bb < 4; ++bb)
-    { const double v = (valid && bb < nb) ? Aat(r, nc + bb) * Esh[nc + bb] * f : 0.0; bad |= !(fabs(v) < INFINITY); Ab[(size_t)bb * J * 64 + js * 64 + lane] = v; }
+    { const double v = (valid && bb < nb) ? ab[bb] * Esh[nc + bb] * f : 0.0; bad |= !(fabs(v) < INFINITY); Ab[(size_t)bb * J * 64 + js * 64 + lane] = v; }
     double l = -INFINITY, u = INFINITY;
     if (valid) {
-      double lr = P.lbA[(size_t)b * m + r], ur = P.ubA[(size_t)b * m + r];
       bad |= (lr != lr) || (ur != ur);
       nexcl += (lr > 0.0) || (ur < 0.0);
       l = lr > -P.inf_bound ? lr * f : -INFINITY;
@@ -231,46 +251,94 @@ __global__ __launch_bounds__(1024) void qp_prep_kernel(QpParams P) {
     Ur[(J + jb) * 64 + lane] = u;
   }
   __syncthreads();  // Fs visible to the whole workgroup (global memory, same CU)
+  PSTAMP(4);
 
   // ---- A -> operand stream.  Column tile by column tile: coalesced column reads -> LDS -> lane order ----
   const int R4 = 4 * Kq, mp1 = R4 + 1;  // padded LDS row length (odd => conflict-free across the 16 columns)
+  const int RCH = (R4 + 63) >> 6, NIT = TW * RCH;   // staging items: (staged column, run of 64 rows), one wavefront each
   for (int t = 0; t < T; ++t)
     for (int c0 = 0; c0 < 16; c0 += TW) {
-      for (int e = tid; e < TW * R4; e += NTH) {
-        const int cc = e / R4, r = e - cc * R4;
-        const int col = 16 * t + c0 + cc;
-        double v = 0.0;
-        if (col < nc && col < n && r < m) v = Aat(r, col) * Esh[col];
-        bad |= !(fabs(v) < INFINITY);
-        tile[cc * mp1 + r] = v;
+      // (eight items of loads in flight per wavefront, a wavefront reads 64 consecutive rows of one column: with one load per trip
+      //  and a division per element this loop ran at one memory latency per 8 bytes and lane)
+      for (int i0 = w; i0 < NIT; i0 += 8 * NW) {
+        double av[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int i = i0 + u * NW, cc = i / RCH, r = (i - cc * RCH) * 64 + lane, col = 16 * t + c0 + cc;
+          av[u] = (i < NIT && col < nc && col < n && r < m) ? Aat(r, col) : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int i = i0 + u * NW, cc = i / RCH, r = (i - cc * RCH) * 64 + lane, col = 16 * t + c0 + cc;
+          if (i < NIT && r < R4) {
+            double v = 0.0;
+            if (col < nc && col < n && r < m) v = av[u] * Esh[col];
+            bad |= !(fabs(v) < INFINITY);
+            tile[cc * mp1 + r] = v;
+          }
+        }
       }
       __syncthreads();
-      for (int s = w; s < 4 * ntr; s += NW) {   // k-steps are stored in pairs (16 B per lane and load); padded positions carry zeros
-        const int tr = s >> 2, tc = tcs_sh[tr];
-        if (t < tc && c >= c0 && c < c0 + TW) {
-          const int r = perm_sh[4 * s + q];
-          const double v = r >= 0 ? tile[(c - c0) * mp1 + r] * Fr_sh[r] : 0.0;   // (row scale from LDS: the owner-layout copy in global memory cost a load latency per k-step)
-          Aw[((size_t)aoff_sh[tr] + ((s >> 1) & 1) * tc + t) * 128 + lane * 2 + (s & 1)] = v;
+      // k-steps are stored in pairs (16 B per lane and load): a lane writes both k-steps of a pair as one 16-byte store, a
+      // wavefront a whole 1 KB record (TW = 16); padded positions carry zeros.  Four pairs per trip of the loop: their LDS reads
+      // are independent and go ahead of the stores.
+      for (int sp0 = w; sp0 < 2 * ntr; sp0 += 4 * NW) {
+        int r0[4], r1[4]; bool on[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int sp = sp0 + u * NW;
+          on[u] = sp < 2 * ntr && t < tcs_sh[sp < 2 * ntr ? sp >> 1 : 0] && c >= c0 && c < c0 + TW;
+          r0[u] = on[u] ? perm_sh[8 * sp + q] : -1; r1[u] = on[u] ? perm_sh[8 * sp + 4 + q] : -1;
+        }
+        v2d v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {   // (row scale from LDS: the owner-layout copy in global memory cost a load latency per k-step)
+          v[u][0] = r0[u] >= 0 ? tile[(c - c0) * mp1 + r0[u]] * Fr_sh[r0[u]] : 0.0;
+          v[u][1] = r1[u] >= 0 ? tile[(c - c0) * mp1 + r1[u]] * Fr_sh[r1[u]] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int sp = sp0 + u * NW;
+          if (on[u]) { const int tr = sp >> 1, tc = tcs_sh[tr]; *reinterpret_cast<v2d*>(Aw + ((size_t)aoff_sh[tr] + (sp & 1) * tc + t) * 128 + lane * 2) = v[u]; }
         }
       }
       __syncthreads();
     }
+  PSTAMP(5);
 
-  // ---- H -> accumulator-layout tiles (T x T grid of the core; symmetric read for coalescing) ----
-  for (int idx = w; idx < T * T * 4; idx += NW) {
-    const int p = idx & 3, IJ = idx >> 2, I = IJ / T, Jt = IJ - I * T;
-    const int row = 16 * I + q + 4 * p, col = 16 * Jt + c;
-    double v = 0.0;
-    if (row < nc && col < nc && row < n && col < n) v = Hat(col, row) * Esh[row] * Esh[col];  // H[col][row] == H[row][col]
-    bad |= !(fabs(v) < INFINITY);
-    Hw[(size_t)idx * 64 + lane] = v;
+  // ---- H -> accumulator-layout tiles (T x T grid of the core; symmetric read for coalescing); eight tiles of loads in flight ----
+  for (int i0 = w; i0 < T * T * 4; i0 += 8 * NW) {
+    double hv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int idx = i0 + u * NW, p = idx & 3, IJ = idx >> 2, I = IJ / T, Jt = IJ - I * T;
+      const int row = 16 * I + q + 4 * p, col = 16 * Jt + c;
+      hv[u] = (idx < T * T * 4 && row < nc && col < nc && row < n && col < n) ? Hat(col, row) : 0.0;  // H[col][row] == H[row][col]
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int idx = i0 + u * NW, p = idx & 3, IJ = idx >> 2, I = IJ / T, Jt = IJ - I * T;
+      const int row = 16 * I + q + 4 * p, col = 16 * Jt + c;
+      if (idx < T * T * 4) {
+        double v = 0.0;
+        if (row < nc && col < nc && row < n && col < n) v = hv[u] * Esh[row] * Esh[col];
+        bad |= !(fabs(v) < INFINITY);
+        Hw[(size_t)idx * 64 + lane] = v;
+      }
+    }
   }
-  for (int e = tid; e < 4 * np; e += NTH) {
-    const int bb = e / np, i = e - bb * np;
-    const double v = (bb < nb && i < n) ? Hat(i, nc + bb) * Esh[nc + bb] * Esh[i] : 0.0;
-    bad |= !(fabs(v) < INFINITY);
-    Hb[e] = v;
+  for (int i = tid; i < np; i += NTH) {   // the four border columns of an index together
+    double hv[4];
+#pragma unroll
+    for (int bb = 0; bb < 4; ++bb) hv[bb] = (bb < nb && i < n) ? Hat(i, nc + bb) : 0.0;
+#pragma unroll
+    for (int bb = 0; bb < 4; ++bb) {
+      const double v = (bb < nb && i < n) ? hv[bb] * Esh[nc + bb] * Esh[i] : 0.0;
+      bad |= !(fabs(v) < INFINITY);
+      Hb[bb * np + i] = v;
+    }
   }
+  PSTAMP(6);
   bad = __syncthreads_or(bad);
   if (tid == 0) ws[d.off_bad] = bad ? 1.0 : 0.0;
   if (P.score) {
@@ -281,6 +349,10 @@ __global__ __launch_bounds__(1024) void qp_prep_kernel(QpParams P) {
     __syncthreads();
     if (tid == 0) P.score[b] = P.score_in ? P.score_in[b] : score_sh;
   }
+#ifdef QP_PREP_STAMPS
+  PSTAMP(7);
+  if (P.dump && P.dump_stage == 10 && tid == 0) for (int i = 0; i < 8; ++i) P.dump[(size_t)b * 8 + i] = (double)pst[i];
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -501,7 +573,7 @@ static hipError_t qp_wg_launch(const QpParams& P, int batch, hipStream_t st) {
   }
   return hipErrorInvalidValue;
 }
-static int prep_thr() { static const char* e = getenv("FSAEMPC_PREP_THR"); return e ? atoi(e) : 256; }   // (A/B runs)
+static int prep_thr() { static const char* e = getenv("FSAEMPC_PREP_THR"); return e ? atoi(e) : 512; }   // rows up to which the prep kernel runs on 256 threads (the variable: A/B runs)
 hipError_t qp_launch(const QpParams& P, int batch, hipStream_t st, hipEvent_t ev_mid) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qp_prep_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.d.lds_prep);

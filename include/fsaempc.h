@@ -683,6 +683,11 @@ int fsaempc_selftest_lane_reduce(void);
  * numbers 1..1e10, a pivot under the floor, a NaN, +Inf) through the former form of diag_factor and through the newer ones; the
  * factor, both companion tiles and the flag are compared bit for bit.  Returns 0 if all agree, >0 number of mismatches, <0 without a device. */
 int fsaempc_selftest_diag_factor(void);
+/* Runs the on-device self-test of the solve kernel's start-up pass on five small QPs with staircase sparsity and infinite, one-sided
+ * and equality bounds, (nV, nC) = (20, 5), (35, 70), (32, 64), (25, 72), (81, 240), prepared by the real prep kernel: A~x and A~'w of
+ * the initial multipliers from the one fused pass against a pass of its own for each, bit for bit.  Returns 0 if all agree, >0 number of
+ * mismatches, <0 without a device. */
+int fsaempc_selftest_initial_point(void);
 /* Debug hook of the diagnostic builds only (libfsaempc_dbg.so, -DQP_DEBUG_DUMP; the shipped kernels carry no dump
  * branches and ignore it): dumps solver internals of instance 0 after `stage` (see qp_solver.hip) into `out` (device
  * pointer, >= 4*nV*nV+8*(nV+nC) doubles).  Process-global, not thread-safe. */

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-phase cycle shares of qp_solve_kernel from the diagnostic build (bash tools/build_exp.sh 5 -DQP_STAMPS=1; FSAEMPC_QP_V1=1 selects the phase names of the one-wavefront kernel).
+"""Per-phase cycle shares of qp_solve_kernel from the diagnostic build (bash tools/build_exp.sh 5 -DQP_STAMPS=1; FSAEMPC_QP_V1=1 selects the phase names of the one-wavefront kernel;
+-DQP_STAMPS=2 with FSAEMPC_STAMPS=2: the pieces of the start-up).
 Never quote this build's run time: read the SHARES."""
 import ctypes as C
 import os
@@ -14,8 +15,10 @@ import torch  # noqa: E402
 import fsae_mpc_amd as fm  # noqa: E402
 
 NAMES_V1 = ["setup", "row1", "hx", "syrk", "resid+toLDS", "chol", "solve2", "passAv2", "row2", "passAtw", "solve1", "passAv1", "row3+update", "epilogue"]
+# -DQP_STAMPS=2 splits the start-up instead of the loop (FSAEMPC_STAMPS=2 selects these names); add -DQP_STARTUP_ATW=1 for the former start-up
+NAMES_V1_STARTUP = ["Atw pass (former start-up only) + multiplier fix-up", "iteration loop + epilogue", "v = Gx pass (+ A'w)", "row initialisation", "hx_full"]
 NAMES_WG = ["setup", "row1", "hx", "acc_init+syrk", "resid+rhs", "diag add+dmax", "chol (K loop)", "border+backward", "pass2 (fused)", "row2", "corrector solve", "pass3", "row3a+alpha", "update sweep", "epilogue + refinement", "(of syrk: per-trip wait + barrier)"]
-NAMES = NAMES_V1 if os.environ.get("FSAEMPC_QP_V1") else NAMES_WG
+NAMES = (NAMES_V1_STARTUP if os.environ.get("FSAEMPC_STAMPS") == "2" else NAMES_V1) if os.environ.get("FSAEMPC_QP_V1") else NAMES_WG
 
 
 def main():
