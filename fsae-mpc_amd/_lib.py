@@ -27,6 +27,7 @@ EXPORTS = [
     "fsaempc_plan_profile_batch_device", "fsaempc_plan_reference_batch_device", "fsaempc_cl_pre_plan_batch_device",
     "fsaempc_raceline_build_qp_device", "fsaempc_plan_line_profile_batch_device", "fsaempc_plan_raceline_workspace_bytes",
     "fsaempc_plan_raceline_batch_device",
+    "fsaempc_cl_metrics_batch_device", "fsaempc_cl_report",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -35,6 +36,18 @@ PARAM_INDEX = {name: i for i, name in enumerate(
     ["M", "IZ", "LF", "LR", "GRAV", "PB", "PC", "PD", "PE", "Q_S", "Q_N", "Q_MU", "Q_TERMINAL", "R_ACC", "R_STEER",
      "R_SOFT0", "R_SOFT1", "R_SOFT2", "R_SOFT3", "U_ACC_MAX", "U_STEER_MAX", "DELTA_MAX", "N_MAX", "V_MIN", "ALAT_MAX", "SLIP_MAX",
      "ELL_LONG", "ELL_LAT", "PID_KP_V", "PID_MAX_F", "PID_KP_D", "PID_MAX_DRATE"])}
+
+# per-car records of the lap report (include/fsaempc.h FSAEMPC_M_*) and its batch summary (FSAEMPC_R_*); tests check both tables
+# against the header's macros
+NMETRIC = 16
+METRIC_INDEX = {name: i for i, name in enumerate(
+    ["STEPS", "STATUS", "N_VIOL_INT", "N_VIOL_MAX", "N_ABS_MAX", "ABNORMAL", "OBJ_SUM", "OBJ_CNT", "SLACK_N_CNT", "SLACK_TYRE_CNT",
+     "ELL_VIOL_INT", "ELL_VIOL_MAX", "ITER_SUM", "ITER_MAX", "S_START", "S_LAST"])}
+NREPORT = 20
+REPORT_INDEX = {name: i for i, name in enumerate(
+    ["CARS_DRIVING", "CARS_FINISHED", "CARS_LOST", "LAP_MEAN", "LAP_MIN", "LAP_MAX", "STEPS", "ABNORMAL_PCT", "SLACK_N_PCT", "SLACK_TYRE_PCT",
+     "OBJ_MEAN", "N_VIOL_INT_MEAN", "N_VIOL_INT_MAX", "N_VIOL_MAX", "ELL_VIOL_INT_MEAN", "ELL_VIOL_INT_MAX", "ELL_VIOL_MAX", "ITER_MEAN",
+     "ITER_MAX", "N_ABS_MAX"])}
 
 
 class QpOpts(C.Structure):
@@ -214,6 +227,8 @@ def lib():
         L.fsaempc_plan_raceline_workspace_bytes.argtypes = [C.c_int, C.c_int]
         L.fsaempc_plan_raceline_batch_device.argtypes = [C.c_int, C.POINTER(Spline), C.c_double, C.POINTER(LtvParams), C.c_int, C.c_int, C.c_int,
                                                          C.c_double, C.c_double, C.c_double, C.POINTER(QpOpts), vp, vp, vp, vp, vp, ll, vp]
+        L.fsaempc_cl_metrics_batch_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(LtvParams)] + [vp] * 10
+        L.fsaempc_cl_report.argtypes = [vp, C.c_int, C.c_double, vp]
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p
         L.fsaempc_track_from_csv.argtypes = [C.c_char_p, C.c_int, C.POINTER(TrackTable)]

@@ -4,9 +4,28 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import ParamBlock, Spline, check, check_blocking, lib
+from ._lib import METRIC_INDEX, NMETRIC, NREPORT, REPORT_INDEX, ParamBlock, Spline, check, check_blocking, lib
 from .ltvmpc import LtvBatch, dims
 from .plan import Plan
+
+
+class LapReport:
+    """The per-car records of a closed-loop run (include/fsaempc.h FSAEMPC_M_*; main.m:196-228 per car) on the host.  Every slot is an
+    attribute by its lower-case name (steps, status, n_viol_int, ...), one entry per car; lap_time = steps * dt (a lap only for
+    the cars with status == 1).  summary() is the batch summary of fsaempc_cl_report as a dict (lower-case FSAEMPC_R_* names)."""
+
+    def __init__(self, metrics, dt):
+        self.metrics = np.ascontiguousarray(np.asarray(metrics, dtype=np.float64).reshape(-1, NMETRIC))
+        self.dt = float(dt)
+        for name, i in METRIC_INDEX.items():
+            setattr(self, name.lower(), self.metrics[:, i])
+        self.lap_time = self.steps * self.dt
+
+    def summary(self):
+        out = np.zeros(NREPORT)
+        check(lib().fsaempc_cl_report(C.c_void_p(self.metrics.ctypes.data), self.metrics.shape[0], C.c_double(self.dt), C.c_void_p(out.ctypes.data)),
+              "fsaempc_cl_report")
+        return {name.lower(): float(out[i]) for name, i in REPORT_INDEX.items()}
 
 
 class ClosedLoop:
@@ -16,12 +35,16 @@ class ClosedLoop:
     plan -- and the exit flags are only tallied.  Cars that completed the lap (s >= L) or left the track keep their state."""
 
     def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
-                 params=None, plant_params=None, blocking=None, reference=None):
+                 params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6):
         """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
         None = the same as params (both None: the reference's constants compiled into the kernels).  blocking: block lengths of the
         controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2).  reference: None = the live
         generator of main.m:107-114 (a ramp to target_vel); a Plan = main.m:115, the cars track it (shared, or one table per car;
-        target_vel is then unused)."""
+        target_vel is then unused).  metrics: keep the lap report's per-car records (self.metrics, (B, 16) on the device; one more
+        kernel per step, on the same stream; limits and ellipse axes are those of params) -- report() reads them back.  slack_tol: a slack
+        counts as in use above it (the reference tests == 0; 1e-6 is this build's solve tolerance)."""
+        if not (float(slack_tol) >= 0):
+            raise ValueError("slack_tol must be >= 0")
         if blocking is not None:
             check_blocking(blocking, N)   # (before the library is touched)
         if reference is not None:
@@ -58,6 +81,8 @@ class ClosedLoop:
         self.x_ref = torch.empty((self.B, N, self.nx), dtype=torch.float64, device=self.device)
         self.u_last = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)
         self.steps = 0
+        self.slack_tol = float(slack_tol)
+        self.metrics = torch.zeros((self.B, NMETRIC), dtype=torch.float64, device=self.device) if metrics else None
         # warm_start: every solve starts from the plan of the previous period shifted by one stage (fsaempc_qp_aux.x_init): the
         # inputs u_1..u_{N-1}, the last stage repeated, the previous slack values.  Off by default -- the reference's loop solves
         # cold (main.m:117-120 passes no initial guess) and the gain is modest (profiles/round3/warm_start_ab.json)
@@ -123,15 +148,29 @@ class ClosedLoop:
         check(lib().fsaempc_cl_accept_batch_device(self.model, self.N, self.B, P(out["x_opt"]), P(out["u_opt"]), P(out["exitflag"]), P(self.x_opt), P(self.u_opt),
                                                    self._stream(stream)), "fsaempc_cl_accept_batch_device")
         self.plant(None, stream)
+        if self.metrics is not None:
+            check(lib().fsaempc_cl_metrics_batch_device(self.model, self.N, C.c_double(self.dt), C.c_double(self.slack_tol), self.B,
+                                                        self.mpc.params.ref() if self.mpc.params is not None else None, P(self.x0), P(self.finished),
+                                                        P(out["exitflag"]), P(out["iter"]), P(out["fval"]), P(out["slack"]), P(self.u_opt), P(self.cart),
+                                                        P(self.metrics), self._stream(stream)), "fsaempc_cl_metrics_batch_device")
         self.steps += 1
         return out
 
+    def report(self):
+        """The lap report so far (LapReport): one read-back of self.metrics."""
+        if self.metrics is None:
+            raise ValueError("ClosedLoop(metrics=True) keeps the records report() reads")
+        return LapReport(self.metrics.cpu().numpy(), self.dt)
 
-def monte_carlo_carts(track, B, seed):
+
+def monte_carlo_carts(track, B, seed, lap=False):
     """Initial Cartesian states of BASELINE configs[3]: s0 = u*L, lateral +-0.5 m, heading +-0.1 rad,
-    speed U[0,15]; numpy PCG64(seed).  Returns (cart (B,7), s0 (B,))."""
+    speed U[0,15]; numpy PCG64(seed).  lap: every car at s = 0 and at rest instead (main.m:63 starts from zeros(7,1)), same lateral and
+    heading scatter.  Returns (cart (B,7), s0 (B,))."""
     rng = np.random.default_rng(seed)
     s = rng.uniform(0, track.L, B); n = rng.uniform(-0.5, 0.5, B); dth = rng.uniform(-0.1, 0.1, B); v = rng.uniform(0, 15, B)
+    if lap:
+        s = np.zeros(B); v = np.zeros(B)
 
     def ev(P, t):   # the Bezier table on the host (same formulas as interpolate_spline / interpolate_spline_d); P is M x 4
         r = np.mod(t, track.dl * track.M); i = np.minimum(np.floor(r / track.dl).astype(int), track.M - 1); u = r / track.dl - i; w = 1 - u
@@ -146,15 +185,15 @@ def monte_carlo_carts(track, B, seed):
 
 
 def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
-                plant_params=None, blocking=None, reference=None):
+                plant_params=None, blocking=None, reference=None, metrics=False):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
-    reference: None (the live ramp) or a Plan the cars track (ClosedLoop).
+    reference: None (the live ramp) or a Plan the cars track (ClosedLoop).  metrics: ClosedLoop(metrics=True); cl.report() afterwards.
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
     import torch
     cart0, s_init = monte_carlo_carts(track, B, seed)
     cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
-                    params=params, plant_params=plant_params, blocking=blocking, reference=reference)
+                    params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

@@ -943,8 +943,65 @@ int fsaempc_cl_accept_batch_device(int model, int N, int batch, const double* x_
   return 0;
 }
 
-/* ---- s-domain plans (DESIGN.md 6i) ---- */
 static bool pos_finite(double v) { return v > 0 && v < INFINITY; }
+
+/* ---- lap report ---- */
+int fsaempc_cl_metrics_batch_device(int model, int N, double dt, double slack_tol, int batch, const fsaempc_ltv_params* par,
+                                    const double* x0, const int* finished, const int* exitflag, const int* iter, const double* fval,
+                                    const double* slack, const double* u_drive, const double* cart, double* metrics, void* stream) {
+  if (!x0 || !finished || !exitflag || !iter || !fval || !slack || !u_drive || !cart || !metrics) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (N <= 0 || batch < 0 || !pos_finite(dt)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (!(slack_tol >= 0)) return fail(FSAEMPC_ERR_ARG, "slack_tol must be >= 0");
+  if (batch == 0) return 0;
+  ClMetricsParams P; P.ns = ltv_ns(model); P.N = N; P.batch = batch; P.tyre = model == FSAEMPC_MODEL_DYNAMIC ? 3 : 0;
+  P.dt = dt; P.slack_tol = slack_tol; P.nx = fsaempc_ltv_nx(model); P.x0 = x0; P.finished = finished; P.exitflag = exitflag; P.iter = iter;
+  P.fval = fval; P.slack = slack; P.u_drive = u_drive; P.cart = cart; P.metrics = metrics;
+  hipError_t e = cl_metrics_launch(P, (hipStream_t)stream, par_values(par), par_stride(par));
+  if (e != hipSuccess) return hipfail(e, "cl_metrics_launch");
+  return 0;
+}
+
+// Host.  Every sum runs over the cars in index order.  Means over an empty set are NaN (MATLAB's mean([])).
+int fsaempc_cl_report(const double* metrics_host, int batch, double dt, double* out) {
+  if (!out || (!metrics_host && batch != 0)) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (batch < 0 || !pos_finite(dt)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  double cars[3] = {0, 0, 0}, lap_sum = 0, lap_min = NAN, lap_max = NAN, steps = 0, abn = 0, sl_n = 0, sl_t = 0, obj = 0, obj_cnt = 0;
+  double recorded = 0, nv_sum = 0, nv_big = 0, nv_max = 0, el_sum = 0, el_big = 0, el_max = 0, it_sum = 0, it_max = 0, n_abs = 0;
+  for (int b = 0; b < batch; ++b) {
+    const double* m = metrics_host + (size_t)b * FSAEMPC_NMETRIC;
+    const int st = m[FSAEMPC_M_STATUS] == 1.0 ? 1 : (m[FSAEMPC_M_STATUS] == 2.0 ? 2 : 0);
+    cars[st] += 1;
+    if (st == 1) {
+      const double lap = m[FSAEMPC_M_STEPS] * dt;
+      lap_sum += lap;
+      if (!(lap_min <= lap)) lap_min = lap;
+      if (!(lap_max >= lap)) lap_max = lap;
+    }
+    steps += m[FSAEMPC_M_STEPS]; abn += m[FSAEMPC_M_ABNORMAL]; sl_n += m[FSAEMPC_M_SLACK_N_CNT]; sl_t += m[FSAEMPC_M_SLACK_TYRE_CNT];
+    obj += m[FSAEMPC_M_OBJ_SUM]; obj_cnt += m[FSAEMPC_M_OBJ_CNT]; it_sum += m[FSAEMPC_M_ITER_SUM];
+    if (m[FSAEMPC_M_STEPS] > 0) { recorded += 1; nv_sum += m[FSAEMPC_M_N_VIOL_INT]; el_sum += m[FSAEMPC_M_ELL_VIOL_INT]; }
+    if (m[FSAEMPC_M_N_VIOL_INT] > nv_big) nv_big = m[FSAEMPC_M_N_VIOL_INT];
+    if (m[FSAEMPC_M_N_VIOL_MAX] > nv_max) nv_max = m[FSAEMPC_M_N_VIOL_MAX];
+    if (m[FSAEMPC_M_ELL_VIOL_INT] > el_big) el_big = m[FSAEMPC_M_ELL_VIOL_INT];
+    if (m[FSAEMPC_M_ELL_VIOL_MAX] > el_max) el_max = m[FSAEMPC_M_ELL_VIOL_MAX];
+    if (m[FSAEMPC_M_ITER_MAX] > it_max) it_max = m[FSAEMPC_M_ITER_MAX];
+    if (m[FSAEMPC_M_N_ABS_MAX] > n_abs) n_abs = m[FSAEMPC_M_N_ABS_MAX];
+  }
+  out[FSAEMPC_R_CARS_DRIVING] = cars[0]; out[FSAEMPC_R_CARS_FINISHED] = cars[1]; out[FSAEMPC_R_CARS_LOST] = cars[2];
+  out[FSAEMPC_R_LAP_MEAN] = cars[1] > 0 ? lap_sum / cars[1] : NAN; out[FSAEMPC_R_LAP_MIN] = lap_min; out[FSAEMPC_R_LAP_MAX] = lap_max;
+  out[FSAEMPC_R_STEPS] = steps;
+  out[FSAEMPC_R_ABNORMAL_PCT] = steps > 0 ? abn / steps * 100 : NAN;
+  out[FSAEMPC_R_SLACK_N_PCT] = steps > 0 ? sl_n / steps * 100 : NAN;
+  out[FSAEMPC_R_SLACK_TYRE_PCT] = steps > 0 ? sl_t / steps * 100 : NAN;
+  out[FSAEMPC_R_OBJ_MEAN] = obj_cnt > 0 ? obj / obj_cnt : NAN;
+  out[FSAEMPC_R_N_VIOL_INT_MEAN] = recorded > 0 ? nv_sum / recorded : NAN; out[FSAEMPC_R_N_VIOL_INT_MAX] = nv_big; out[FSAEMPC_R_N_VIOL_MAX] = nv_max;
+  out[FSAEMPC_R_ELL_VIOL_INT_MEAN] = recorded > 0 ? el_sum / recorded : NAN; out[FSAEMPC_R_ELL_VIOL_INT_MAX] = el_big; out[FSAEMPC_R_ELL_VIOL_MAX] = el_max;
+  out[FSAEMPC_R_ITER_MEAN] = steps > 0 ? it_sum / steps : NAN; out[FSAEMPC_R_ITER_MAX] = it_max; out[FSAEMPC_R_N_ABS_MAX] = n_abs;
+  return 0;
+}
+
+/* ---- s-domain plans (DESIGN.md 6i) ---- */
 static int plan_check(const fsaempc_plan* plan, PlanTable* out) {
   if (!plan || !plan->table || !plan->t) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (plan->N_s < 1 || !pos_finite(plan->ds)) return fail(FSAEMPC_ERR_ARG, "bad plan dimensions");

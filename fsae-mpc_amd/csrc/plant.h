@@ -22,6 +22,18 @@ struct ClPlantParams {
   const int* exitflag;     // optional: cars whose step did not solve keep their state
   double* u_last;          // optional batch x 2: actuator rates of the last sub-step
 };
+struct ClMetricsParams {   // lap report (include/fsaempc.h FSAEMPC_M_*): inputs of one MPC period, all per car
+  int ns, N, batch, tyre;  // slack count of the model, horizon, cars, index of the tyre slack (main.m:133; kinematic: 0)
+  double dt, slack_tol;
+  int nx;
+  const double* x0;        // batch x nx (entries 0 = s and 1 = n are read)
+  const int* finished;     // as cl_pre left it
+  const int* exitflag; const int* iter; const double* fval; const double* slack;   // of this period's solve
+  const double* u_drive;   // batch x 2N: the plan the car drives on
+  const double* cart;      // batch x 7, post-plant
+  double* metrics;         // batch x FSAEMPC_NMETRIC, in/out
+};
+hipError_t cl_metrics_launch(const ClMetricsParams& P, hipStream_t st, const double* par = nullptr, int par_stride = 0);
 hipError_t cl_pre_launch(const ClPreParams& P, hipStream_t st);
 // par (optional): parameter blocks (include/fsaempc.h FSAEMPC_P_*), car b reads par + b * par_stride; null: f_cart_dyn.m's own constants
 hipError_t cl_plant_launch(const ClPlantParams& P, hipStream_t st, const double* par = nullptr, int par_stride = 0);

@@ -8,6 +8,7 @@
 //                    (vehicle_models/pid_controller.m:5-18, gains main.m:84-88) driving the Cartesian dynamic bicycle
 //                    (cartesian_dynamic/f_cart_dyn.m:13-54) through the 6-stage scheme of integrate_cart_dyn.m:12-22
 //                    (stage formulas exactly as written there, including the doubled k2 term of k5)
+//   cl_metrics_kernel main.m:196-228 the lap report's figures, accumulated per car after every period (opt-in)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "plant.h"
@@ -149,8 +150,65 @@ __global__ void cl_accept_kernel(int len_x, int len_u, int batch, const double* 
   for (int i = 0; i < len_u; ++i) u_keep[(size_t)b * len_u + i] = u_new[(size_t)b * len_u + i];
 }
 
+// main.m:196-228 per car, one MPC period at a time (include/fsaempc.h FSAEMPC_M_*).  Runs after the plant; `finished` is
+// what cl_pre left.  Every slot is a count, a maximum or a sum in step order, so a record depends only on the car's own history.
+template <class PAR> __global__ void cl_metrics_kernel(ClMetricsParams P, typename PAR::Args pa) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= P.batch) return;
+  PAR p;
+  if constexpr (PAR::RT) {
+    p = par_load(pa.values + (size_t)b * (size_t)pa.stride);
+    if (p.bad) return;
+  }
+  double* m = P.metrics + (size_t)b * FSAEMPC_NMETRIC;
+  if (m[FSAEMPC_M_STATUS] != 0.0) return;                     // latched: later steps touch nothing
+  const int fin = P.finished[b];
+  if (fin == 2) { m[FSAEMPC_M_STATUS] = 2.0; return; }        // lost: x0 is a placeholder
+  const double s = P.x0[(size_t)b * P.nx], an = fabs(P.x0[(size_t)b * P.nx + 1]);
+  if (an > m[FSAEMPC_M_N_ABS_MAX]) m[FSAEMPC_M_N_ABS_MAX] = an;                 // main.m:101: n_list(i) precedes the lap check
+  if (an > p.N_MAX) {                                                           // main.m:204-205
+    const double v = an - p.N_MAX;
+    m[FSAEMPC_M_N_VIOL_INT] += v * P.dt;
+    if (v > m[FSAEMPC_M_N_VIOL_MAX]) m[FSAEMPC_M_N_VIOL_MAX] = v;
+  }
+  if (fin != 0) { m[FSAEMPC_M_STATUS] = 1.0; return; }        // main.m:102-104: the break; i - 1 steps were solved
+  if (m[FSAEMPC_M_STEPS] == 0.0) m[FSAEMPC_M_S_START] = s;
+  m[FSAEMPC_M_S_LAST] = s;
+  m[FSAEMPC_M_STEPS] += 1.0;
+  const int ef = P.exitflag[b];
+  if (ef != 0) m[FSAEMPC_M_ABNORMAL] += 1.0;                                    // main.m:209
+  const double it = (double)P.iter[b];
+  m[FSAEMPC_M_ITER_SUM] += it;
+  if (it > m[FSAEMPC_M_ITER_MAX]) m[FSAEMPC_M_ITER_MAX] = it;
+  const bool use_n = P.slack[(size_t)b * P.ns] > P.slack_tol;                   // main.m:132-133 (NaN: not in use)
+  const bool use_t = P.slack[(size_t)b * P.ns + P.tyre] > P.slack_tol;
+  if (use_n) m[FSAEMPC_M_SLACK_N_CNT] += 1.0;
+  if (use_t) m[FSAEMPC_M_SLACK_TYRE_CNT] += 1.0;
+  if (ef == 0 && !use_n && !use_t) { m[FSAEMPC_M_OBJ_SUM] += P.fval[b]; m[FSAEMPC_M_OBJ_CNT] += 1.0; }   // main.m:198, 210
+  // main.m:180-182, 199: rear lateral force of f_curv_dyn.m:32-53 at the post-plant state, acceleration of the driven plan
+  const double* c = P.cart + (size_t)b * 7;
+  const double x_d = c[3], y_d = c[4], theta_d = c[5];
+  const double x_d_hat = x_d + 5 * exp(-x_d / 5);
+  const double alpha_r = -atan((y_d - p.LR * theta_d) / x_d_hat);
+  const double B = p.PB, C = p.PC, D = p.PD, E = p.PE;
+  const double Fcr = p.FZR * D * sin(C * atan(B * alpha_r - E * (B * alpha_r - atan(B * alpha_r))));
+  const double a = P.u_drive[(size_t)b * 2 * P.N];
+  const double el = Fcr / (p.M * p.ELL_LAT), ea = a / p.ELL_LONG;
+  const double e = el * el + ea * ea;
+  if (e > 1.0) {                                                                // main.m:212-213
+    m[FSAEMPC_M_ELL_VIOL_INT] += (e - 1.0) * P.dt;
+    if (e - 1.0 > m[FSAEMPC_M_ELL_VIOL_MAX]) m[FSAEMPC_M_ELL_VIOL_MAX] = e - 1.0;
+  }
+}
+
 }  // namespace
 
+hipError_t cl_metrics_launch(const ClMetricsParams& P, hipStream_t st, const double* par, int par_stride) {
+  if (P.batch == 0) return hipSuccess;
+  if (par) hipLaunchKernelGGL(cl_metrics_kernel<RtPar>, dim3((P.batch + 63) / 64), dim3(64), 0, st, P, ParArgs{par, par_stride, nullptr});
+  else hipLaunchKernelGGL(cl_metrics_kernel<FixedPar>, dim3((P.batch + 63) / 64), dim3(64), 0, st, P, NoParArgs{});
+  return hipGetLastError();
+}
 hipError_t cl_accept_launch(int len_x, int len_u, int batch, const double* x_new, const double* u_new, const int* exitflag, double* x_keep, double* u_keep, hipStream_t st) {
   if (batch == 0) return hipSuccess;
   hipLaunchKernelGGL(cl_accept_kernel, dim3((batch + 63) / 64), dim3(64), 0, st, len_x, len_u, batch, x_new, u_new, exitflag, x_keep, u_keep);

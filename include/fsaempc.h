@@ -494,6 +494,72 @@ int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_splin
 int fsaempc_cl_plant_batch_device_p(int model, int N, double dt, int batch, const fsaempc_ltv_params* par, double* cart, double* pid,
                                     const double* x_opt, const int* finished, const int* exitflag, double* u_last, void* stream);
 
+/* ---- lap report: what main.m:196-228 prints, accumulated per car on the device ----------
+ * One record of FSAEMPC_NMETRIC doubles per car, instance-major, zeroed by the caller before the first step.  A step is "recorded"
+ * for a car while it drives (finished[b] == 0 when fsaempc_cl_pre_batch_device returned). */
+#define FSAEMPC_NMETRIC 16
+#define FSAEMPC_M_STEPS          0   /* MPC steps solved while the car drove: main.m:203,216's i - 1 (lap time = STEPS dt) */
+#define FSAEMPC_M_STATUS         1   /* 0 driving, 1 finished (s >= L, main.m:102-104), 2 lost; latched: a latched record is final */
+#define FSAEMPC_M_N_VIOL_INT     2   /* sum (|n| - N_MAX) dt over recorded n with |n| > N_MAX (main.m:204,217) */
+#define FSAEMPC_M_N_VIOL_MAX     3   /* max (|n| - N_MAX) over the same steps, 0 if none (main.m:205,218) */
+#define FSAEMPC_M_N_ABS_MAX      4   /* largest |n| recorded (main.m:101, n_list) */
+#define FSAEMPC_M_ABNORMAL       5   /* steps with exitflag != 0 (main.m:209,222) */
+#define FSAEMPC_M_OBJ_SUM        6   /* fval summed over steps with exitflag == 0 and no slack in use (main.m:198,210,223) */
+#define FSAEMPC_M_OBJ_CNT        7   /* number of those steps */
+#define FSAEMPC_M_SLACK_N_CNT    8   /* steps with slack[0] in use (main.m:132,211,224) */
+#define FSAEMPC_M_SLACK_TYRE_CNT 9   /* steps with the tyre slack in use: dynamic slack[3], kinematic slack[0] (main.m:133,214,227) */
+#define FSAEMPC_M_ELL_VIOL_INT   10  /* sum (e - 1) dt over steps with e > 1, e = (Fcr / (M ELL_LAT))^2 + (a / ELL_LONG)^2 (main.m:180-182,199,212,225) */
+#define FSAEMPC_M_ELL_VIOL_MAX   11  /* max (e - 1) over the same steps, 0 if none (main.m:213,226) */
+#define FSAEMPC_M_ITER_SUM       12  /* solver iterations summed: the batch's stand-in for cpu_time (main.m:131,206,219) */
+#define FSAEMPC_M_ITER_MAX       13  /* most iterations of one step (main.m:208,221) */
+#define FSAEMPC_M_S_START        14  /* s at the first recorded step */
+#define FSAEMPC_M_S_LAST         15  /* s at the last recorded step */
+
+/*
+ * One call per MPC period, after the plant; asynchronous on `stream`.  Per car, with finished[b] as the pre-step left it:
+ *   record already latched (STATUS != 0): nothing is touched;
+ *   finished[b] == 2: STATUS = 2, nothing else (x0 is a placeholder);
+ *   otherwise n = x0[1] enters N_ABS_MAX and, if |n| > N_MAX, the track violation; then finished[b] == 1: STATUS = 1 and nothing
+ *   else of this step (main.m:101 stores n_list(i) before the break of :102-104, and :204 sums over it);
+ *   a driving car records the rest: STEPS, S_START / S_LAST = x0[0], the exit flag, iter, fval, the slacks and the ellipse value.
+ * "In use" is slack > slack_tol (a NaN slack is not in use).  a = u_drive[0], the first acceleration of the plan the car drives on
+ * (2N per car: u_keep after fsaempc_cl_accept_batch_device); Fcr is the rear lateral force of vehicle_models/curvilinear_dynamic/
+ * f_curv_dyn.m:32-53 (x_d + 5 exp(-x_d / 5) in the slip angle) at the post-plant state cart (batch x 7).
+ * par: NULL (the reference's constants), one shared block or one per car; N_MAX, ELL_LONG, ELL_LAT, M, LF, LR, GRAV, PB..PE are read.
+ * A block that cannot describe a car leaves that car's record untouched.  slack: 1 (kinematic) or 4 (dynamic) per car.
+ * FSAEMPC_ERR_ARG before any launch: a NULL pointer (par excepted), an unknown model, N < 1, batch < 0, dt not finite or <= 0,
+ * slack_tol negative or NaN.  batch == 0 succeeds without a launch.
+ */
+int fsaempc_cl_metrics_batch_device(int model, int N, double dt, double slack_tol, int batch, const fsaempc_ltv_params* par,
+                                    const double* x0, const int* finished, const int* exitflag, const int* iter, const double* fval,
+                                    const double* slack, const double* u_drive, const double* cart, double* metrics, void* stream);
+
+/* Batch summary of `batch` records on the HOST (no device needed), summed in index order: the same bits on every call. */
+#define FSAEMPC_NREPORT 20
+#define FSAEMPC_R_CARS_DRIVING    0   /* cars by STATUS */
+#define FSAEMPC_R_CARS_FINISHED   1
+#define FSAEMPC_R_CARS_LOST       2
+#define FSAEMPC_R_LAP_MEAN        3   /* STEPS dt over the finished cars (main.m:203); NaN if none finished.  Lost cars are not in it */
+#define FSAEMPC_R_LAP_MIN         4
+#define FSAEMPC_R_LAP_MAX         5
+#define FSAEMPC_R_STEPS           6   /* recorded steps of all cars: the denominator of the three percentages and of ITER_MEAN */
+#define FSAEMPC_R_ABNORMAL_PCT    7   /* main.m:209 pooled over all recorded steps; NaN without a recorded step */
+#define FSAEMPC_R_SLACK_N_PCT     8   /* main.m:211 */
+#define FSAEMPC_R_SLACK_TYRE_PCT  9   /* main.m:214 */
+#define FSAEMPC_R_OBJ_MEAN        10  /* main.m:210: OBJ_SUM / OBJ_CNT pooled; NaN if no step counted */
+#define FSAEMPC_R_N_VIOL_INT_MEAN 11  /* main.m:204 as the mean over the cars with STEPS > 0 (NaN if none) ... */
+#define FSAEMPC_R_N_VIOL_INT_MAX  12  /* ... and the largest of one car (0 for an empty batch) */
+#define FSAEMPC_R_N_VIOL_MAX      13  /* main.m:205: largest of all cars */
+#define FSAEMPC_R_ELL_VIOL_INT_MEAN 14 /* main.m:212, as N_VIOL_INT_MEAN */
+#define FSAEMPC_R_ELL_VIOL_INT_MAX 15
+#define FSAEMPC_R_ELL_VIOL_MAX    16  /* main.m:213 */
+#define FSAEMPC_R_ITER_MEAN       17  /* main.m:206 with iterations for cpu_time; NaN without a recorded step */
+#define FSAEMPC_R_ITER_MAX        18  /* main.m:208 */
+#define FSAEMPC_R_N_ABS_MAX       19  /* largest |n| of all cars */
+/* metrics_host: batch x FSAEMPC_NMETRIC (host); out: FSAEMPC_NREPORT doubles.  FSAEMPC_ERR_ARG: NULL (metrics_host may be NULL
+ * with batch == 0), batch < 0, dt not finite or <= 0. */
+int fsaempc_cl_report(const double* metrics_host, int batch, double dt, double* out);
+
 /* ---- s-domain plans: a speed-profile planner and the loop that tracks a plan -----------
  * The reference's controller is meant to track a planned trajectory: main.m:20 computes an s-domain plan with
  * dynamic_minimum_time_planner (IPOPT; not part of this build) and main.m:115 resamples it in time with obtain_reference.

@@ -5,8 +5,11 @@ no per-step read-back (fsae_mpc_amd.monte_carlo).  Prints one JSON line: QP solv
 driving, the exit-flag tally the way main.m:209,222 reports it ("abnormal exits %"), iterations, progress.
 --plan: the cars track a plan of the planner stand-in (fsaempc.Plan.profile) instead of the live ramp to 20 m/s.
 --raceline: the plan is made on a minimum-curvature racing line (fsaempc.Plan.raceline) instead of the centre line.
-usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40]
-                                  [--plan | --raceline [--margin M] [--points N_c]] [--grip G] [--cells N_s]"""
+--report: the lap report (main.m:196-228 over the batch) joins the JSON line as "lap_report".
+--lap: every car starts at s = 0 on the centre line, at rest, with the usual lateral and heading scatter (main.m:63), and the step cap
+defaults to 1000 (main.m:62): a finished car's STEPS * dt is then a lap time.
+usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--track fss2019]
+                                  [--plan | --raceline [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -18,7 +21,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="dynamic", choices=["kinematic", "dynamic"])
     ap.add_argument("--batch", type=int, default=2048)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=None, help="step cap (default 200; with --lap 1000, main.m:62)")
+    ap.add_argument("--track", default="fss2019", choices=["fsg2019", "fss2019", "fso2020"])
+    ap.add_argument("--report", action="store_true", help="keep the lap report's records on the device and add its summary to the JSON line")
+    ap.add_argument("--lap", action="store_true", help="all cars start at s = 0 at rest; step cap 1000")
+    ap.add_argument("--slack-tol", type=float, default=1e-6, help="with --report: a slack counts as in use above this value")
     ap.add_argument("--horizon", type=int, default=40)
     ap.add_argument("--seed", type=int, default=20190)
     ap.add_argument("--max-iter", type=int, default=100, help="interior-point iteration limit (bounds the batch tail)")
@@ -31,8 +38,10 @@ def main():
     ap.add_argument("--margin", type=float, default=0.25, help="with --raceline: distance the line keeps from N_MAX, m")
     ap.add_argument("--points", type=int, default=100, help="with --raceline: control points of the line (N_c)")
     a = ap.parse_args()
+    if a.steps is None:
+        a.steps = 1000 if a.lap else 200
     model = fm.KINEMATIC if a.model == "kinematic" else fm.DYNAMIC
-    tr = fm.Track.load("fss2019")
+    tr = fm.Track.load(a.track)
     plan = fm.Plan.profile(model, tr, N_s=a.cells, grip=a.grip) if a.plan else None
     if a.raceline:
         plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip)
@@ -42,8 +51,9 @@ def main():
     t0 = time.perf_counter()
     # the loop of fm.monte_carlo with two more counts kept on the device: steps off the track (|n| > N_MAX) and the last arc length of
     # every car while it drives
-    cart0, s_init = fm.monte_carlo_carts(tr, a.batch, a.seed)
-    cl = fm.ClosedLoop(model, a.horizon, 0.05, tr, cart0, options=opts, warm_start=a.warm, launch_hint=not a.no_launch_hint, reference=plan)
+    cart0, s_init = fm.monte_carlo_carts(tr, a.batch, a.seed, lap=a.lap)
+    cl = fm.ClosedLoop(model, a.horizon, 0.05, tr, cart0, options=opts, warm_start=a.warm, launch_hint=not a.no_launch_hint, reference=plan,
+                       metrics=a.report, slack_tol=a.slack_tol)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]
     fl_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
@@ -75,9 +85,12 @@ def main():
     print(json.dumps({
         "metric": "QP solves/sec (closed loop, %s N=%d, fp64)" % (a.model, a.horizon), "value": solved / dt_wall, "unit": "QP solves/s",
         "n_gpus": 1, "steps": a.steps, "ms_per_step": 1e3 * dt_wall / a.steps, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "BASELINE configs[3] share of one GPU: %d cars on fss2019, %d receding-horizon steps, every step one batch of QPs "
+        "config": {"workload": "BASELINE configs[3] share of one GPU: %d cars on %s, %d receding-horizon steps, every step one batch of QPs "
                                "(frame transform + reference + linearise/condense/solve + PID/plant, device-resident loop, no per-step read-back; "
-                               "wall time includes the allocation of the run)" % (a.batch, a.steps),
+                               "wall time includes the allocation of the run)" % (a.batch, a.track, a.steps),
+                   "track": a.track, "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
+                   # (a mean over an empty set is NaN in the report: null in the JSON line)
+                   **({"lap_report": {k: (None if v != v else v) for k, v in cl.report().summary().items()}, "slack_tol": a.slack_tol} if a.report else {}),
                    "qps_of_driving_cars": n_act, "qps_total_launched": int(a.batch * a.steps),
                    "exitflag_histogram_driving_cars": hist, "minus1_with_nonfinite_qp_data": bad_data,
                    "minus1_on_finite_qp_data_pct": 100.0 * (hist.get(-1, 0) - bad_data) / max(1, n_act), "abnormal_exit_pct": 100.0 * (1.0 - solved / max(1, n_act)),
