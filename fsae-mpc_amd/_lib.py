@@ -28,6 +28,8 @@ EXPORTS = [
     "fsaempc_raceline_build_qp_device", "fsaempc_plan_line_profile_batch_device", "fsaempc_plan_raceline_workspace_bytes",
     "fsaempc_plan_raceline_batch_device",
     "fsaempc_cl_metrics_batch_device", "fsaempc_cl_report",
+    "fsaempc_ltv_build_qp_batch_device_c", "fsaempc_ltv_step_batch_device_c", "fsaempc_cl_metrics_batch_device_c",
+    "fsaempc_plan_raceline_batch_device_c", "fsaempc_corridor_line_bounds_device",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -97,6 +99,10 @@ MAX_NV = 196         # FSAEMPC_MAX_NV
 
 class PlanTable(C.Structure):   # fsaempc_plan
     _fields_ = [("table", C.c_void_p), ("t", C.c_void_p), ("N_s", C.c_int), ("ds", C.c_double), ("per_instance", C.c_int)]
+
+
+class CorridorTable(C.Structure):   # fsaempc_corridor
+    _fields_ = [("n_lo", C.c_void_p), ("n_hi", C.c_void_p), ("N_w", C.c_int), ("ds", C.c_double), ("per_instance", C.c_int)]
 
 
 def check_blocking(blocking, N):
@@ -229,6 +235,16 @@ def lib():
                                                          C.c_double, C.c_double, C.c_double, C.POINTER(QpOpts), vp, vp, vp, vp, vp, ll, vp]
         L.fsaempc_cl_metrics_batch_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(LtvParams)] + [vp] * 10
         L.fsaempc_cl_report.argtypes = [vp, C.c_int, C.c_double, vp]
+        L.fsaempc_ltv_build_qp_batch_device_c.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(LtvBlocking),
+                                                          C.POINTER(CorridorTable)] + [vp] * 4 + [vp] * 7 + [vp] * 3 + [vp]
+        L.fsaempc_ltv_step_batch_device_c.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(LtvBlocking),
+                                                      C.POINTER(CorridorTable)] + [vp] * 4 + [C.POINTER(QpOpts)] + [vp] * 7 + [C.POINTER(QpAux), vp, ll, vp]
+        L.fsaempc_cl_metrics_batch_device_c.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(LtvParams),
+                                                        C.POINTER(CorridorTable)] + [vp] * 10
+        L.fsaempc_corridor_line_bounds_device.argtypes = [C.POINTER(CorridorTable), C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp]
+        L.fsaempc_plan_raceline_batch_device_c.argtypes = [C.c_int, C.POINTER(Spline), C.c_double, C.POINTER(LtvParams), C.POINTER(CorridorTable),
+                                                           C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(QpOpts),
+                                                           vp, vp, vp, vp, vp, ll, vp]
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p
         L.fsaempc_track_from_csv.argtypes = [C.c_char_p, C.c_int, C.POINTER(TrackTable)]

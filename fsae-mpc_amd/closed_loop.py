@@ -6,6 +6,7 @@ import numpy as np
 
 from ._lib import METRIC_INDEX, NMETRIC, NREPORT, REPORT_INDEX, ParamBlock, Spline, check, check_blocking, lib
 from .ltvmpc import LtvBatch, dims
+from .corridor import check_corridor
 from .plan import Plan
 
 
@@ -35,14 +36,16 @@ class ClosedLoop:
     plan -- and the exit flags are only tallied.  Cars that completed the lap (s >= L) or left the track keep their state."""
 
     def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
-                 params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6):
+                 params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6, corridor=None):
         """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
         None = the same as params (both None: the reference's constants compiled into the kernels).  blocking: block lengths of the
         controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2).  reference: None = the live
         generator of main.m:107-114 (a ramp to target_vel); a Plan = main.m:115, the cars track it (shared, or one table per car;
         target_vel is then unused).  metrics: keep the lap report's per-car records (self.metrics, (B, 16) on the device; one more
         kernel per step, on the same stream; limits and ellipse axes are those of params) -- report() reads them back.  slack_tol: a slack
-        counts as in use above it (the reference tests == 0; 1e-6 is this build's solve tolerance)."""
+        counts as in use above it (the reference tests == 0; 1e-6 is this build's solve tolerance).  corridor: None or a Corridor (shared,
+        or one per car): the controller's track rows and, with metrics, the report's track violation are taken against it
+        (DESIGN.md 6l)."""
         if not (float(slack_tol) >= 0):
             raise ValueError("slack_tol must be >= 0")
         if blocking is not None:
@@ -53,6 +56,7 @@ class ClosedLoop:
             reference.check_batch(np.asarray(cart0).size // 7)
             reference.check_device(device)
         self.reference = reference
+        check_corridor(corridor, np.asarray(cart0).size // 7, device)   # (before the library is touched)
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -62,7 +66,8 @@ class ClosedLoop:
         self.B = cart0.shape[0]
         self.track = track
         self.mpc = LtvBatch(model, N, dt, track, self.B, device=device, options=options, integrator=integrator, params=params,
-                            blocking=blocking)
+                            blocking=blocking, corridor=corridor)
+        self.corridor = self.mpc.corridor
         if plant_params is None:
             plant_params = params
         self.plant_params = ParamBlock(plant_params, self.B, self.device) if plant_params is not None else None
@@ -148,7 +153,13 @@ class ClosedLoop:
         check(lib().fsaempc_cl_accept_batch_device(self.model, self.N, self.B, P(out["x_opt"]), P(out["u_opt"]), P(out["exitflag"]), P(self.x_opt), P(self.u_opt),
                                                    self._stream(stream)), "fsaempc_cl_accept_batch_device")
         self.plant(None, stream)
-        if self.metrics is not None:
+        if self.metrics is not None and self.corridor is not None:
+            check(lib().fsaempc_cl_metrics_batch_device_c(self.model, self.N, C.c_double(self.dt), C.c_double(self.slack_tol), self.B,
+                                                          self.mpc.params.ref() if self.mpc.params is not None else None, self.corridor.ref(),
+                                                          P(self.x0), P(self.finished), P(out["exitflag"]), P(out["iter"]), P(out["fval"]),
+                                                          P(out["slack"]), P(self.u_opt), P(self.cart), P(self.metrics), self._stream(stream)),
+                  "fsaempc_cl_metrics_batch_device_c")
+        elif self.metrics is not None:
             check(lib().fsaempc_cl_metrics_batch_device(self.model, self.N, C.c_double(self.dt), C.c_double(self.slack_tol), self.B,
                                                         self.mpc.params.ref() if self.mpc.params is not None else None, P(self.x0), P(self.finished),
                                                         P(out["exitflag"]), P(out["iter"]), P(out["fval"]), P(out["slack"]), P(self.u_opt), P(self.cart),
@@ -185,15 +196,16 @@ def monte_carlo_carts(track, B, seed, lap=False):
 
 
 def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
-                plant_params=None, blocking=None, reference=None, metrics=False):
+                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
     reference: None (the live ramp) or a Plan the cars track (ClosedLoop).  metrics: ClosedLoop(metrics=True); cl.report() afterwards.
+    corridor: None or a Corridor (ClosedLoop).
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
     import torch
     cart0, s_init = monte_carlo_carts(track, B, seed)
     cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
-                    params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics)
+                    params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics, corridor=corridor)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

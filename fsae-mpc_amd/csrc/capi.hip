@@ -17,6 +17,7 @@
 #include "plant.h"
 #include "planner.h"
 #include "raceline.h"
+#include "corridor.h"
 #include "sqp.h"
 #include "qp_sens.h"
 
@@ -416,6 +417,8 @@ static int ltv_check(const fsaempc_ltv_desc* d, const fsaempc_spline* sp) {
   return 0;
 }
 
+static bool pos_finite(double v) { return v > 0 && v < INFINITY; }
+
 static int ltv_integ(const fsaempc_ltv_desc* d) {
   return d->integrator >= 0 ? d->integrator : (d->model == FSAEMPC_MODEL_KINEMATIC ? FSAEMPC_INT_RK2 : FSAEMPC_INT_RK4);   // ltvmpc_*.m:38
 }
@@ -490,6 +493,27 @@ int fsaempc_nlp_build_qp_batch_device(const fsaempc_ltv_desc* desc, const fsaemp
   return fsaempc_nlp_build_qp_batch_device_p(desc, sp, nullptr, x0, x_ref, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
 }
 
+/* ---- s-varying track corridors ---- */
+// the descriptor as the kernels take it; every refusal names the argument
+static int cor_check(const fsaempc_corridor* cor, CorTable* out) {
+  if (!cor->n_lo) return fail(FSAEMPC_ERR_ARG, "corridor: n_lo is NULL");
+  if (!cor->n_hi) return fail(FSAEMPC_ERR_ARG, "corridor: n_hi is NULL");
+  if (cor->N_w < 2) return fail(FSAEMPC_ERR_ARG, "corridor: N_w must be >= 2");
+  if (!pos_finite(cor->ds)) return fail(FSAEMPC_ERR_ARG, "corridor: ds must be finite and > 0");
+  out->n_lo = cor->n_lo; out->n_hi = cor->n_hi; out->N_w = cor->N_w; out->ds = cor->ds; out->stride = cor->per_instance ? cor->N_w : 0;
+  return 0;
+}
+// the track-row bounds of a built batch (plain or blocked: the rows are the same) from the corridor
+static int cor_rows(const fsaempc_ltv_desc* desc, const CorTable& cor, const double* x_lin, const double* pred, double* lbA, double* ubA,
+                    void* stream) {
+  Range r("fsaempc.ltv.corridor");
+  CorRowsParams P; P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.nC = fsaempc_ltv_nC(desc->model, desc->N); P.batch = desc->batch;
+  P.x_lin = x_lin; P.pred = pred; P.lbA = lbA; P.ubA = ubA; P.cor = cor;
+  hipError_t e = cor_rows_launch(P, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "cor_rows_launch");
+  return 0;
+}
+
 struct LtvCarve { size_t H, g, A, lb, ub, lbA, ubA, pred, Bt, qc, z, qpws, total; };
 static void ltv_carve(const fsaempc_ltv_desc* d, LtvCarve* c) {
   const size_t B = d->batch > 0 ? d->batch : 1, nx = fsaempc_ltv_nx(d->model), N = d->N;
@@ -522,7 +546,7 @@ int fsaempc_ltv_step_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_sp
 static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
                     const double* u_lin, const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
                     int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream,
-                    const fsaempc_ltv_params* par = nullptr);
+                    const fsaempc_ltv_params* par = nullptr, const CorTable* cor = nullptr);
 
 int fsaempc_ltv_step_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
                                     const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
@@ -551,7 +575,7 @@ int fsaempc_ltv_step_batch_device_lambda(const fsaempc_ltv_desc* desc, const fsa
 static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
                     const double* u_lin, const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
                     int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream,
-                    const fsaempc_ltv_params* par) {
+                    const fsaempc_ltv_params* par, const CorTable* cor) {
   int rc = ltv_check(desc, sp); if (rc) return rc;
   if (!x0 || !x_ref || !x_lin || !u_lin || !u_opt || !x_opt || !slack || !fval || !exitflag || !iter || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
@@ -567,6 +591,7 @@ static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, cons
     rc = fsaempc_ltv_build_qp_batch_device_p(desc, sp, par, x0, x_ref, x_lin, u_lin, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA),
                                              D(c.pred), D(c.Bt), D(c.qc), stream); }
   if (rc) return rc;
+  if (cor) { rc = cor_rows(desc, *cor, x_lin, D(c.pred), D(c.lbA), D(c.ubA), stream); if (rc) return rc; }
   fsaempc_qp_desc q{fsaempc_ltv_nV(desc->model, desc->N), fsaempc_ltv_nC(desc->model, desc->N), desc->batch, 0};
   rc = fsaempc_qp_solve_batch_device_aux(&q, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA), opts, D(c.z), fval, exitflag, iter,
                                          lambda, aux, w + c.qpws, (long long)(c.total - c.qpws), stream);
@@ -653,15 +678,15 @@ long long fsaempc_ltv_workspace_bytes_b(const fsaempc_ltv_desc* desc, const fsae
   return (long long)c.total;
 }
 
-int fsaempc_ltv_step_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
-                                    const fsaempc_ltv_blocking* blk,
-                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
-                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
-                                    void* workspace, long long workspace_bytes, void* stream) {
+static int ltv_step_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                      const fsaempc_ltv_blocking* blk, const CorTable* cor,
+                      const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                      const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                      int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                      void* workspace, long long workspace_bytes, void* stream) {
   LtvBlockMap bm; bool trivial = false;
   int rc = blk_check(desc, blk, &bm, &trivial); if (rc) return rc;
-  if (trivial) return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream, par);
+  if (trivial) return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream, par, cor);
   rc = ltv_check(desc, sp); if (rc) return rc;
   if (!x0 || !x_ref || !x_lin || !u_lin || !u_opt || !x_opt || !slack || !fval || !exitflag || !iter || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (desc->batch == 0) return 0;
@@ -676,6 +701,7 @@ int fsaempc_ltv_step_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_
     rc = fsaempc_ltv_build_qp_batch_device_b(desc, sp, par, blk, x0, x_ref, x_lin, u_lin, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA),
                                              D(c.pred), D(c.Bt), D(c.qc), stream); }
   if (rc) return rc;
+  if (cor) { rc = cor_rows(desc, *cor, x_lin, D(c.pred), D(c.lbA), D(c.ubA), stream); if (rc) return rc; }
   const int ns = ltv_ns(desc->model);
   fsaempc_qp_desc q{2 * bm.M + ns, fsaempc_ltv_nC(desc->model, desc->N), desc->batch, 0};
   rc = fsaempc_qp_solve_batch_device_s(&q, ns, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA), opts, D(c.z), fval, exitflag, iter,
@@ -688,6 +714,47 @@ int fsaempc_ltv_step_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_
   if (e != hipSuccess) return hipfail(e, "ltv_post_blocked_launch");
   if (timing) { e = hipEventRecord(g_evf[1], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
   return 0;
+}
+
+int fsaempc_ltv_step_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const fsaempc_ltv_blocking* blk,
+                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                    void* workspace, long long workspace_bytes, void* stream) {
+  return ltv_step_b(desc, sp, par, blk, nullptr, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux,
+                    workspace, workspace_bytes, stream);
+}
+
+/* ---- the build and the step inside a corridor ---- */
+int fsaempc_ltv_build_qp_batch_device_c(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const fsaempc_ltv_blocking* blk, const fsaempc_corridor* cor,
+                                        const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream) {
+  CorTable ct;
+  if (cor) {
+    if (int rc = cor_check(cor, &ct)) return rc;
+    if (!pred) return fail(FSAEMPC_ERR_ARG, "null argument (pred is required with a corridor)");
+  }
+  int rc = blk ? fsaempc_ltv_build_qp_batch_device_b(desc, sp, par, blk, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream)
+               : fsaempc_ltv_build_qp_batch_device_p(desc, sp, par, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
+  if (rc || !cor) return rc;
+  return cor_rows(desc, ct, x_lin, pred, lbA, ubA, stream);
+}
+
+int fsaempc_ltv_step_batch_device_c(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const fsaempc_ltv_blocking* blk, const fsaempc_corridor* cor,
+                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                    void* workspace, long long workspace_bytes, void* stream) {
+  CorTable ct;
+  if (cor) { if (int rc = cor_check(cor, &ct)) return rc; }
+  const CorTable* c = cor ? &ct : nullptr;
+  if (blk) return ltv_step_b(desc, sp, par, blk, c, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux,
+                             workspace, workspace_bytes, stream);
+  return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream, par, c);
 }
 
 /* ---- sensitivities of the LTV-MPC step ---- */
@@ -943,12 +1010,12 @@ int fsaempc_cl_accept_batch_device(int model, int N, int batch, const double* x_
   return 0;
 }
 
-static bool pos_finite(double v) { return v > 0 && v < INFINITY; }
-
 /* ---- lap report ---- */
-int fsaempc_cl_metrics_batch_device(int model, int N, double dt, double slack_tol, int batch, const fsaempc_ltv_params* par,
-                                    const double* x0, const int* finished, const int* exitflag, const int* iter, const double* fval,
-                                    const double* slack, const double* u_drive, const double* cart, double* metrics, void* stream) {
+static int cl_metrics(int model, int N, double dt, double slack_tol, int batch, const fsaempc_ltv_params* par, const fsaempc_corridor* cor,
+                      const double* x0, const int* finished, const int* exitflag, const int* iter, const double* fval,
+                      const double* slack, const double* u_drive, const double* cart, double* metrics, void* stream) {
+  CorTable ct;
+  if (cor) { if (int rc = cor_check(cor, &ct)) return rc; }
   if (!x0 || !finished || !exitflag || !iter || !fval || !slack || !u_drive || !cart || !metrics) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
   if (N <= 0 || batch < 0 || !pos_finite(dt)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
@@ -957,9 +1024,21 @@ int fsaempc_cl_metrics_batch_device(int model, int N, double dt, double slack_to
   ClMetricsParams P; P.ns = ltv_ns(model); P.N = N; P.batch = batch; P.tyre = model == FSAEMPC_MODEL_DYNAMIC ? 3 : 0;
   P.dt = dt; P.slack_tol = slack_tol; P.nx = fsaempc_ltv_nx(model); P.x0 = x0; P.finished = finished; P.exitflag = exitflag; P.iter = iter;
   P.fval = fval; P.slack = slack; P.u_drive = u_drive; P.cart = cart; P.metrics = metrics;
-  hipError_t e = cl_metrics_launch(P, (hipStream_t)stream, par_values(par), par_stride(par));
-  if (e != hipSuccess) return hipfail(e, "cl_metrics_launch");
+  hipError_t e = cor ? cor_metrics_launch(P, ct, (hipStream_t)stream, par_values(par), par_stride(par))
+                     : cl_metrics_launch(P, (hipStream_t)stream, par_values(par), par_stride(par));
+  if (e != hipSuccess) return hipfail(e, cor ? "cor_metrics_launch" : "cl_metrics_launch");
   return 0;
+}
+int fsaempc_cl_metrics_batch_device(int model, int N, double dt, double slack_tol, int batch, const fsaempc_ltv_params* par,
+                                    const double* x0, const int* finished, const int* exitflag, const int* iter, const double* fval,
+                                    const double* slack, const double* u_drive, const double* cart, double* metrics, void* stream) {
+  return cl_metrics(model, N, dt, slack_tol, batch, par, nullptr, x0, finished, exitflag, iter, fval, slack, u_drive, cart, metrics, stream);
+}
+int fsaempc_cl_metrics_batch_device_c(int model, int N, double dt, double slack_tol, int batch, const fsaempc_ltv_params* par,
+                                      const fsaempc_corridor* cor,
+                                      const double* x0, const int* finished, const int* exitflag, const int* iter, const double* fval,
+                                      const double* slack, const double* u_drive, const double* cart, double* metrics, void* stream) {
+  return cl_metrics(model, N, dt, slack_tol, batch, par, cor, x0, finished, exitflag, iter, fval, slack, u_drive, cart, metrics, stream);
 }
 
 // Host.  Every sum runs over the cars in index order.  Means over an empty set are NaN (MATLAB's mean([])).
@@ -1129,9 +1208,11 @@ long long fsaempc_plan_raceline_workspace_bytes(int n_plans, int N_c) {
   return (long long)c.total;
 }
 
-int fsaempc_plan_raceline_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, int n_plans, int N_s,
-                                       int N_c, double margin, double v_cap, double grip, const fsaempc_qp_opts* opts, double* line, int* flag,
-                                       double* table, double* t, void* workspace, long long workspace_bytes, void* stream) {
+static int plan_raceline(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, const fsaempc_corridor* cor, int n_plans,
+                         int N_s, int N_c, double margin, double v_cap, double grip, const fsaempc_qp_opts* opts, double* line, int* flag,
+                         double* table, double* t, void* workspace, long long workspace_bytes, void* stream) {
+  CorLineParams CL;
+  if (cor) { if (int rc = cor_check(cor, &CL.cor)) return rc; }
   if (!line || !flag || !table || !t || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (int rc = line_check(sp, L, N_s, N_c)) return rc;
   if (int rc = line_profile_check(model, par, n_plans, v_cap, grip)) return rc;
@@ -1143,16 +1224,54 @@ int fsaempc_plan_raceline_batch_device(int model, const fsaempc_spline* sp, doub
   double *H = (double*)(ws + c.H), *g = (double*)(ws + c.g), *lb = (double*)(ws + c.lb), *ub = (double*)(ws + c.ub);
   hipError_t e = raceline_qp_launch(line_qp_params(sp, L, N_s, N_c, H, g), (hipStream_t)stream);
   if (e != hipSuccess) return hipfail(e, "raceline_qp_launch");
-  RacelineBoundsParams B; B.n_plans = n_plans; B.N_c = N_c; B.margin = margin; B.g = g; B.lb = lb; B.ub = ub;
-  e = raceline_bounds_launch(B, par_values(par), par_stride(par), (hipStream_t)stream);
-  if (e != hipSuccess) return hipfail(e, "raceline_bounds_launch");
+  if (cor) {
+    CL.n_plans = n_plans; CL.N_s = N_s; CL.N_c = N_c; CL.L = L; CL.margin = margin; CL.g = g; CL.lb = lb; CL.ub = ub; CL.line = line; CL.flag = flag;
+    e = cor_line_bounds_launch(CL, (hipStream_t)stream);
+    if (e != hipSuccess) return hipfail(e, "cor_line_bounds_launch");
+  } else {
+    RacelineBoundsParams B; B.n_plans = n_plans; B.N_c = N_c; B.margin = margin; B.g = g; B.lb = lb; B.ub = ub;
+    e = raceline_bounds_launch(B, par_values(par), par_stride(par), (hipStream_t)stream);
+    if (e != hipSuccess) return hipfail(e, "raceline_bounds_launch");
+  }
   const fsaempc_qp_desc d = {N_c, 0, n_plans, 1};
   if (int rc = fsaempc_qp_solve_batch_device_s(&d, 0, H, g, nullptr, lb, ub, nullptr, nullptr, opts, line, (double*)(ws + c.fval), flag,
                                                (int*)(ws + c.iter), nullptr, nullptr, ws + c.qp, c.qp_bytes, stream)) return rc;
+  if (cor) {   // a plan whose QP was not solved (no box: flag -1, or any other flag but 0): NaN control points, which the profile turns into a NaN plan
+    e = cor_line_void_launch(CL, (hipStream_t)stream);
+    if (e != hipSuccess) return hipfail(e, "cor_line_void_launch");
+  }
   PlanLineParams P = line_profile_params(model, sp, L, n_plans, N_s, N_c, v_cap, grip, table, t);
-  P.line = line; P.line_stride = N_c; P.flag = flag; P.line_out = line; P.check_width = 1; P.margin = margin;
+  P.line = line; P.line_stride = N_c; P.flag = cor ? nullptr : flag; P.line_out = line; P.check_width = cor ? 0 : 1; P.margin = margin;   // (in a corridor: no centre-line fallback)
   e = plan_line_profile_launch(P, par_values(par), par_stride(par), (hipStream_t)stream);
   if (e != hipSuccess) return hipfail(e, "plan_line_profile_launch");
+  return 0;
+}
+
+int fsaempc_plan_raceline_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, int n_plans, int N_s,
+                                       int N_c, double margin, double v_cap, double grip, const fsaempc_qp_opts* opts, double* line, int* flag,
+                                       double* table, double* t, void* workspace, long long workspace_bytes, void* stream) {
+  return plan_raceline(model, sp, L, par, nullptr, n_plans, N_s, N_c, margin, v_cap, grip, opts, line, flag, table, t, workspace, workspace_bytes, stream);
+}
+int fsaempc_plan_raceline_batch_device_c(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, const fsaempc_corridor* cor,
+                                         int n_plans, int N_s, int N_c, double margin, double v_cap, double grip, const fsaempc_qp_opts* opts,
+                                         double* line, int* flag, double* table, double* t, void* workspace, long long workspace_bytes, void* stream) {
+  return plan_raceline(model, sp, L, par, cor, n_plans, N_s, N_c, margin, v_cap, grip, opts, line, flag, table, t, workspace, workspace_bytes, stream);
+}
+
+int fsaempc_corridor_line_bounds_device(const fsaempc_corridor* cor, double L, int n_plans, int N_s, int N_c, double margin,
+                                        double* lb, double* ub, void* stream) {
+  CorLineParams CL;
+  if (!cor) return fail(FSAEMPC_ERR_ARG, "null argument (corridor)");
+  if (int rc = cor_check(cor, &CL.cor)) return rc;
+  if (!lb || !ub) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (!pos_finite(L)) return fail(FSAEMPC_ERR_ARG, "L must be finite and > 0");
+  if (N_c < FSAEMPC_LINE_MIN_NC || N_c > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_ARG, "N_c must be FSAEMPC_LINE_MIN_NC .. FSAEMPC_MAX_NV");
+  if (N_s < 2 * N_c || N_s > FSAEMPC_LINE_MAX_NS) return fail(FSAEMPC_ERR_ARG, "N_s must be 2 N_c .. FSAEMPC_LINE_MAX_NS");
+  if (n_plans < 1) return fail(FSAEMPC_ERR_ARG, "n_plans must be >= 1");
+  if (!(margin >= 0 && margin < INFINITY)) return fail(FSAEMPC_ERR_ARG, "margin must be finite and >= 0");
+  CL.n_plans = n_plans; CL.N_s = N_s; CL.N_c = N_c; CL.L = L; CL.margin = margin; CL.g = nullptr; CL.lb = lb; CL.ub = ub; CL.line = nullptr; CL.flag = nullptr;
+  hipError_t e = cor_line_bounds_launch(CL, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "cor_line_bounds_launch");
   return 0;
 }
 

@@ -8,7 +8,8 @@
 //                    (vehicle_models/pid_controller.m:5-18, gains main.m:84-88) driving the Cartesian dynamic bicycle
 //                    (cartesian_dynamic/f_cart_dyn.m:13-54) through the 6-stage scheme of integrate_cart_dyn.m:12-22
 //                    (stage formulas exactly as written there, including the doubled k2 term of k5)
-//   cl_metrics_kernel main.m:196-228 the lap report's figures, accumulated per car after every period (opt-in)
+//   cl_metrics_kernel main.m:196-228 the lap report's figures, accumulated per car after every period (opt-in); corridor.hip's
+//                    cor_metrics_kernel repeats its text with another track violation: a change here belongs there too
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "plant.h"

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import Blocking, LtvDesc, ParamBlock, QpAux, QpDesc, Spline, check, default_opts, lib
+from .corridor import check_corridor
 from .synthetic import DYNAMIC, KINEMATIC
 
 
@@ -21,13 +22,17 @@ class LtvBatch:
     """Device-resident batched LTV-MPC step (one call = linearise + condense + solve + post-solve for
     `batch` independent instances).  Inputs/outputs are torch tensors on the GPU."""
 
-    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1, params=None, blocking=None):
+    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1, params=None, blocking=None, corridor=None):
         """params: None (the reference's constants, compiled into the kernels), or a block of vehicle / cost / limit parameters
         (fsaempc.default_params, PARAM_INDEX): (32,) shared by the batch or (batch, 32) per instance, numpy or a device tensor.
         blocking: None, or a sequence of block lengths (each >= 1, sum N): the input is held over each block of consecutive steps
         (move blocking).  The QP then has nV = 2 * n_blocks + ns variables [v_1 .. v_M; slacks]: build_qp, x_init and
-        lam are in these sizes, while u_opt stays (B, 2N), the held values."""
+        lam are in these sizes, while u_opt stays (B, 2N), the held values.
+        corridor: None, or a Corridor (shared, or one table per instance): the track rows |n_k| <= N_MAX + slack become
+        n_lo(s_k) <= n_k + slack, n_k - slack <= n_hi(s_k) at the rows' linearisation points; build_qp and step go
+        through the _c entries, and the SQP's exact build, the affine maps and the VJPs refuse the batch."""
         self.blocking = Blocking(blocking, N) if blocking is not None else None   # (validated before the library is touched)
+        self.corridor = check_corridor(corridor, batch, device)
         import torch
         self.torch = torch
         self.model, self.N, self.dt, self.batch = model, N, float(dt), batch
@@ -65,7 +70,11 @@ class LtvBatch:
                  const=self._f64(B))
         P = lambda t: C.c_void_p(t.data_ptr())
         out = (P(q["H"]), P(q["g"]), P(q["A"]), P(q["lb"]), P(q["ub"]), P(q["lbA"]), P(q["ubA"]), P(q["pred"]), P(q["Bt"]), P(q["const"]))
-        if self.blocking is not None:
+        if self.corridor is not None:
+            rc = lib().fsaempc_ltv_build_qp_batch_device_c(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
+                                                           self.blocking.ref() if self.blocking is not None else None, self.corridor.ref(),
+                                                           P(x0), P(x_ref), P(x_lin), P(u_lin), *out, self._stream(stream))
+        elif self.blocking is not None:
             rc = lib().fsaempc_ltv_build_qp_batch_device_b(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
                                                            self.blocking.ref(), P(x0), P(x_ref), P(x_lin), P(u_lin), *out, self._stream(stream))
         elif self.params is not None:
@@ -110,7 +119,14 @@ class LtvBatch:
             raise ValueError("difficulty must be a contiguous int32 (batch,) tensor on the GPU")
         df = P(difficulty) if difficulty is not None else None
         aux = QpAux(P(out["kkt"]), P(out["polished"]), xi, df) if want_aux else QpAux(None, None, xi, df)
-        if self.blocking is not None:
+        if self.corridor is not None:
+            rc = lib().fsaempc_ltv_step_batch_device_c(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
+                                                       self.blocking.ref() if self.blocking is not None else None, self.corridor.ref(),
+                                                       P(x0), P(x_ref), P(x_lin), P(u_lin),
+                                                       C.byref(self.opts), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]),
+                                                       P(out["exitflag"]), P(out["iter"]), lam, C.byref(aux), P(self._ws),
+                                                       C.c_longlong(self._ws.numel() * 8), self._stream(stream))
+        elif self.blocking is not None:
             rc = lib().fsaempc_ltv_step_batch_device_b(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
                                                        self.blocking.ref(), P(x0), P(x_ref), P(x_lin), P(u_lin),
                                                        C.byref(self.opts), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]),

@@ -8,6 +8,7 @@ import math
 
 import numpy as np
 
+from .corridor import Corridor, check_corridor
 from ._lib import LINE_MAX_NS, LINE_MIN_NC, MAX_NV, NPAR, PLAN_MAX_NS, ParamBlock, PlanTable, Spline, check, default_opts, lib
 
 
@@ -148,16 +149,28 @@ class Plan:
 
     @staticmethod
     def raceline(model, track, N_s=500, N_c=100, margin=0.25, v_cap=20.0, grip=1.0, params=None, n_plans=1, options=None, device="cuda:0",
-                 stream=None):
+                 stream=None, corridor=None):
         """Racing-line plans (fsaempc_plan_raceline_batch_device): a minimum-curvature line within +-(N_MAX - margin) of
         the centre line (N_MAX: the block's, default 0.75) as N_c control points of a periodic cubic B-spline, then the profile of
         Plan.profile on it.  Returns a Plan with .line (P, N_c) control points and .line_flag (P,) exit flags of the line QPs; a plan
-        whose flag is not 0 is the centre-line plan."""
+        whose flag is not 0 is the centre-line plan.  corridor: None, or a Corridor (shared, or one per plan; n_plans is then its count):
+        the line stays within [n_lo + margin, n_hi - margin] at every cell (fsaempc_plan_raceline_batch_device_c, DESIGN.md 6l: each
+        control point takes the tightest limits of the cells it touches, so a pinch is smeared over four knot spacings).  A plan whose
+        corridor leaves a control point no room has flag -1 and is NaN; in a corridor NO plan falls back to the centre line (it may
+        lie outside the corridor): every plan whose flag is not 0 is NaN in table, t and line."""
         check_profile_args(N_s, v_cap, grip, n_plans)
         check_line_args(N_s, N_c, margin)
         if model not in (0, 1):
             raise ValueError("unknown model %r" % (model,))
         params, n_plans = check_params(params, n_plans)
+        if corridor is not None:
+            if not isinstance(corridor, Corridor):
+                raise ValueError("corridor must be None or a Corridor")
+            if corridor.P > 1 and params is not None and len(tuple(params.shape)) == 1:
+                raise ValueError("a shared parameter block makes one plan, the corridor holds %d" % corridor.P)
+            if corridor.P > 1 and params is None and n_plans == 1:
+                n_plans = corridor.P                     # (one plan per corridor; with (P, 32) blocks n_plans is already their count)
+            check_corridor(corridor, n_plans, device)
         import torch
         dev = torch.device(device)
         N_s, N_c, n_plans = int(N_s), int(N_c), int(n_plans)
@@ -175,12 +188,18 @@ class Plan:
         opts = options if options is not None else default_opts()
         st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
         p = lambda a: C.c_void_p(a.data_ptr())
-        rc = lib().fsaempc_plan_raceline_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
-                                                      n_plans, N_s, N_c, C.c_double(margin), C.c_double(v_cap), C.c_double(grip), C.byref(opts),
-                                                      p(line), p(flag), p(table), p(t), p(ws), C.c_longlong(ws.numel() * 8), st)
+        if corridor is not None:
+            rc = lib().fsaempc_plan_raceline_batch_device_c(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                            corridor.ref(), n_plans, N_s, N_c, C.c_double(margin), C.c_double(v_cap),
+                                                            C.c_double(grip), C.byref(opts), p(line), p(flag), p(table), p(t), p(ws),
+                                                            C.c_longlong(ws.numel() * 8), st)
+        else:
+            rc = lib().fsaempc_plan_raceline_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                          n_plans, N_s, N_c, C.c_double(margin), C.c_double(v_cap), C.c_double(grip), C.byref(opts),
+                                                          p(line), p(flag), p(table), p(t), p(ws), C.c_longlong(ws.numel() * 8), st)
         check(rc, "fsaempc_plan_raceline_batch_device")
         plan = Plan(table, t, track.L / N_s)
-        plan._blocks, plan._ws = blocks, ws   # (read by launches that may still be queued)
+        plan._blocks, plan._ws, plan._corridor = blocks, ws, corridor   # (read by launches that may still be queued)
         plan.line, plan.line_flag = line, flag
         return plan
 

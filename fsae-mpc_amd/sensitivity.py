@@ -109,6 +109,8 @@ def _no_params(batch, what):
     blk = getattr(batch, "blocking", None)
     if blk is not None and not blk.trivial:   # the same holds for move blocking: the maps and the VJP chain are those of the unblocked build
         raise NotImplementedError("%s is not available for an LtvBatch with move blocking (blocking=None, or one step per block)" % what)
+    if getattr(batch, "corridor", None) is not None:   # and for a corridor: the row shifts of the chain are those of the constant width
+        raise NotImplementedError("%s is not available for an LtvBatch with a corridor (corridor=None)" % what)
 
 
 def _ptr(t):

@@ -12,9 +12,12 @@ STATUS = {0: "converged", 1: "sweep limit", 2: "no step accepted", -1: "QP faile
 class SqpBatch:
     """Device-resident batched SQP.  Inputs / outputs are torch tensors on the GPU, laid out as for LtvBatch.step."""
 
-    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1, params=None, blocking=None):
+    def __init__(self, model, N, dt, track, batch, device="cuda:0", options=None, integrator=-1, params=None, blocking=None, corridor=None):
         """blocking: accepted for symmetry with LtvBatch, but only the trivial one ([1] * N): the exact build of the NLP has no
         move-blocked form (LtvBatch.sqp re-linearises a blocked batch)."""
+        if corridor is not None:   # (accepted for symmetry too: the exact build has no corridor form, DESIGN.md 6l)
+            raise NotImplementedError("SqpBatch (the exact build of the NLP, nlp_build_qp) is not available with a corridor; "
+                                      "LtvBatch(..., corridor=...).sqp re-linearises a batch inside a corridor")
         if blocking is not None and len(check_blocking(blocking, N)) != N:
             raise NotImplementedError("SqpBatch (the exact build of the NLP, nlp_build_qp) is not available with move blocking; "
                                       "LtvBatch(..., blocking=...).sqp re-linearises a blocked batch")

@@ -711,6 +711,79 @@ int fsaempc_qp_solve_batch_device_s(const fsaempc_qp_desc* desc, int n_slack,
  * padding included), out[3] = 1 for the one-wavefront kernel, 0 for the workgroup kernel. */
 int fsaempc_qp_layout(const fsaempc_qp_desc* desc, int n_slack, int out[4]);
 
+/* ---- s-varying track corridors -----------------------------------------------------
+ * Everywhere else the track's width is the one number FSAEMPC_P_N_MAX.  A corridor gives the two edges as periodic tables over arc
+ * length, linear between the cells.  Lookup at any finite s, negative values and values past L included: q = s / ds wrapped into
+ * [0, N_w), i = floor(q), u = q - i, value = t[i] + u (t[(i + 1) mod N_w] - t[i]); a constant table returns the constant exactly.
+ * A non-finite s, or one of the two cells read where n_lo < n_hi does not hold, gives NaN for both limits of that lookup only.
+ * The limits are for the car's reference point: the caller subtracts the half-width of the car.  No geometry is derived here: a
+ * caller with cones resamples them over s on the host.  The _c entries take `cor` after `blk`; cor == NULL hands over to the entry
+ * without a corridor and returns its bits.  Before any launch FSAEMPC_ERR_ARG, with the argument named in fsaempc_last_error: a NULL
+ * n_lo or n_hi, N_w < 2, ds not finite or <= 0. */
+typedef struct {
+  const double* n_lo;   /* device; N_w per corridor: least admissible n (right edge, usually < 0) at s_i = i * ds */
+  const double* n_hi;   /* device; N_w per corridor: greatest admissible n (left edge) */
+  int N_w; double ds;   /* cells per lap, ds = L / N_w; periodic */
+  int per_instance;     /* 0: one corridor for the batch; 1: one per instance / plan, instance-major */
+} fsaempc_corridor;
+
+/*
+ * The LTV build and the fused step with the corridor in place of N_MAX.  par and blk may each be NULL: blk == NULL (or one step per
+ * block) is the build of fsaempc_ltv_build_qp_batch_device_p, otherwise that of fsaempc_ltv_build_qp_batch_device_b; sizes, outputs
+ * and errors are theirs.  After the build one more kernel, one thread per (instance, step), overwrites the 2N track-row bounds:
+ *   lbA[2N + k] = n_lo(s_k) - pred_n,k        ubA[3N + k] = n_hi(s_k) - pred_n,k
+ * with s_k = x_lin[k nx + 0], the point the row's coefficients and kappa are linearised at, and pred_n,k entry 1 of step k of
+ * `pred` (required with a corridor).  The 1e10 / -1e10 on the rows' other sides and the matrix A stay.  The first-order term
+ * -n_hi'(s) (s_k - s_lin,k) is left out: the stated approximation.  A block's N_MAX is not read.  A NaN limit (see above) sits in
+ * that row only; the solve answers -1 with iter = 0 for that instance, and its neighbours are unaffected.  In the fused step the
+ * kernel runs between the build and the solve's preparation on `stream`.  Workspace of the step: fsaempc_ltv_workspace_bytes_b
+ * (blk given) or fsaempc_ltv_workspace_bytes (blk == NULL); the corridor needs none.
+ * The exact NLP build, the SQP, the affine maps and the VJPs have no corridor form.
+ */
+int fsaempc_ltv_build_qp_batch_device_c(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const fsaempc_ltv_blocking* blk, const fsaempc_corridor* cor,
+                                        const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream);
+int fsaempc_ltv_step_batch_device_c(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const fsaempc_ltv_blocking* blk, const fsaempc_corridor* cor,
+                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                    void* workspace, long long workspace_bytes, void* stream);
+
+/*
+ * fsaempc_cl_metrics_batch_device against the corridor: N_VIOL_INT and N_VIOL_MAX take v = max(n - n_hi(s), n_lo(s) - n) where
+ * v > 0, at the recorded x0 (s = x0[0], n = x0[1]; NaN limits record no violation).  N_ABS_MAX and every other slot are as there.
+ * per_instance: one corridor per car.
+ */
+int fsaempc_cl_metrics_batch_device_c(int model, int N, double dt, double slack_tol, int batch, const fsaempc_ltv_params* par,
+                                      const fsaempc_corridor* cor,
+                                      const double* x0, const int* finished, const int* exitflag, const int* iter, const double* fval,
+                                      const double* slack, const double* u_drive, const double* cart, double* metrics, void* stream);
+
+/*
+ * fsaempc_plan_raceline_batch_device inside the corridor (same workspace): only the bounds of the line QP change.  Control point j:
+ *   lb_j = max (n_lo(s_i) + margin)        ub_j = min (n_hi(s_i) - margin)
+ * over the plan's cells i whose basis touches c_j, floor(i N_c / N_s) in {j - 2, j - 1, j, j + 1} (cyclic), s_i = i L / N_s.  The
+ * weights are non-negative and sum to one, so the line is inside the corridor minus the margin at every cell.  Sufficient, not
+ * necessary: a pinch is smeared over four knot spacings.  A control point with lb_j >= ub_j (or a NaN limit) gets NaN bounds, so that
+ * plan's QP has non-finite data: its flag is -1 (no iteration) and the plan is NaN in table, t and line, like w_p <= 0 there; the other
+ * plans are unaffected.  Unlike there, NO plan falls back to the centre line: the centre line may lie outside a corridor (a blocked
+ * side, n_hi - margin < 0), so every plan whose flag is not 0 is NaN in table, t and line.  per_instance: one corridor per plan.  A
+ * block's N_MAX is not read.
+ */
+int fsaempc_plan_raceline_batch_device_c(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par,
+                                         const fsaempc_corridor* cor,
+                                         int n_plans, int N_s, int N_c, double margin, double v_cap, double grip,
+                                         const fsaempc_qp_opts* opts, double* line, int* flag, double* table, double* t,
+                                         void* workspace, long long workspace_bytes, void* stream);
+/* The bounds alone, as the call above hands them to the solve (lb, ub: n_plans * N_c each, device; NaN where a control point has no
+ * box): for inspection and timing.  FSAEMPC_ERR_ARG before the launch: the corridor's cases, a NULL pointer, L not finite or <= 0,
+ * N_c, N_s outside the racing line's ranges, n_plans < 1, margin < 0 or not finite. */
+int fsaempc_corridor_line_bounds_device(const fsaempc_corridor* cor, double L, int n_plans, int N_s, int N_c, double margin,
+                                        double* lb, double* ub, void* stream);
+
 /* ---- track pipeline (host side) --------------------------------------------------- */
 
 /* Spline table of a track as main.m:11-17 produces it: M arc-length segments, xP / yP = M x 4 Bezier control points per axis

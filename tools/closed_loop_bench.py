@@ -6,10 +6,13 @@ driving, the exit-flag tally the way main.m:209,222 reports it ("abnormal exits 
 --plan: the cars track a plan of the planner stand-in (fsaempc.Plan.profile) instead of the live ramp to 20 m/s.
 --raceline: the plan is made on a minimum-curvature racing line (fsaempc.Plan.raceline) instead of the centre line.
 --report: the lap report (main.m:196-228 over the batch) joins the JSON line as "lap_report".
+--corridor FILE.npz: an s-varying track corridor (fsaempc.Corridor) from arrays n_lo, n_hi of (N_w,) over the lap of the
+track; the controller's track rows, the report's track violation and, with --raceline, the line's bounds are taken against it.
 --lap: every car starts at s = 0 on the centre line, at rest, with the usual lateral and heading scatter (main.m:63), and the step cap
 defaults to 1000 (main.m:62): a finished car's STEPS * dt is then a lap time.
 usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--track fss2019]
-                                  [--plan | --raceline [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap]"""
+                                  [--plan | --raceline [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap]
+                                  [--corridor FILE.npz]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -37,15 +40,20 @@ def main():
     ap.add_argument("--raceline", action="store_true", help="track a plan on a minimum-curvature racing line (Plan.raceline); takes --grip and --cells too")
     ap.add_argument("--margin", type=float, default=0.25, help="with --raceline: distance the line keeps from N_MAX, m")
     ap.add_argument("--points", type=int, default=100, help="with --raceline: control points of the line (N_c)")
+    ap.add_argument("--corridor", default=None, metavar="FILE.npz", help="track corridor: arrays n_lo, n_hi of (N_w,) over the lap (Corridor.from_table)")
     a = ap.parse_args()
     if a.steps is None:
         a.steps = 1000 if a.lap else 200
     model = fm.KINEMATIC if a.model == "kinematic" else fm.DYNAMIC
     tr = fm.Track.load(a.track)
+    cor = None
+    if a.corridor is not None:
+        with np.load(a.corridor) as z:
+            cor = fm.Corridor.from_table(z["n_lo"], z["n_hi"], tr.L)
     plan = fm.Plan.profile(model, tr, N_s=a.cells, grip=a.grip) if a.plan else None
     if a.raceline:
-        plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip)
-    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan)          # warm-up (allocations, code load)
+        plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip, corridor=cor)
+    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor)          # warm-up (allocations, code load)
     n_max = float(fm.default_params(model)[fm.PARAM_INDEX["N_MAX"]])
     opts = fm.default_opts(max_iter=a.max_iter)
     t0 = time.perf_counter()
@@ -53,7 +61,7 @@ def main():
     # every car while it drives
     cart0, s_init = fm.monte_carlo_carts(tr, a.batch, a.seed, lap=a.lap)
     cl = fm.ClosedLoop(model, a.horizon, 0.05, tr, cart0, options=opts, warm_start=a.warm, launch_hint=not a.no_launch_hint, reference=plan,
-                       metrics=a.report, slack_tol=a.slack_tol)
+                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]
     fl_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
@@ -88,7 +96,7 @@ def main():
         "config": {"workload": "BASELINE configs[3] share of one GPU: %d cars on %s, %d receding-horizon steps, every step one batch of QPs "
                                "(frame transform + reference + linearise/condense/solve + PID/plant, device-resident loop, no per-step read-back; "
                                "wall time includes the allocation of the run)" % (a.batch, a.track, a.steps),
-                   "track": a.track, "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
+                   "track": a.track, "corridor": a.corridor, "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
                    # (a mean over an empty set is NaN in the report: null in the JSON line)
                    **({"lap_report": {k: (None if v != v else v) for k, v in cl.report().summary().items()}, "slack_tol": a.slack_tol} if a.report else {}),
                    "qps_of_driving_cars": n_act, "qps_total_launched": int(a.batch * a.steps),

@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""What a track corridor costs, and the corridor file of the driven-lap comparison.
+  --make TRACK OUT.npz   writes n_lo, n_hi of (N_w,) for tools/closed_loop_bench.py --corridor: +-WIDE where |kappa| < KAPPA, +-NARROW
+                         elsewhere (defaults 1.5 m, 0.02 1/m, 0.75 m; N_w 500); kappa from the track's Bezier table on the host.
+  default                one JSON line: the fused step with a (constant) corridor (_c entry) against the step without one (kinematic N = 40,
+                         B = 4096, same process, median of 20 launches after 5 warm-ups, HIP events), and Plan.raceline with and
+                         without a corridor (N_s 500, N_c 100) and the line's control-point bounds kernel alone, measured the same way.
+usage: tools/corridor_bench.py [--make TRACK OUT.npz [--wide W] [--narrow W] [--kappa K] [--cells N_w]] [--batch 4096] [--horizon 40]"""
+import argparse, json, os, sys
+import numpy as np
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def kappa_host(tr, s):
+    """curvature of the centre line at s from the M x 4 Bezier tables (first and second derivative in the segment's own parameter)"""
+    r = np.mod(s, tr.dl * tr.M); i = np.minimum(np.floor(r / tr.dl).astype(int), tr.M - 1); u = r / tr.dl - i; w = 1 - u
+
+    def d12(P):
+        d1 = 3 * (w * w * (P[i, 1] - P[i, 0]) + 2 * w * u * (P[i, 2] - P[i, 1]) + u * u * (P[i, 3] - P[i, 2])) / tr.dl
+        d2 = 6 * (w * (P[i, 2] - 2 * P[i, 1] + P[i, 0]) + u * (P[i, 3] - 2 * P[i, 2] + P[i, 1])) / tr.dl ** 2
+        return d1, d2
+    (xd, xdd), (yd, ydd) = d12(np.asarray(tr.xP)), d12(np.asarray(tr.yP))
+    return (xd * ydd - yd * xdd) / (xd * xd + yd * yd) ** 1.5
+
+
+def median_ms(torch, fn, warm=5, reps=20):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); fn(); b.record(); b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts)), float(np.min(ts)), float(np.max(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--make", nargs=2, metavar=("TRACK", "OUT.npz"), default=None)
+    ap.add_argument("--wide", type=float, default=1.5)
+    ap.add_argument("--narrow", type=float, default=0.75)
+    ap.add_argument("--kappa", type=float, default=0.02)
+    ap.add_argument("--cells", type=int, default=500)
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--horizon", type=int, default=40)
+    a = ap.parse_args()
+    import fsae_mpc_amd as fm
+    if a.make is not None:
+        tr = fm.Track.load(a.make[0])
+        s = np.arange(a.cells) * tr.L / a.cells
+        w = np.where(np.abs(kappa_host(tr, s)) < a.kappa, a.wide, a.narrow)
+        np.savez(a.make[1], n_lo=-w, n_hi=w)
+        print(json.dumps({"track": a.make[0], "cells": a.cells, "wide_share": float((w == a.wide).mean()), "file": a.make[1]}))
+        return
+    import torch
+    tr = fm.Track.load("fsg2019")
+    model, N, B = fm.KINEMATIC, a.horizon, a.batch
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    x0, xl, ul, xr = (dev(v) for v in fm.instances(model, N, 0.05, tr.L, 20190, range(B)))
+    cor = fm.Corridor.constant(tr.L, 0.75, N_w=500)   # +-N_MAX: the QPs keep their bits, so the difference is the corridor's kernels alone
+    plain, inside = fm.LtvBatch(model, N, 0.05, tr, B), fm.LtvBatch(model, N, 0.05, tr, B, corridor=cor)
+    t_plain = median_ms(torch, lambda: plain.step(x0, xr, xl, ul))
+    t_cor = median_ms(torch, lambda: inside.step(x0, xr, xl, ul))
+    t_plain2 = median_ms(torch, lambda: plain.step(x0, xr, xl, ul))
+    l_plain = median_ms(torch, lambda: fm.Plan.raceline(model, tr, N_s=500, N_c=100))
+    l_cor = median_ms(torch, lambda: fm.Plan.raceline(model, tr, N_s=500, N_c=100, corridor=cor))
+    # the control-point bounds kernel on its own (fsaempc_corridor_line_bounds_device), one plan and 256 plans
+    cor256 = fm.Corridor.from_table(np.tile(cor.n_lo.cpu().numpy(), (256, 1)), np.tile(cor.n_hi.cpu().numpy(), (256, 1)), tr.L)
+    b_1 = median_ms(torch, lambda: cor.line_bounds(500, 100, 0.25))
+    b_256 = median_ms(torch, lambda: cor256.line_bounds(500, 100, 0.25))
+    print(json.dumps({"what": "median / min / max ms of 20 launches after 5 warm-ups, HIP events, one process; the corridor is the constant +-0.75 "
+                              "(500 cells): the same QPs bit for bit with and without it",
+                      "step": {"model": "kinematic", "N": N, "B": B, "without_corridor_ms": t_plain, "with_corridor_ms": t_cor,
+                               "without_corridor_again_ms": t_plain2},
+                      "raceline": {"N_s": 500, "N_c": 100, "without_corridor_ms": l_plain, "with_corridor_ms": l_cor,
+                                   "note": "whole Plan.raceline call, allocations included"},
+                      "line_bounds_kernel": {"N_s": 500, "N_c": 100, "one_plan_ms": b_1, "plans_256_ms": b_256,
+                                             "note": "the bounds call alone (two output allocations and one launch between the events)"}}))
+
+
+if __name__ == "__main__":
+    main()
