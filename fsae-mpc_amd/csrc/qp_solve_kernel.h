@@ -24,6 +24,11 @@
 #ifndef QP_STARTUP_ATW
 #define QP_STARTUP_ATW 0
 #endif
+// slots per load batch of the iteration's row sweeps where SweepBatch<T, NB> does not hold an instantiation at 2 (A/B builds: 2 is
+// the former pairwise sweep; profiles/row_sweeps/README.md)
+#ifndef QP_SWEEP_BATCH
+#define QP_SWEEP_BATCH 6
+#endif
 
 namespace {
 
@@ -660,6 +665,12 @@ template <int FORM> DEVINL int diag_factor(const Ctx& k, v4d& Ud, v4d& Yk, v4d& 
 // or better.
 template <int T, int NB> struct DiagForm { static constexpr int form = (T == 5 && NB > 0) ? QP_DIAG_FLAT : 0; };
 
+// How many owner-layout slots a row sweep of the iteration (row phase 2, step length, update) loads before it runs their bodies:
+// one exposed global round trip per batch instead of one per pair of slots.  The bodies still run in ascending slot order, so the
+// sums and the blocking-pair scan are those of the pairwise sweep, bit for bit.  An instantiation that the wider batch costs
+// scratch or spilled vector registers keeps the former 2 (profiles/row_sweeps/resource_usage.txt).
+template <int T, int NB> struct SweepBatch { static constexpr int nsb = (T == 5 && NB > 0) ? QP_SWEEP_BATCH : 2; };
+
 // Blocked Cholesky of acc (upper tiles) in place.  Yt[K] = U_KK^-T stays in LDS (YL) for the solves.
 template <int T, int NB, int K> struct FactorStep {
   static DEVINL int run(const Ctx& k, v4d* acc, double* YL, double floor_abs) {
@@ -1066,6 +1077,31 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     s_.va = aVA[ix]; s_.vc = aVC[ix]; s_.w2 = aW2[ix]; s_.rpl = aRPL[ix]; s_.rpu = aRPU[ix];
     return s_;
   };
+  // What a variable-bound slot (js >= J) takes from the n-vectors: row `lane` of slot J + h is element i = lane + 64 h, which this
+  // very lane holds or reads from LDS, so these values make no trip through the row arrays (whose bound parts of VA, VC, W2 the
+  // iteration no longer writes: load_slot's values for them are replaced before a body sees them).
+  struct BoundVals { double va[2], vc[2], w2[2]; };
+  auto bound_dirs = [&](BoundVals& bv) {   // va, vc of the bound slots: the affine / centering directions in R1, R2
+    for (int h = 0; h < 2; ++h) { const int i = lane + 64 * h; bv.va[h] = i < n ? R1[i] : 0.0; bv.vc[h] = i < n ? R2[i] : 0.0; }
+  };
+  // One row sweep: NSB slots per trip, all their loads issued before the first body runs; slots past JT are clamped and invalid
+  // (load_slot), so JT need not be a multiple of NSB.  Bodies run in ascending js.
+  constexpr int NSB = SweepBatch<T, NB>::nsb;
+  auto sweep = [&](const BoundVals& bv, auto&& body) __attribute__((always_inline)) {
+    for (int js0 = 0; js0 < JT; js0 += NSB) {
+      Slot r[NSB];
+#pragma unroll
+      for (int e = 0; e < NSB; ++e) r[e] = load_slot(js0 + e);
+#pragma unroll
+      for (int e = 0; e < NSB; ++e) {
+        const int js = js0 + e;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          if (js == J + h) { r[e].va = bv.va[h]; r[e].vc = bv.vc[h]; r[e].w2 = bv.w2[h]; }
+        body(r[e], js);
+      }
+    }
+  };
   double gap = 0.0, rp_rel = 0.0;   // carried across iterations (produced by the update sweep)
 
   v4d acc[NT];          // upper tiles of M, then of its Cholesky factor U
@@ -1268,12 +1304,16 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     WAVE_SYNC();
     STAMP(3);
     // objective, dual residual
-    double fl = 0, m_rd = 0;
+    // (the bound rows' weights of the two right-hand sides below are loaded here with W3: one round trip for the block, not two)
+    double fl = 0, m_rd = 0, w1b[2] = {0.0, 0.0}, w2b[2] = {0.0, 0.0}, w3b[2] = {0.0, 0.0};
+    for (int h = 0; h < 2; ++h) {
+      const int i = lane + 64 * h;
+      if (i < n) { const int ix = (J + (i >> 6)) * 64 + (i & 63); w3b[h] = aW3[ix]; w1b[h] = aW1[ix]; w2b[h] = aW2[ix]; }
+    }
     for (int h = 0; h < 2; ++h) {
       const int i = lane + 64 * h;
       if (i < n) {
-        const int ix = (J + (i >> 6)) * 64 + (i & 63);
-        const double gz = P3[i] + aW3[ix];
+        const double gz = P3[i] + w3b[h];
         fl += 0.5 * X[i] * HX[i] + G[i] * X[i];
         const double sc = fmax(1.0, fmax(fabs(G[i]), fmax(fabs(HX[i]), fabs(gz))));
         m_rd = fmax(m_rd, fabs(HX[i] + G[i] - gz) / sc);
@@ -1333,9 +1373,8 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     for (int h = 0; h < 2; ++h) {
       const int i = lane + 64 * h;
       if (i < k.np) {
-        const int ix = (J + (i >> 6)) * 64 + (i & 63);
-        R1[i] = i < n ? -(HX[i] + G[i]) + P1[i] + aW1[ix] : 0.0;
-        R2[i] = i < n ? P2[i] + aW2[ix] : 0.0;
+        R1[i] = i < n ? -(HX[i] + G[i]) + P1[i] + w1b[h] : 0.0;
+        R2[i] = i < n ? P2[i] + w2b[h] : 0.0;
       }
     }
     STAMP(4);
@@ -1368,16 +1407,15 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     {
       const double* vin[2] = {R1, R2}; double* rout[2] = {aVA, aVC};
       pass_Av<T, NB, 2, 1>(k, st, vin, rout, P1);   // fused: P1 = A~' w_cor
-      for (int jb = 0; jb < k.JB; ++jb) {
-        const int i = jb * 64 + lane;
-        aVA[(J + jb) * 64 + lane] = i < n ? R1[i] : 0.0;
-        aVC[(J + jb) * 64 + lane] = i < n ? R2[i] : 0.0;
-      }
     }
+    BoundVals bv;   // the variable-bound rows' va = dxa, vc = dxc come straight from R1, R2 (bound_dirs)
+    bound_dirs(bv);
+    bv.w2[0] = bv.w2[1] = 0.0;
     STAMP(7);
     // ================= row phase 2: affine step length, sigma, corrector weights (one sweep) =================
     // mu_aff(alpha) = [S0 + alpha S1 + alpha^2 S2]/cnt with S0 = sum t z, S1 = sum (t dz + z dt), S2 = sum dt dz
     double a_aff = 1.0, s1 = 0.0, s2 = 0.0;
+    double wb[2] = {0.0, 0.0};   // second-order weight of this lane's variable-bound rows (slots J, J + 1): the corrector's right-hand side reads it
     auto row2_body = [&](const Slot& r, int js) {
       const bool hl = r.valid && r.l > -INFINITY, hu = r.valid && r.u < INFINITY;
       double w = 0.0;
@@ -1395,12 +1433,10 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
         s1 += r.tu * dz + r.zu * dt; s2 += dt * dz;
         w += dt * dz / r.tu;
       }
-      if (js >= J && js < JT) aW1[r.ix] = w;   // second-order weight of the variable-bound rows (A rows: fused in pass 2)
+      if (js == J) wb[0] = w;       // (A rows: fused in pass 2; an invalid slot has w = 0)
+      if (js == J + 1) wb[1] = w;
     };
-    for (int js = 0; js < JT; js += 2) {
-      const Slot r0 = load_slot(js), r1 = load_slot(js + 1);
-      row2_body(r0, js); row2_body(r1, js + 1);
-    }
+    sweep(bv, row2_body);
     a_aff = wave_min(a_aff);
     s1 = wave_sum(s1); s2 = wave_sum(s2);
     const double mu_aff = fmax(0.0, gap + a_aff * (s1 + a_aff * s2)) / cnt;
@@ -1421,7 +1457,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     STAMP(9);
     for (int h = 0; h < 2; ++h) {
       const int i = lane + 64 * h;
-      if (i < k.np) { const int ix = (J + (i >> 6)) * 64 + (i & 63); DX[i] = i < n ? P1[i] + aW1[ix] : 0.0; }
+      if (i < k.np) DX[i] = i < n ? P1[i] + wb[h] : 0.0;
     }
     WAVE_SYNC();
     solve1(DX);
@@ -1431,14 +1467,16 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     {
       const double* vin[1] = {DX}; double* rout[1] = {aW2};  // W2 reused for G dx_cor
       pass_Av<T, NB, 1, 0>(k, st, vin, rout, nullptr);
-      for (int jb = 0; jb < k.JB; ++jb) { const int i = jb * 64 + lane; aW2[(J + jb) * 64 + lane] = i < n ? DX[i] : 0.0; }
     }
     STAMP(11);
     } else {   // no corrector this iteration
       for (int i = lane; i < k.np; i += 64) DX[i] = 0.0;
-      for (int js = 0; js < JT; ++js) aW2[js * 64 + lane] = 0.0;
+      for (int js = 0; js < J; ++js) aW2[js * 64 + lane] = 0.0;
       WAVE_SYNC();
     }
+    // the bound rows' G dx_cor is dx_cor itself: taken here, before DX becomes the full direction
+    bound_dirs(bv);
+    for (int h = 0; h < 2; ++h) { const int i = lane + 64 * h; bv.w2[h] = i < n ? DX[i] : 0.0; }
     // full direction dx = dxa + smu*dxc + dxcor ; dv likewise
     for (int h = 0; h < 2; ++h) {
       const int i = lane + 64 * h;
@@ -1446,10 +1484,13 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     }
     // ================= row phase 3: step length (Mehrotra heuristic on the blocking pair), update =================
     double amax = 1e300, bp = 0, bdp = 0, bd = 0, bdd = 0, q1 = 0.0, q2 = 0.0;
+    double dvb[2] = {0.0, 0.0};
     auto row3a_body = [&](const Slot& r, int js) {
       const bool hl = r.valid && r.l > -INFINITY, hu = r.valid && r.u < INFINITY;
       const double dv = r.va + smu * r.vc + r.w2;
-      if (js < JT) aVC[r.ix] = dv;  // keep the full G dx for the update
+      if (js < J) aVC[r.ix] = dv;  // keep the full G dx for the update (variable-bound slots: in dvb)
+      if (js == J) dvb[0] = dv;
+      if (js == J + 1) dvb[1] = dv;
       if (hl) {
         const double dta = r.va + r.rpl, dza = -r.zl - (r.zl / r.tl) * dta;
         const double cl = smu - cw * dta * dza;
@@ -1467,10 +1508,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
         q1 += r.tu * dz + r.zu * dt; q2 += dt * dz;
       }
     };
-    for (int js = 0; js < JT; js += 2) {
-      const Slot r0 = load_slot(js), r1 = load_slot(js + 1);
-      row3a_body(r0, js); row3a_body(r1, js + 1);
-    }
+    sweep(bv, row3a_body);
     const double amax_w = wave_min(amax);
     double alpha = 1.0;
     if (amax_w < 1e299) {
@@ -1491,7 +1529,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     }
     if (P.dump && b == 0 && P.dump_stage == 4 && it == P.dump_iter) {   // debug: step-length pipeline of this iteration
       double c1 = 0, c2 = 0, c3 = 0, c4 = 0;
-      for (int js = 0; js < JT; ++js) { const int ix = js * 64 + lane; c1 += aVA[ix]; c2 += aVC[ix]; c3 += aW2[ix]; c4 += aW1[ix]; }
+      for (int js = 0; js < J; ++js) { const int ix = js * 64 + lane; c1 += aVA[ix]; c2 += aVC[ix]; c3 += aW2[ix]; c4 += aW1[ix]; }   // (A rows: the bound rows' parts never reach these arrays)
       c1 = wave_sum(c1); c2 = wave_sum(c2); c3 = wave_sum(c3); c4 = wave_sum(c4);
       if (lane == 0) {
         double* o_ = P.dump;
@@ -1528,10 +1566,8 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
       aV[r.ix] = v;
       row1_body(r.ix, r.valid, r.l, r.u, v, tl, tu, zl, zu, s_gap, m_rp);
     };
-    for (int js = 0; js < JT; js += 2) {
-      const Slot r0 = load_slot(js), r1 = load_slot(js + 1);
-      row3b_body(r0, js); row3b_body(r1, js + 1);
-    }
+    bv.vc[0] = dvb[0]; bv.vc[1] = dvb[1];   // (row3b_body reads the slot's full G dx as its vc)
+    sweep(bv, row3b_body);
     for (int h = 0; h < 2; ++h) {
       const int i = lane + 64 * h;
       if (i < n) { X[i] += alpha * DX[i]; xn = fmax(xn, fabs(X[i])); }

@@ -10,7 +10,8 @@ import sys
 
 COLS = [("mov0", r"v_mov_b32(_e32)? v\d+, 0$"), ("movdpp", r"v_mov_b32_dpp"), ("snop", r"s_nop"), ("fma", r"v_(fma|fmac)_f64"),
         ("add", r"v_add_f64"), ("mul", r"v_mul_f64"), ("mfma", r"v_mfma"), ("rsq", r"v_rsq_f64"), ("saveexec", r"s_and_saveexec"),
-        ("execz", r"s_cbranch_execz"), ("readlane", r"v_readlane"), ("accvgpr", r"v_accvgpr_"), ("cndmask", r"v_cndmask")]
+        ("execz", r"s_cbranch_execz"), ("readlane", r"v_readlane"), ("accvgpr", r"v_accvgpr_"), ("cndmask", r"v_cndmask"),
+        ("gload", r"global_load"), ("gstore", r"global_store"), ("vmwait", r"s_waitcnt.*vmcnt")]
 USAGE = ["codeLenInByte", "TotalNumSgprs", "NumVgprs", "NumAgprs", "ScratchSize", "Occupancy"]
 
 
