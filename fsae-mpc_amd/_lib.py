@@ -30,6 +30,7 @@ EXPORTS = [
     "fsaempc_cl_metrics_batch_device", "fsaempc_cl_report",
     "fsaempc_ltv_build_qp_batch_device_c", "fsaempc_ltv_step_batch_device_c", "fsaempc_cl_metrics_batch_device_c",
     "fsaempc_plan_raceline_batch_device_c", "fsaempc_corridor_line_bounds_device",
+    "fsaempc_cl_lap_gate_batch_device", "fsaempc_cl_lap_summary",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -50,6 +51,19 @@ REPORT_INDEX = {name: i for i, name in enumerate(
     ["CARS_DRIVING", "CARS_FINISHED", "CARS_LOST", "LAP_MEAN", "LAP_MIN", "LAP_MAX", "STEPS", "ABNORMAL_PCT", "SLACK_N_PCT", "SLACK_TYRE_PCT",
      "OBJ_MEAN", "N_VIOL_INT_MEAN", "N_VIOL_INT_MAX", "N_VIOL_MAX", "ELL_VIOL_INT_MEAN", "ELL_VIOL_INT_MAX", "ELL_VIOL_MAX", "ITER_MEAN",
      "ITER_MAX", "N_ABS_MAX"])}
+# per-car state of the lap gate (include/fsaempc.h FSAEMPC_LS_*; tests check the table against the header's macros)
+MAX_LAPS = 64
+NLAPSTATE = 4
+LAP_STATE_INDEX = {name: i for i, name in enumerate(["DONE", "STEPS", "S_PREV", "T_CROSS"])}
+
+
+def check_laps(laps):
+    """Validates a lap count (no library call) and returns it as an int."""
+    if isinstance(laps, bool) or int(laps) != laps:
+        raise ValueError("laps must be an integer")
+    if not 1 <= int(laps) <= MAX_LAPS:
+        raise ValueError("laps must be 1 .. %d" % MAX_LAPS)
+    return int(laps)
 
 
 class QpOpts(C.Structure):
@@ -245,6 +259,8 @@ def lib():
         L.fsaempc_plan_raceline_batch_device_c.argtypes = [C.c_int, C.POINTER(Spline), C.c_double, C.POINTER(LtvParams), C.POINTER(CorridorTable),
                                                            C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(QpOpts),
                                                            vp, vp, vp, vp, vp, ll, vp]
+        L.fsaempc_cl_lap_gate_batch_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 9
+        L.fsaempc_cl_lap_summary.argtypes = [vp, C.c_int, C.c_int, vp]
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p
         L.fsaempc_track_from_csv.argtypes = [C.c_char_p, C.c_int, C.POINTER(TrackTable)]

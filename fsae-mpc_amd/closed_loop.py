@@ -4,7 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import METRIC_INDEX, NMETRIC, NREPORT, REPORT_INDEX, ParamBlock, Spline, check, check_blocking, lib
+from ._lib import (LAP_STATE_INDEX, METRIC_INDEX, NLAPSTATE, NMETRIC, NREPORT, REPORT_INDEX, ParamBlock, Spline, check, check_blocking,
+                   check_laps, lib)
 from .ltvmpc import LtvBatch, dims
 from .corridor import check_corridor
 from .plan import Plan
@@ -13,14 +14,41 @@ from .plan import Plan
 class LapReport:
     """The per-car records of a closed-loop run (include/fsaempc.h FSAEMPC_M_*; main.m:196-228 per car) on the host.  Every slot is an
     attribute by its lower-case name (steps, status, n_viol_int, ...), one entry per car; lap_time = steps * dt (a lap only for
-    the cars with status == 1).  summary() is the batch summary of fsaempc_cl_report as a dict (lower-case FSAEMPC_R_* names)."""
+    the cars with status == 1).  summary() is the batch summary of fsaempc_cl_report as a dict (lower-case FSAEMPC_R_* names).
 
-    def __init__(self, metrics, dt):
+    Multi-lap runs (ClosedLoop(laps > 1)) hand in what the lap gate kept: lap_times (B, laps) with NaN for a lap not
+    completed, lap_state (B, 4) and lap_records (B, laps, 16).  Then `metrics` -- and with it every slot attribute and summary() -- is the
+    record of the lap each car is driving (or of its last lap, once it finished); laps_done counts the completed laps; lap_records holds
+    rows 0 .. laps_done - 1 from the gate and the car's current or latched record in row laps_done (row laps - 1 for a car that finished);
+    lap_time is the sum of the completed laps' times.  Without them (laps == 1) the same attributes describe the single lap: laps_done is
+    1 for a finished car, lap_times (B, 1) is its lap_time (NaN for the others), lap_records (B, 1, 16) is metrics.  lap_summary() is the
+    (laps, 4) table of fsaempc_cl_lap_summary: per lap the cars that completed it, then mean, min and max of its time."""
+
+    def __init__(self, metrics, dt, lap_times=None, lap_state=None, lap_records=None):
         self.metrics = np.ascontiguousarray(np.asarray(metrics, dtype=np.float64).reshape(-1, NMETRIC))
         self.dt = float(dt)
         for name, i in METRIC_INDEX.items():
             setattr(self, name.lower(), self.metrics[:, i])
-        self.lap_time = self.steps * self.dt
+        B = self.metrics.shape[0]
+        if lap_times is None:
+            self.laps = 1
+            self.lap_time = self.steps * self.dt
+            self.laps_done = (self.status == 1.0).astype(np.int64)
+            self.lap_times = np.where(self.status == 1.0, self.lap_time, np.nan).reshape(B, 1)
+            self.lap_records = self.metrics.reshape(B, 1, NMETRIC)
+            return
+        self.lap_times = np.ascontiguousarray(np.asarray(lap_times, dtype=np.float64).reshape(B, -1))
+        self.laps = self.lap_times.shape[1]
+        self.laps_done = np.asarray(lap_state, dtype=np.float64).reshape(B, NLAPSTATE)[:, LAP_STATE_INDEX["DONE"]].astype(np.int64)
+        self.lap_records = np.array(np.asarray(lap_records, dtype=np.float64).reshape(B, self.laps, NMETRIC))
+        self.lap_records[np.arange(B), np.minimum(self.laps_done, self.laps - 1)] = self.metrics
+        self.lap_time = np.where(np.isnan(self.lap_times), 0.0, self.lap_times).sum(axis=1)
+
+    def lap_summary(self):
+        out = np.zeros((self.laps, 4))
+        check(lib().fsaempc_cl_lap_summary(C.c_void_p(self.lap_times.ctypes.data) if self.lap_times.size else None, self.lap_times.shape[0], self.laps,
+                                           C.c_void_p(out.ctypes.data)), "fsaempc_cl_lap_summary")
+        return out
 
     def summary(self):
         out = np.zeros(NREPORT)
@@ -36,7 +64,7 @@ class ClosedLoop:
     plan -- and the exit flags are only tallied.  Cars that completed the lap (s >= L) or left the track keep their state."""
 
     def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
-                 params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6, corridor=None):
+                 params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6, corridor=None, laps=1):
         """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
         None = the same as params (both None: the reference's constants compiled into the kernels).  blocking: block lengths of the
         controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2).  reference: None = the live
@@ -45,9 +73,13 @@ class ClosedLoop:
         kernel per step, on the same stream; limits and ellipse axes are those of params) -- report() reads them back.  slack_tol: a slack
         counts as in use above it (the reference tests == 0; 1e-6 is this build's solve tolerance).  corridor: None or a Corridor (shared,
         or one per car): the controller's track rows and, with metrics, the report's track violation are taken against it
-        (DESIGN.md 6l)."""
+        (DESIGN.md 6l).  laps: 1 = the run of a car ends the first time s >= L (main.m:102-104); K > 1 = the lap gate (lap_gate(), one more
+        kernel per step between pre() and the MPC step) carries it over the line K - 1 times: self.lap_times (B, K) holds the laps' times
+        to a fraction of dt (NaN: not completed), self.lap_state (B, 4) the gate's state (LAP_STATE_INDEX), and with metrics
+        self.lap_records (B, K, 16) the closed laps' records while self.metrics is the record of the lap being driven."""
         if not (float(slack_tol) >= 0):
             raise ValueError("slack_tol must be >= 0")
+        self.laps = check_laps(laps)   # (before the library is touched)
         if blocking is not None:
             check_blocking(blocking, N)   # (before the library is touched)
         if reference is not None:
@@ -88,6 +120,9 @@ class ClosedLoop:
         self.steps = 0
         self.slack_tol = float(slack_tol)
         self.metrics = torch.zeros((self.B, NMETRIC), dtype=torch.float64, device=self.device) if metrics else None
+        self.lap_state = self.lap_times = self.lap_records = None   # laps == 1: nothing is allocated unless lap_gate() is called
+        if self.laps > 1:
+            self._lap_alloc()
         # warm_start: every solve starts from the plan of the previous period shifted by one stage (fsaempc_qp_aux.x_init): the
         # inputs u_1..u_{N-1}, the last stage repeated, the previous slack values.  Off by default -- the reference's loop solves
         # cold (main.m:117-120 passes no initial guess) and the gain is modest (profiles/round3/warm_start_ab.json)
@@ -118,6 +153,23 @@ class ClosedLoop:
                                                P(self.finished), self._stream(stream))
         check(rc, "fsaempc_cl_pre_batch_device")
 
+    def _lap_alloc(self):
+        torch = self.torch
+        self.lap_state = torch.zeros((self.B, NLAPSTATE), dtype=torch.float64, device=self.device)
+        self.lap_times = torch.full((self.B, self.laps), float("nan"), dtype=torch.float64, device=self.device)
+        if self.metrics is not None:
+            self.lap_records = torch.zeros((self.B, self.laps, NMETRIC), dtype=torch.float64, device=self.device)
+
+    def lap_gate(self, stream=None):
+        """The lap gate on what pre() left (fsaempc_cl_lap_gate_batch_device): step() calls it after pre() when laps > 1."""
+        if self.lap_state is None:
+            self._lap_alloc()
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(lib().fsaempc_cl_lap_gate_batch_device(self.nx, self.N, C.c_double(self.dt), C.c_double(self.track.L), self.laps, self.B, P(self.x0),
+                                                     P(self.x_ref), P(self.x_opt), P(self.finished), P(self.lap_state), P(self.lap_times),
+                                                     P(self.metrics) if self.lap_records is not None else None, P(self.lap_records),
+                                                     self._stream(stream)), "fsaempc_cl_lap_gate_batch_device")
+
     def plant(self, exitflag, stream=None):
         P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         if self.plant_params is not None:
@@ -131,6 +183,8 @@ class ClosedLoop:
     def step(self, stream=None):
         torch = self.torch
         self.pre(stream)
+        if self.laps > 1:
+            self.lap_gate(stream)
         x_init = None
         if self.warm_start and self.steps > 0:
             N = self.N
@@ -171,7 +225,9 @@ class ClosedLoop:
         """The lap report so far (LapReport): one read-back of self.metrics."""
         if self.metrics is None:
             raise ValueError("ClosedLoop(metrics=True) keeps the records report() reads")
-        return LapReport(self.metrics.cpu().numpy(), self.dt)
+        if self.lap_records is None:
+            return LapReport(self.metrics.cpu().numpy(), self.dt)
+        return LapReport(self.metrics.cpu().numpy(), self.dt, self.lap_times.cpu().numpy(), self.lap_state.cpu().numpy(), self.lap_records.cpu().numpy())
 
 
 def monte_carlo_carts(track, B, seed, lap=False):
@@ -196,16 +252,16 @@ def monte_carlo_carts(track, B, seed, lap=False):
 
 
 def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
-                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None):
+                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
     reference: None (the live ramp) or a Plan the cars track (ClosedLoop).  metrics: ClosedLoop(metrics=True); cl.report() afterwards.
-    corridor: None or a Corridor (ClosedLoop).
+    corridor: None or a Corridor (ClosedLoop).  laps: ClosedLoop(laps=...); cl.lap_times afterwards.
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
     import torch
     cart0, s_init = monte_carlo_carts(track, B, seed)
     cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
-                    params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics, corridor=corridor)
+                    params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics, corridor=corridor, laps=laps)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

@@ -1080,6 +1080,42 @@ int fsaempc_cl_report(const double* metrics_host, int batch, double dt, double* 
   return 0;
 }
 
+/* ---- multi-lap closed loop: the lap gate ---- */
+int fsaempc_cl_lap_gate_batch_device(int nx, int N, double dt, double L, int laps, int batch, double* x0, double* x_ref, double* x_keep,
+                                     int* finished, double* lap_state, double* lap_times, double* metrics, double* lap_records, void* stream) {
+  if (laps < 1 || laps > FSAEMPC_MAX_LAPS) return fail(FSAEMPC_ERR_ARG, "laps must be 1 .. FSAEMPC_MAX_LAPS");
+  if (nx != 5 && nx != 7) return fail(FSAEMPC_ERR_ARG, "nx must be 5 or 7");
+  if (N < 1 || batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (!pos_finite(dt) || !pos_finite(L)) return fail(FSAEMPC_ERR_ARG, "dt and L must be finite and > 0");
+  if (!x0 || !x_ref || !x_keep || !finished || !lap_state || !lap_times) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if ((metrics == nullptr) != (lap_records == nullptr)) return fail(FSAEMPC_ERR_ARG, "metrics and lap_records are given together or not at all");
+  if (batch == 0) return 0;
+  ClLapGateParams P; P.nx = nx; P.N = N; P.laps = laps; P.batch = batch; P.dt = dt; P.L = L; P.x0 = x0; P.x_ref = x_ref; P.x_keep = x_keep;
+  P.finished = finished; P.lap_state = lap_state; P.lap_times = lap_times; P.metrics = metrics; P.lap_records = lap_records;
+  hipError_t e = cl_lap_gate_launch(P, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "cl_lap_gate_launch");
+  return 0;
+}
+
+// Host.  Every sum runs over the cars in index order; a lap nobody completed has NaN mean, min and max.
+int fsaempc_cl_lap_summary(const double* lap_times_host, int batch, int laps, double* out) {
+  if (!out || (!lap_times_host && batch != 0)) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (laps < 1 || laps > FSAEMPC_MAX_LAPS) return fail(FSAEMPC_ERR_ARG, "laps must be 1 .. FSAEMPC_MAX_LAPS");
+  for (int l = 0; l < laps; ++l) {
+    double cnt = 0, sum = 0, lo = NAN, hi = NAN;
+    for (int b = 0; b < batch; ++b) {
+      const double t = lap_times_host[(size_t)b * laps + l];
+      if (t != t) continue;
+      cnt += 1; sum += t;
+      if (!(lo <= t)) lo = t;
+      if (!(hi >= t)) hi = t;
+    }
+    out[4 * l] = cnt; out[4 * l + 1] = cnt > 0 ? sum / cnt : NAN; out[4 * l + 2] = lo; out[4 * l + 3] = hi;
+  }
+  return 0;
+}
+
 /* ---- s-domain plans ---- */
 static int plan_check(const fsaempc_plan* plan, PlanTable* out) {
   if (!plan || !plan->table || !plan->t) return fail(FSAEMPC_ERR_ARG, "null argument");

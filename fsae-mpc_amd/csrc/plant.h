@@ -33,6 +33,19 @@ struct ClMetricsParams {   // lap report (include/fsaempc.h FSAEMPC_M_*): inputs
   const double* cart;      // batch x 7, post-plant
   double* metrics;         // batch x FSAEMPC_NMETRIC, in/out
 };
+struct ClLapGateParams {   // lap gate (include/fsaempc.h FSAEMPC_LS_*): between the pre-step and the MPC step, all per car
+  int nx, N, laps, batch;
+  double dt, L;
+  double* x0;              // batch x nx, in/out (entry 0 = s)
+  double* x_ref;           // batch x (nx x N), in/out (column 0 of every stage)
+  double* x_keep;          // batch x (nx x N), in/out: the kept plan (column 0 of every stage)
+  int* finished;           // as the pre-step left it, in/out
+  double* lap_state;       // batch x FSAEMPC_NLAPSTATE, in/out
+  double* lap_times;       // batch x laps
+  double* metrics;         // optional batch x FSAEMPC_NMETRIC, in/out; given together with ...
+  double* lap_records;     // ... batch x laps x FSAEMPC_NMETRIC
+};
+hipError_t cl_lap_gate_launch(const ClLapGateParams& P, hipStream_t st);
 hipError_t cl_metrics_launch(const ClMetricsParams& P, hipStream_t st, const double* par = nullptr, int par_stride = 0);
 hipError_t cl_pre_launch(const ClPreParams& P, hipStream_t st);
 // par (optional): parameter blocks (include/fsaempc.h FSAEMPC_P_*), car b reads par + b * par_stride; null: f_cart_dyn.m's own constants

@@ -10,6 +10,8 @@
 //                    (stage formulas exactly as written there, including the doubled k2 term of k5)
 //   cl_metrics_kernel main.m:196-228 the lap report's figures, accumulated per car after every period (opt-in); corridor.hip's
 //                    cor_metrics_kernel repeats its text with another track violation: a change here belongs there too
+//   cl_lap_gate_kernel (no counterpart: main.m:102-104 ends the run at the line) multi-lap driving, opt-in, between cl_pre and the
+//                    step: sub-period crossing time, per-lap times, the lap's record handed over, s wrapped by L
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "plant.h"
@@ -202,8 +204,63 @@ template <class PAR> __global__ void cl_metrics_kernel(ClMetricsParams P, typena
   }
 }
 
+// The lap gate (include/fsaempc.h FSAEMPC_LS_*): carries a car over the finish line.  Runs between the pre-step and the
+// MPC step; `finished` is what the pre-step left.  One thread per car, like its neighbours: the every-period part is a handful of loads,
+// compares and flops on the car's own four state slots; the strided column shift (2N + 1 doubles, and the record's 16) runs only for a car
+// that crosses in this period -- about once in several hundred periods -- so spreading it over a wavefront would buy nothing
+// (profiles/trackdrive/ has the kernel's time beside cl_pre and the plant).
+__global__ void cl_lap_gate_kernel(ClLapGateParams P) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= P.batch) return;
+  int fin = P.finished[b];
+  double* ls = P.lap_state + (size_t)b * FSAEMPC_NLAPSTATE;
+  double done = ls[FSAEMPC_LS_DONE];
+  if (fin == 2 || (fin == 1 && done >= (double)P.laps)) return;   // lost, or the last lap is complete: the car's data stay as they are
+  if (!(done >= 0.0)) return;                                      // (a state the caller did not zero indexes nothing)
+  const int nx = P.nx;
+  double* x0 = P.x0 + (size_t)b * nx;
+  if (fin == 1) {                                                  // the pre-step saw s >= L on this call: a crossing
+    const double k = ls[FSAEMPC_LS_STEPS], s = x0[0], s_prev = ls[FSAEMPC_LS_S_PREV];
+    double f = 1.0;                                                // share of the period before the line, linear in s
+    if (k > 0.0 && s > s_prev) f = fmin(fmax((P.L - s_prev) / (s - s_prev), 0.0), 1.0);
+    const double t = k > 0.0 ? (k - 1.0 + f) * P.dt : 0.0;
+    P.lap_times[(size_t)b * P.laps + (int)done] = t - ls[FSAEMPC_LS_T_CROSS];
+    ls[FSAEMPC_LS_T_CROSS] = t;
+    done += 1.0;
+    ls[FSAEMPC_LS_DONE] = done;
+    if (done < (double)P.laps) {                                   // the car drives on
+      if (P.metrics && P.lap_records) {                            // the lap's record is closed and handed over, a fresh one starts
+        double* m = P.metrics + (size_t)b * FSAEMPC_NMETRIC;
+        double* r = P.lap_records + ((size_t)b * P.laps + (int)done - 1) * FSAEMPC_NMETRIC;
+        double v[FSAEMPC_NMETRIC];                                 // (all loads, then all stores: one memory round trip, not sixteen)
+        for (int i = 0; i < FSAEMPC_NMETRIC; ++i) v[i] = m[i];
+        v[FSAEMPC_M_STATUS] = 1.0;
+        for (int i = 0; i < FSAEMPC_NMETRIC; ++i) { r[i] = v[i]; m[i] = 0.0; }
+      }
+      x0[0] = s - P.L;                                             // the wrap: every arc length the next step reads
+      double* xr = P.x_ref + (size_t)b * nx * P.N;
+      double* xk = P.x_keep + (size_t)b * nx * P.N;
+      for (int j0 = 0; j0 < P.N; j0 += 8) {                        // eight stages of both plans per round trip: the stores may alias the
+        double a[8], c[8];                                         // loads for all the compiler knows, so a plain loop waits on every one
+#pragma unroll
+        for (int i = 0; i < 8; ++i) if (j0 + i < P.N) { a[i] = xr[(j0 + i) * nx]; c[i] = xk[(j0 + i) * nx]; }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) if (j0 + i < P.N) { xr[(j0 + i) * nx] = a[i] - P.L; xk[(j0 + i) * nx] = c[i] - P.L; }
+      }
+      P.finished[b] = 0;
+      fin = 0;
+    }                                                              // (final crossing: finished stays 1, cl_metrics latches the record)
+  }
+  if (fin == 0) { ls[FSAEMPC_LS_S_PREV] = x0[0]; ls[FSAEMPC_LS_STEPS] += 1.0; }
+}
+
 }  // namespace
 
+hipError_t cl_lap_gate_launch(const ClLapGateParams& P, hipStream_t st) {
+  if (P.batch == 0) return hipSuccess;
+  hipLaunchKernelGGL(cl_lap_gate_kernel, dim3((P.batch + 63) / 64), dim3(64), 0, st, P);
+  return hipGetLastError();
+}
 hipError_t cl_metrics_launch(const ClMetricsParams& P, hipStream_t st, const double* par, int par_stride) {
   if (P.batch == 0) return hipSuccess;
   if (par) hipLaunchKernelGGL(cl_metrics_kernel<RtPar>, dim3((P.batch + 63) / 64), dim3(64), 0, st, P, ParArgs{par, par_stride, nullptr});

@@ -784,6 +784,46 @@ int fsaempc_plan_raceline_batch_device_c(int model, const fsaempc_spline* sp, do
 int fsaempc_corridor_line_bounds_device(const fsaempc_corridor* cor, double L, int n_plans, int N_s, int N_c, double margin,
                                         double* lb, double* ub, void* stream);
 
+/* ---- multi-lap closed loop: the lap gate ---------------------------------------------
+ * The loop above ends a car's run the first time the pre-step sees s >= L (main.m:102-104).  The gate carries a car over the line
+ * instead, up to `laps` laps: it times the crossing inside the period, hands the lap's record over and takes L off every arc
+ * length the next step reads.  Everything downstream is periodic in s already.  Opt-in: a loop that never calls the gate is the
+ * single-lap loop, and with laps = 1 the gate changes no datum of it. */
+#define FSAEMPC_MAX_LAPS 64
+#define FSAEMPC_NLAPSTATE 4
+#define FSAEMPC_LS_DONE    0   /* laps completed */
+#define FSAEMPC_LS_STEPS   1   /* periods on which the gate saw the car driving (finished[b] == 0 on exit) */
+#define FSAEMPC_LS_S_PREV  2   /* the car's s at the previous such period, after any wrap */
+#define FSAEMPC_LS_T_CROSS 3   /* time of the last crossing, 0 at the start */
+
+/*
+ * One call per MPC period, after the pre-step (either flavour) and before the step, on the same stream.  lap_state: batch x
+ * FSAEMPC_NLAPSTATE, instance-major, zeroed by the caller before the first period.  Per car, with k = STEPS and s = x0[b][0]:
+ *   finished[b] == 2, or finished[b] == 1 with DONE >= laps: nothing is touched;
+ *   finished[b] == 1 is a crossing: f = (L - S_PREV) / (s - S_PREV) clamped to [0, 1] if k > 0 and s > S_PREV, else f = 1;
+ *     t = (k - 1 + f) dt for k > 0, else 0; lap_times[b][DONE] = t - T_CROSS; T_CROSS = t; DONE += 1.
+ *     DONE < laps afterwards, the car drives on: with metrics and lap_records given, metrics[b] goes to lap_records[b][DONE - 1]
+ *     with STATUS = 1 and is zeroed; L is taken off x0[b][0] and off column 0 of every stage of x_ref[b] and of the kept plan
+ *     x_keep[b] (the next linearisation point and closest-point guess); finished[b] = 0.
+ *     DONE == laps, the final crossing: finished[b] stays 1 and the record stays where it is (the metrics entry latches it as it
+ *     latches a single lap).
+ *   finally, finished[b] == 0 on exit: S_PREV = x0[b][0], STEPS += 1.
+ * lap_times: batch x laps, filled with NaN by the caller (a lap not completed stays NaN).  metrics (batch x FSAEMPC_NMETRIC) and
+ * lap_records (batch x laps x FSAEMPC_NMETRIC, zeroed by the caller) are both given or both NULL.
+ * FSAEMPC_ERR_ARG before any launch: laps outside 1 .. FSAEMPC_MAX_LAPS, nx not 5 or 7, N < 1, batch < 0, dt or L not finite
+ * or <= 0, a NULL pointer among x0, x_ref, x_keep, finished, lap_state, lap_times, exactly one of metrics / lap_records.
+ * batch == 0 succeeds without a launch.
+ */
+int fsaempc_cl_lap_gate_batch_device(int nx, int N, double dt, double L, int laps, int batch, double* x0, double* x_ref,
+                                     double* x_keep, int* finished, double* lap_state, double* lap_times, double* metrics,
+                                     double* lap_records, void* stream);
+
+/* Per-lap summary of `batch` cars on the HOST (no device needed), summed in index order.  lap_times_host: batch x laps as the gate
+ * left it.  out: laps x 4 -- per lap the number of cars that completed it (a time that is not NaN), then the mean, min and max of
+ * its time over those cars (NaN for a lap nobody completed).  FSAEMPC_ERR_ARG: NULL (lap_times_host may be NULL with batch == 0),
+ * batch < 0, laps outside 1 .. FSAEMPC_MAX_LAPS. */
+int fsaempc_cl_lap_summary(const double* lap_times_host, int batch, int laps, double* out);
+
 /* ---- track pipeline (host side) --------------------------------------------------- */
 
 /* Spline table of a track as main.m:11-17 produces it: M arc-length segments, xP / yP = M x 4 Bezier control points per axis

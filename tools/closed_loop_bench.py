@@ -10,8 +10,11 @@ driving, the exit-flag tally the way main.m:209,222 reports it ("abnormal exits 
 track; the controller's track rows, the report's track violation and, with --raceline, the line's bounds are taken against it.
 --lap: every car starts at s = 0 on the centre line, at rest, with the usual lateral and heading scatter (main.m:63), and the step cap
 defaults to 1000 (main.m:62): a finished car's STEPS * dt is then a lap time.
+--laps K: every car drives K consecutive laps (ClosedLoop(laps=K), DESIGN.md 6m: the lap gate carries it over the line and times the
+crossing to a fraction of dt); with --lap the step cap defaults to 1000 K; the per-lap summary (cars that completed the lap, mean, min and
+max of its time) joins the JSON line as "lap_summary".
 usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--track fss2019]
-                                  [--plan | --raceline [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap]
+                                  [--plan | --raceline [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap] [--laps K]
                                   [--corridor FILE.npz]"""
 import argparse, json, os, sys, time
 import numpy as np
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--track", default="fss2019", choices=["fsg2019", "fss2019", "fso2020"])
     ap.add_argument("--report", action="store_true", help="keep the lap report's records on the device and add its summary to the JSON line")
     ap.add_argument("--lap", action="store_true", help="all cars start at s = 0 at rest; step cap 1000")
+    ap.add_argument("--laps", type=int, default=1, help="consecutive laps per car (the lap gate); with --lap the step cap becomes 1000 per lap")
     ap.add_argument("--slack-tol", type=float, default=1e-6, help="with --report: a slack counts as in use above this value")
     ap.add_argument("--horizon", type=int, default=40)
     ap.add_argument("--seed", type=int, default=20190)
@@ -43,7 +47,7 @@ def main():
     ap.add_argument("--corridor", default=None, metavar="FILE.npz", help="track corridor: arrays n_lo, n_hi of (N_w,) over the lap (Corridor.from_table)")
     a = ap.parse_args()
     if a.steps is None:
-        a.steps = 1000 if a.lap else 200
+        a.steps = 1000 * a.laps if a.lap else 200
     model = fm.KINEMATIC if a.model == "kinematic" else fm.DYNAMIC
     tr = fm.Track.load(a.track)
     cor = None
@@ -61,7 +65,7 @@ def main():
     # every car while it drives
     cart0, s_init = fm.monte_carlo_carts(tr, a.batch, a.seed, lap=a.lap)
     cl = fm.ClosedLoop(model, a.horizon, 0.05, tr, cart0, options=opts, warm_start=a.warm, launch_hint=not a.no_launch_hint, reference=plan,
-                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor)
+                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]
     fl_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
@@ -81,6 +85,8 @@ def main():
     fl, it, ac = fl_d.cpu().numpy(), it_d.cpu().numpy(), ac_d.cpu().numpy()
     dt_wall = time.perf_counter() - t0
     dist = (s_last - s_first).cpu().numpy()
+    if a.laps > 1:   # (s is wrapped by L at every crossing the car drove on from; the final crossing leaves it beyond L)
+        dist = dist + tr.L * np.minimum(cl.lap_state[:, fm.LAP_STATE_INDEX["DONE"]].cpu().numpy(), a.laps - 1)
     n_act = int(ac.sum())
     hist = {int(k_): int(c_) for k_, c_ in zip(*np.unique(fl[ac], return_counts=True))}
     solved = int(((fl == 0) & ac).sum())
@@ -89,6 +95,11 @@ def main():
                                                            # MEX gateway rejects such a call ("Argument contains NaN")
     x0 = cl.x0.cpu().numpy()
     fin = cl.finished.cpu().numpy()
+    lap_summary = None
+    if a.laps > 1:
+        lt = cl.lap_times.cpu().numpy()
+        lap_summary = np.zeros((a.laps, 4))
+        fm._lib.check(fm.lib().fsaempc_cl_lap_summary(lt.ctypes.data, a.batch, a.laps, lap_summary.ctypes.data), "fsaempc_cl_lap_summary")
     lost_qps = int((~ac[:, fin == 2]).sum())   # steps the lost cars sat out
     print(json.dumps({
         "metric": "QP solves/sec (closed loop, %s N=%d, fp64)" % (a.model, a.horizon), "value": solved / dt_wall, "unit": "QP solves/s",
@@ -99,6 +110,9 @@ def main():
                    "track": a.track, "corridor": a.corridor, "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
                    # (a mean over an empty set is NaN in the report: null in the JSON line)
                    **({"lap_report": {k: (None if v != v else v) for k, v in cl.report().summary().items()}, "slack_tol": a.slack_tol} if a.report else {}),
+                   **({"laps": a.laps, "lap_summary": [{"lap": i + 1, "cars": int(r[0]), "mean_s": None if r[1] != r[1] else float(r[1]),
+                                                         "min_s": None if r[2] != r[2] else float(r[2]), "max_s": None if r[3] != r[3] else float(r[3])}
+                                                        for i, r in enumerate(lap_summary)]} if lap_summary is not None else {}),
                    "qps_of_driving_cars": n_act, "qps_total_launched": int(a.batch * a.steps),
                    "exitflag_histogram_driving_cars": hist, "minus1_with_nonfinite_qp_data": bad_data,
                    "minus1_on_finite_qp_data_pct": 100.0 * (hist.get(-1, 0) - bad_data) / max(1, n_act), "abnormal_exit_pct": 100.0 * (1.0 - solved / max(1, n_act)),
