@@ -172,13 +172,10 @@ class ClosedLoop:
 
     def plant(self, exitflag, stream=None):
         P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        if self.plant_params is not None:
-            rc = lib().fsaempc_cl_plant_batch_device_p(self.model, self.N, C.c_double(self.dt), self.B, self.plant_params.ref(), P(self.cart), P(self.pid),
-                                                       P(self.x_opt), P(self.finished), P(exitflag), P(self.u_last), self._stream(stream))
-        else:
-            rc = lib().fsaempc_cl_plant_batch_device(self.model, self.N, C.c_double(self.dt), self.B, P(self.cart), P(self.pid), P(self.x_opt),
-                                                     P(self.finished), P(exitflag), P(self.u_last), self._stream(stream))
-        check(rc, "fsaempc_cl_plant_batch_device")
+        rc = lib().fsaempc_cl_plant_batch_device_p(self.model, self.N, C.c_double(self.dt), self.B,
+                                                   self.plant_params.ref() if self.plant_params is not None else None, P(self.cart), P(self.pid),
+                                                   P(self.x_opt), P(self.finished), P(exitflag), P(self.u_last), self._stream(stream))
+        check(rc, "fsaempc_cl_plant_batch_device_p")
 
     def step(self, stream=None):
         torch = self.torch
@@ -207,17 +204,13 @@ class ClosedLoop:
         check(lib().fsaempc_cl_accept_batch_device(self.model, self.N, self.B, P(out["x_opt"]), P(out["u_opt"]), P(out["exitflag"]), P(self.x_opt), P(self.u_opt),
                                                    self._stream(stream)), "fsaempc_cl_accept_batch_device")
         self.plant(None, stream)
-        if self.metrics is not None and self.corridor is not None:
+        if self.metrics is not None:
             check(lib().fsaempc_cl_metrics_batch_device_c(self.model, self.N, C.c_double(self.dt), C.c_double(self.slack_tol), self.B,
-                                                          self.mpc.params.ref() if self.mpc.params is not None else None, self.corridor.ref(),
+                                                          self.mpc.params.ref() if self.mpc.params is not None else None,
+                                                          self.corridor.ref() if self.corridor is not None else None,
                                                           P(self.x0), P(self.finished), P(out["exitflag"]), P(out["iter"]), P(out["fval"]),
                                                           P(out["slack"]), P(self.u_opt), P(self.cart), P(self.metrics), self._stream(stream)),
                   "fsaempc_cl_metrics_batch_device_c")
-        elif self.metrics is not None:
-            check(lib().fsaempc_cl_metrics_batch_device(self.model, self.N, C.c_double(self.dt), C.c_double(self.slack_tol), self.B,
-                                                        self.mpc.params.ref() if self.mpc.params is not None else None, P(self.x0), P(self.finished),
-                                                        P(out["exitflag"]), P(out["iter"]), P(out["fval"]), P(out["slack"]), P(self.u_opt), P(self.cart),
-                                                        P(self.metrics), self._stream(stream)), "fsaempc_cl_metrics_batch_device")
         self.steps += 1
         return out
 

@@ -1,6 +1,10 @@
 // capi.hip -- the C ABI of libfsaempc.so (include/fsaempc.h).  Host-side glue only: argument checks,
 // workspace carving, kernel launches.  There is no CPU compute path: without a gfx950 device every entry
 // point fails with FSAEMPC_ERR_NODEVICE / FSAEMPC_ERR_HIP.
+// The LTV build and step entries share one host path each (ltv_build_impl, ltv_step_impl) that takes the parameter block, the
+// blocking and the corridor as optional descriptors; the entries without a suffix and _aux, _lambda, _p, _b are forwards with NULL
+// for what they do not take, plus the one check that is theirs.  The host-buffer QP paths (fsaempc_qp_solve_batch, the
+// qpOASES_sequence handles) share the data scans, the checked copies and the layout of the per-call vectors.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -61,6 +65,8 @@ int hipfail(hipError_t e, const char* where) {
              ? FSAEMPC_ERR_NODEVICE : FSAEMPC_ERR_HIP;
 }
 size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
+// the spline half of a kernel parameter struct (the structs spell it with the same four names)
+template <class T> void set_spline(T* P, const fsaempc_spline* sp) { P->spM = sp->M; P->spdl = sp->dl; P->xP = sp->xP; P->yP = sp->yP; }
 }  // namespace
 
 extern "C" {
@@ -188,6 +194,57 @@ int fsaempc_qp_vjp_batch_device(const fsaempc_qp_desc* desc, int k, const double
   return 0;
 }
 
+// ---- host-buffer QP paths: fsaempc_qp_solve_batch and the qpOASES_sequence handles ----
+// The data checks of the original gateway ("Argument %d contains 'NaN' !"): NaN anywhere and Inf in H, g, A are refused.  A null
+// pointer is a vector this call does not bring (the handles upload H, A and the per-call vectors at different times).
+static int qp_scan(const double* H, size_t nH, const double* g, size_t ng, const double* A, size_t nA,
+                   const double* lb, const double* ub, size_t nb, const double* lbA, const double* ubA, size_t nbA) {
+  auto finite = [](const double* v, size_t cnt) { if (v) for (size_t i = 0; i < cnt; ++i) if (!isfinite(v[i])) return false; return true; };
+  auto no_nan = [](const double* v, size_t cnt) { if (v) for (size_t i = 0; i < cnt; ++i) if (isnan(v[i])) return false; return true; };
+  if (!finite(H, nH)) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): Argument 1 contains 'NaN' or 'Inf' !");
+  if (!finite(g, ng)) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): Argument 2 contains 'NaN' or 'Inf' !");
+  if (!finite(A, nA)) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): Argument 3 contains 'NaN' or 'Inf' !");
+  if (!no_nan(lb, nb) || !no_nan(ub, nb)) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): bounds contain 'NaN' !");
+  if (!no_nan(lbA, nbA) || !no_nan(ubA, nbA)) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): constraint bounds contain 'NaN' !");
+  return 0;
+}
+// checked copies; both do nothing once *rc is set, to_host also for an output the caller did not ask for
+static void to_device(int* rc, void* dst, const void* src, size_t bytes) {
+  if (*rc || bytes == 0) return;
+  hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) *rc = hipfail(e, "hipMemcpy H2D");
+}
+static void to_host(int* rc, void* dst, const void* src, size_t bytes) {
+  if (*rc || !dst) return;
+  hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) *rc = hipfail(e, "hipMemcpy D2H");
+}
+// the per-call vectors of a host-buffer solve, carved from one device allocation: g lb ub lbA ubA | x fval lambda | exitflag iter
+struct QpVecs {
+  double *g, *lb, *ub, *lbA, *ubA, *x, *fval, *lam; int *flag, *iter;
+  static size_t doubles(size_t n, size_t m, size_t B) { return B * (4 * n + 2 * m + 1 + (n + m)) + B + 16; }
+  QpVecs(double* p, size_t n, size_t m, size_t B) {
+    g = p; p += B * n; lb = p; p += B * n; ub = p; p += B * n; lbA = p; p += B * m; ubA = p; p += B * m;
+    x = p; p += B * n; fval = p; p += B; lam = p; p += B * (n + m);
+    flag = (int*)p; iter = flag + B;
+  }
+};
+// vectors to the device, one solve on the null stream with H and A already there, the results the caller asked for back
+static int qp_host_solve(const fsaempc_qp_desc* d, const double* dH, const double* dA, const QpVecs& v, const double* g, const double* lb,
+                         const double* ub, const double* lbA, const double* ubA, const fsaempc_qp_opts* opts, double* x, double* fval,
+                         int* exitflag, int* iter, double* lambda, void* dws, long long wsb) {
+  const size_t n = d->nV, m = d->nC, B = d->batch, D = sizeof(double);
+  int rc = 0;
+  to_device(&rc, v.g, g, B * n * D); to_device(&rc, v.lb, lb, B * n * D); to_device(&rc, v.ub, ub, B * n * D);
+  to_device(&rc, v.lbA, lbA, B * m * D); to_device(&rc, v.ubA, ubA, B * m * D);
+  if (rc == 0) rc = fsaempc_qp_solve_batch_device(d, dH, v.g, m ? dA : nullptr, v.lb, v.ub, m ? v.lbA : nullptr, m ? v.ubA : nullptr, opts,
+                                                  v.x, v.fval, v.flag, v.iter, v.lam, dws, wsb, nullptr);
+  if (rc == 0) { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) rc = hipfail(e, "solve"); }
+  to_host(&rc, x, v.x, B * n * D); to_host(&rc, fval, v.fval, B * D); to_host(&rc, exitflag, v.flag, B * sizeof(int));
+  to_host(&rc, iter, v.iter, B * sizeof(int)); to_host(&rc, lambda, v.lam, B * (n + m) * D);
+  return rc;
+}
+
 int fsaempc_qp_solve_batch(const fsaempc_qp_desc* desc, const double* H, const double* g, const double* A,
                            const double* lb, const double* ub, const double* lbA, const double* ubA,
                            const fsaempc_qp_opts* opts, double* x, double* fval, int* exitflag, int* iter, double* lambda) {
@@ -197,36 +254,18 @@ int fsaempc_qp_solve_batch(const fsaempc_qp_desc* desc, const double* H, const d
   if (desc->nV > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
   const size_t n = desc->nV, m = desc->nC, B = desc->batch, BH = desc->shared_HA ? 1 : B;
   if (B == 0) return 0;
-  // the original gateway rejects NaN anywhere and Inf in H,g,A ("Argument %d contains 'NaN' !")
-  for (size_t i = 0; i < BH * n * n; ++i) if (!isfinite(H[i])) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): Argument 1 contains 'NaN' or 'Inf' !");
-  for (size_t i = 0; i < B * n; ++i) if (!isfinite(g[i])) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): Argument 2 contains 'NaN' or 'Inf' !");
-  for (size_t i = 0; i < BH * m * n; ++i) if (!isfinite(A[i])) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): Argument 3 contains 'NaN' or 'Inf' !");
-  for (size_t i = 0; i < B * n; ++i) if (isnan(lb[i]) || isnan(ub[i])) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): bounds contain 'NaN' !");
-  for (size_t i = 0; i < B * m; ++i) if (isnan(lbA[i]) || isnan(ubA[i])) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): constraint bounds contain 'NaN' !");
+  if (int rc = qp_scan(H, BH * n * n, g, B * n, A, BH * m * n, lb, ub, B * n, lbA, ubA, B * m)) return rc;
   long long wsb = fsaempc_qp_workspace_bytes(desc);
   if (wsb < 0) return fail((int)wsb, "workspace size");
-  const size_t szH = BH * n * n, szg = B * n, szA = BH * m * n, szm = B * m, szl = B * (n + m);
-  const size_t nd = szH + szg + szA + 2 * szg + 2 * szm + szg /*x*/ + B /*fval*/ + szl /*lambda*/;
-  char* dev = nullptr;
-  hipError_t e = hipMalloc((void**)&dev, nd * sizeof(double) + 2 * B * sizeof(int) + (size_t)wsb + 4096);
+  const size_t szH = BH * n * n, szA = BH * m * n, szv = QpVecs::doubles(n, m, B);   // H | A | the vectors | the solver's workspace
+  double* dev = nullptr;
+  hipError_t e = hipMalloc((void**)&dev, (szH + szA + szv) * sizeof(double) + (size_t)wsb + 4096);
   if (e != hipSuccess) return hipfail(e, "hipMalloc");
-  double* p = (double*)dev;
-  double* dH = p; p += szH; double* dg = p; p += szg; double* dA = p; p += szA;
-  double* dlb = p; p += szg; double* dub = p; p += szg; double* dlbA = p; p += szm; double* dubA = p; p += szm;
-  double* dx = p; p += szg; double* dfv = p; p += B; double* dlam = p; p += szl;
-  int* dfl = (int*)p; int* dit = dfl + B;
-  void* dws = (void*)(((uintptr_t)(dit + B) + 255) & ~(uintptr_t)255);
+  double *dH = dev, *dA = dev + szH;
+  void* dws = (void*)(((uintptr_t)(dA + szA + szv) + 255) & ~(uintptr_t)255);
   int rc = 0;
-#define CP(dst, src, cnt) do { if (rc == 0 && (cnt) > 0) { e = hipMemcpy(dst, src, (cnt) * sizeof(double), hipMemcpyHostToDevice); if (e != hipSuccess) rc = hipfail(e, "hipMemcpy H2D"); } } while (0)
-  CP(dH, H, szH); CP(dg, g, szg); CP(dA, A, szA); CP(dlb, lb, szg); CP(dub, ub, szg); CP(dlbA, lbA, szm); CP(dubA, ubA, szm);
-#undef CP
-  if (rc == 0) rc = fsaempc_qp_solve_batch_device(desc, dH, dg, m ? dA : nullptr, dlb, dub, m ? dlbA : nullptr, m ? dubA : nullptr, opts,
-                                                  dx, dfv, dfl, dit, dlam, dws, wsb, nullptr);
-  if (rc == 0) { e = hipDeviceSynchronize(); if (e != hipSuccess) rc = hipfail(e, "solve"); }
-#define BK(dst, src, bytes) do { if (rc == 0 && (dst)) { e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hipfail(e, "hipMemcpy D2H"); } } while (0)
-  BK(x, dx, szg * sizeof(double)); BK(fval, dfv, B * sizeof(double)); BK(exitflag, dfl, B * sizeof(int)); BK(iter, dit, B * sizeof(int));
-  BK(lambda, dlam, szl * sizeof(double));
-#undef BK
+  to_device(&rc, dH, H, szH * sizeof(double)); to_device(&rc, dA, A, szA * sizeof(double));
+  if (rc == 0) rc = qp_host_solve(desc, dH, dA, QpVecs(dA + szA, n, m, B), g, lb, ub, lbA, ubA, opts, x, fval, exitflag, iter, lambda, dws, wsb);
   (void)hipFree(dev);
   return rc;
 }
@@ -253,13 +292,13 @@ std::vector<SeqQP> g_seq;   // handle = index + 1 (the MEX gateway also hands ou
 SeqQP* seq_get(int handle) { return (handle >= 1 && handle <= (int)g_seq.size() && g_seq[handle - 1].used) ? &g_seq[handle - 1] : nullptr; }
 int seq_upload_matrices(SeqQP* q, const double* H, const double* A) {
   const size_t n = q->nV, m = q->nC;
-  for (size_t i = 0; i < n * n; ++i) if (!isfinite(H[i])) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): Argument 1 contains 'NaN' or 'Inf' !");
-  for (size_t i = 0; i < m * n; ++i) if (!isfinite(A[i])) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): Argument 3 contains 'NaN' or 'Inf' !");
+  if (int rc = qp_scan(H, n * n, nullptr, 0, A, m * n, nullptr, nullptr, 0, nullptr, nullptr, 0)) return rc;
   hipError_t e;
   if (!q->dH) { e = hipMalloc((void**)&q->dH, n * n * sizeof(double)); if (e != hipSuccess) return hipfail(e, "hipMalloc"); }
   if (m && !q->dA) { e = hipMalloc((void**)&q->dA, m * n * sizeof(double)); if (e != hipSuccess) return hipfail(e, "hipMalloc"); }
-  e = hipMemcpy(q->dH, H, n * n * sizeof(double), hipMemcpyHostToDevice); if (e != hipSuccess) return hipfail(e, "hipMemcpy H2D");
-  if (m) { e = hipMemcpy(q->dA, A, m * n * sizeof(double), hipMemcpyHostToDevice); if (e != hipSuccess) return hipfail(e, "hipMemcpy H2D"); }
+  int rc = 0;
+  to_device(&rc, q->dH, H, n * n * sizeof(double)); to_device(&rc, q->dA, A, m * n * sizeof(double));
+  if (rc) return rc;
   q->hA.assign(A ? A : nullptr, A ? A + m * n : nullptr);
   return 0;
 }
@@ -267,40 +306,22 @@ int seq_solve(SeqQP* q, const double* g, const double* lb, const double* ub, con
               const fsaempc_qp_opts* opts, double* x, double* fval, int* exitflag, int* iter, double* lambda, bool remember) {
   const size_t n = q->nV, m = q->nC, B = k;
   if (!g || !lb || !ub || !x || (m && (!lbA || !ubA))) return fail(FSAEMPC_ERR_ARG, "null argument");
-  for (size_t i = 0; i < B * n; ++i) if (!isfinite(g[i])) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): Argument 2 contains 'NaN' or 'Inf' !");
-  for (size_t i = 0; i < B * n; ++i) if (isnan(lb[i]) || isnan(ub[i])) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): bounds contain 'NaN' !");
-  for (size_t i = 0; i < B * m; ++i) if (isnan(lbA[i]) || isnan(ubA[i])) return fail(FSAEMPC_ERR_ARG, "ERROR (qpOASES): constraint bounds contain 'NaN' !");
+  if (int rc = qp_scan(nullptr, 0, g, B * n, nullptr, 0, lb, ub, B * n, lbA, ubA, B * m)) return rc;
   fsaempc_qp_desc d{q->nV, q->nC, k, 1};
   hipError_t e;
-  if (k > q->kcap) {   // grow the per-call buffers: g lb ub lbA ubA x fval lambda (doubles), exitflag iter (ints), workspace
+  if (k > q->kcap) {   // grow the per-call buffers (QpVecs) and the workspace
     (void)hipFree(q->dvec); (void)hipFree(q->dws); q->dvec = nullptr; q->dws = nullptr; q->kcap = 0;
     const long long wsb = fsaempc_qp_workspace_bytes(&d);
     if (wsb < 0) return fail((int)wsb, "workspace size");
-    const size_t nd = B * (4 * n + 2 * m + 1 + (n + m)) + B + 16;
-    e = hipMalloc((void**)&q->dvec, nd * sizeof(double)); if (e != hipSuccess) return hipfail(e, "hipMalloc");
+    e = hipMalloc((void**)&q->dvec, QpVecs::doubles(n, m, B) * sizeof(double)); if (e != hipSuccess) return hipfail(e, "hipMalloc");
     e = hipMalloc(&q->dws, (size_t)wsb); if (e != hipSuccess) return hipfail(e, "hipMalloc");
     q->kcap = k; q->wsb = wsb;
   }
-  double* p = q->dvec;
-  double* dg = p; p += B * n; double* dlb = p; p += B * n; double* dub = p; p += B * n; double* dlbA = p; p += B * m; double* dubA = p; p += B * m;
-  double* dx = p; p += B * n; double* dfv = p; p += B; double* dlam = p; p += B * (n + m);
-  int* dfl = (int*)p; int* dit = dfl + B;
-  int rc = 0;
-#define CP(dst, src, cnt) do { if (rc == 0 && (cnt) > 0) { e = hipMemcpy(dst, src, (cnt) * sizeof(double), hipMemcpyHostToDevice); if (e != hipSuccess) rc = hipfail(e, "hipMemcpy H2D"); } } while (0)
-  CP(dg, g, B * n); CP(dlb, lb, B * n); CP(dub, ub, B * n); CP(dlbA, lbA, B * m); CP(dubA, ubA, B * m);
-#undef CP
-  if (rc == 0) rc = fsaempc_qp_solve_batch_device(&d, q->dH, dg, m ? q->dA : nullptr, dlb, dub, m ? dlbA : nullptr, m ? dubA : nullptr, opts,
-                                                  dx, dfv, dfl, dit, dlam, q->dws, q->wsb, nullptr);
-  if (rc == 0) { e = hipDeviceSynchronize(); if (e != hipSuccess) rc = hipfail(e, "solve"); }
+  const QpVecs dv(q->dvec, n, m, B);
+  int rc = qp_host_solve(&d, q->dH, q->dA, dv, g, lb, ub, lbA, ubA, opts, x, fval, exitflag, iter, lambda, q->dws, q->wsb);
   std::vector<double> lam0, x0h;
-  if (rc == 0 && remember && !lambda) lam0.resize(n + m);
-  if (rc == 0 && remember) x0h.resize(n);
-#define BK(dst, src, bytes) do { if (rc == 0 && (dst)) { e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = hipfail(e, "hipMemcpy D2H"); } } while (0)
-  BK(x, dx, B * n * sizeof(double)); BK(fval, dfv, B * sizeof(double)); BK(exitflag, dfl, B * sizeof(int)); BK(iter, dit, B * sizeof(int));
-  BK(lambda, dlam, B * (n + m) * sizeof(double));
-  if (!lam0.empty()) BK(lam0.data(), dlam, (n + m) * sizeof(double));
-  if (!x0h.empty()) BK(x0h.data(), dx, n * sizeof(double));
-#undef BK
+  if (rc == 0 && remember && !lambda) { lam0.resize(n + m); to_host(&rc, lam0.data(), dv.lam, (n + m) * sizeof(double)); }
+  if (rc == 0 && remember) { x0h.resize(n); to_host(&rc, x0h.data(), dv.x, n * sizeof(double)); }
   if (rc == 0 && remember) {
     // Working set of the first column (qpOASES.m:52-62 encoding), by the rule the kernels' active-set refinement uses: a side is
     // active iff its multiplier has the side's sign AND exceeds the side's slack.  On a refined vertex that is the same as
@@ -442,56 +463,6 @@ int fsaempc_ltv_default_params(int model, double* out) {
 static const double* par_values(const fsaempc_ltv_params* par) { return par ? par->values : nullptr; }
 static int par_stride(const fsaempc_ltv_params* par) { return par && par->per_instance ? FSAEMPC_NPAR : 0; }
 
-// par_idx (with par): the batch instance behind each instance of this (sub-)batch, for the per-instance blocks
-static int build_qp(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
-                    const double* u_lin, double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
-                    double* pred, double* Bt, double* qconst, void* stream, bool exact, const fsaempc_ltv_params* par = nullptr,
-                    const int* par_idx = nullptr) {
-  if (par_values(par) && ltv_build_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N, 256, exact, true) > 160 * 1024)
-    return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
-  if (desc->batch == 0) return 0;
-  LtvParams P; memset(&P, 0, sizeof(P));
-  P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.dt = desc->dt;
-  P.integ = ltv_integ(desc);
-  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP;
-  P.x0 = x0; P.x_ref = x_ref; P.x_lin = x_lin; P.u_lin = u_lin;
-  P.H = H; P.g = g; P.A = A; P.lb = lb; P.ub = ub; P.lbA = lbA; P.ubA = ubA; P.pred = pred; P.Bt = Bt; P.qconst = qconst;
-  hipError_t e = par_values(par) ? ltv_build_par_launch(P, par_values(par), par_stride(par), par_idx, desc->batch, (hipStream_t)stream, exact)
-                                 : ltv_build_launch(P, desc->batch, (hipStream_t)stream, exact);
-  if (e != hipSuccess) return hipfail(e, "ltv_build_launch");
-  return 0;
-}
-
-int fsaempc_ltv_build_qp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
-                                        const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
-                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
-                                        double* pred, double* Bt, double* qconst, void* stream) {
-  int rc = ltv_check(desc, sp); if (rc) return rc;
-  if (!x0 || !x_ref || !x_lin || !u_lin || !H || !g || !A || !lb || !ub || !lbA || !ubA || !Bt) return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
-  return build_qp(desc, sp, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream, false, par);
-}
-int fsaempc_ltv_build_qp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
-                                      const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
-                                      double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
-                                      double* pred, double* Bt, double* qconst, void* stream) {
-  return fsaempc_ltv_build_qp_batch_device_p(desc, sp, nullptr, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
-}
-
-int fsaempc_nlp_build_qp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
-                                        const double* x0, const double* x_ref, const double* u_lin,
-                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
-                                        double* pred, double* Bt, double* qconst, void* stream) {
-  int rc = ltv_check(desc, sp); if (rc) return rc;
-  if (ltv_build_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N, 256, true) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
-  if (!x0 || !x_ref || !u_lin || !H || !g || !A || !lb || !ub || !lbA || !ubA || !Bt) return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
-  return build_qp(desc, sp, x0, x_ref, nullptr, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream, true, par);
-}
-int fsaempc_nlp_build_qp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
-                                      const double* x0, const double* x_ref, const double* u_lin,
-                                      double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
-                                      double* pred, double* Bt, double* qconst, void* stream) {
-  return fsaempc_nlp_build_qp_batch_device_p(desc, sp, nullptr, x0, x_ref, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
-}
 
 /* ---- s-varying track corridors ---- */
 // the descriptor as the kernels take it; every refusal names the argument
@@ -514,96 +485,6 @@ static int cor_rows(const fsaempc_ltv_desc* desc, const CorTable& cor, const dou
   return 0;
 }
 
-struct LtvCarve { size_t H, g, A, lb, ub, lbA, ubA, pred, Bt, qc, z, qpws, total; };
-static void ltv_carve(const fsaempc_ltv_desc* d, LtvCarve* c) {
-  const size_t B = d->batch > 0 ? d->batch : 1, nx = fsaempc_ltv_nx(d->model), N = d->N;
-  const size_t nV = fsaempc_ltv_nV(d->model, d->N), nC = fsaempc_ltv_nC(d->model, d->N), R = nx * N;
-  size_t off = 0;
-  auto take = [&](size_t cnt) { size_t o = off; off = align64(off + cnt * sizeof(double)); return o; };
-  c->H = take(B * nV * nV); c->g = take(B * nV); c->A = take(B * nC * nV); c->lb = take(B * nV); c->ub = take(B * nV);
-  c->lbA = take(B * nC); c->ubA = take(B * nC); c->pred = take(B * R); c->Bt = take(B * R * nV); c->qc = take(B); c->z = take(B * nV);
-  off = (off + 255) & ~(size_t)255;
-  c->qpws = off;
-  fsaempc_qp_desc q{(int)nV, (int)nC, (int)B, 0};
-  long long w = fsaempc_qp_workspace_bytes(&q);
-  c->total = off + (w > 0 ? (size_t)w : 0);
-}
-
-long long fsaempc_ltv_workspace_bytes(const fsaempc_ltv_desc* desc) {
-  if (!desc || desc->N <= 0 || desc->batch < 0) return FSAEMPC_ERR_ARG;
-  if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return FSAEMPC_ERR_DIM;
-  LtvCarve c; ltv_carve(desc, &c);
-  return (long long)c.total;
-}
-
-int fsaempc_ltv_step_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
-                                  const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
-                                  const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                                  int* exitflag, int* iter, void* workspace, long long workspace_bytes, void* stream) {
-  return fsaempc_ltv_step_batch_device_aux(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, nullptr, workspace, workspace_bytes, stream);
-}
-
-static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
-                    const double* u_lin, const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream,
-                    const fsaempc_ltv_params* par = nullptr, const CorTable* cor = nullptr);
-
-int fsaempc_ltv_step_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
-                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
-                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
-                                    void* workspace, long long workspace_bytes, void* stream) {
-  return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream, par);
-}
-
-int fsaempc_ltv_step_batch_device_aux(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
-                                      const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
-                                      const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                                      int* exitflag, int* iter, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
-  return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, nullptr, aux, workspace, workspace_bytes, stream);
-}
-
-int fsaempc_ltv_step_batch_device_lambda(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
-                                         const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
-                                         const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                                         int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
-                                         void* workspace, long long workspace_bytes, void* stream) {
-  if (!lambda) return fail(FSAEMPC_ERR_ARG, "null argument (lambda)");
-  return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream);
-}
-
-static int ltv_step(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x0, const double* x_ref, const double* x_lin,
-                    const double* u_lin, const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream,
-                    const fsaempc_ltv_params* par, const CorTable* cor) {
-  int rc = ltv_check(desc, sp); if (rc) return rc;
-  if (!x0 || !x_ref || !x_lin || !u_lin || !u_opt || !x_opt || !slack || !fval || !exitflag || !iter || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
-  if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
-  if (desc->batch == 0) return 0;
-  LtvCarve c; ltv_carve(desc, &c);
-  if ((long long)c.total > workspace_bytes) return fail(FSAEMPC_ERR_WORKSPACE, "workspace too small");
-  char* w = (char*)workspace;
-  auto D = [&](size_t off) { return (double*)(w + off); };
-  Range whole("fsaempc.ltv.step");
-  const bool timing = g_timing.load();
-  if (timing) { hipError_t e = hipEventRecord(g_evf[0], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
-  { Range r("fsaempc.ltv.build");
-    rc = fsaempc_ltv_build_qp_batch_device_p(desc, sp, par, x0, x_ref, x_lin, u_lin, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA),
-                                             D(c.pred), D(c.Bt), D(c.qc), stream); }
-  if (rc) return rc;
-  if (cor) { rc = cor_rows(desc, *cor, x_lin, D(c.pred), D(c.lbA), D(c.ubA), stream); if (rc) return rc; }
-  fsaempc_qp_desc q{fsaempc_ltv_nV(desc->model, desc->N), fsaempc_ltv_nC(desc->model, desc->N), desc->batch, 0};
-  rc = fsaempc_qp_solve_batch_device_aux(&q, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA), opts, D(c.z), fval, exitflag, iter,
-                                         lambda, aux, w + c.qpws, (long long)(c.total - c.qpws), stream);
-  if (rc) return rc;
-  hipError_t e;
-  { Range r("fsaempc.ltv.post");
-    e = ltv_post_launch(fsaempc_ltv_nx(desc->model), desc->N, ltv_ns(desc->model), desc->batch, D(c.z), D(c.pred), D(c.Bt), D(c.qc),
-                        u_opt, x_opt, slack, fval, (hipStream_t)stream); }
-  if (e != hipSuccess) return hipfail(e, "ltv_post_launch");
-  if (timing) { e = hipEventRecord(g_evf[1], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
-  return 0;
-}
 
 /* ---- move blocking ---- */
 int fsaempc_ltv_blocked_nV(int model, const fsaempc_ltv_blocking* blk) {
@@ -631,33 +512,83 @@ static int blk_check(const fsaempc_ltv_desc* d, const fsaempc_ltv_blocking* blk,
   return 0;
 }
 
-int fsaempc_ltv_build_qp_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
-                                        const fsaempc_ltv_blocking* blk,
-                                        const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
-                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
-                                        double* pred, double* Bt, double* qconst, void* stream) {
-  LtvBlockMap bm; bool trivial = false;
-  int rc = blk_check(desc, blk, &bm, &trivial); if (rc) return rc;
-  if (trivial) return fsaempc_ltv_build_qp_batch_device_p(desc, sp, par, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
-  rc = ltv_check(desc, sp); if (rc) return rc;
-  if (!x0 || !x_ref || !x_lin || !u_lin || !H || !g || !A || !lb || !ub || !lbA || !ubA || !Bt) return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
-  if (ltv_build_blocked_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N, bm.M, 256) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
-  if (desc->batch == 0) return 0;
-  LtvParams P; memset(&P, 0, sizeof(P));
-  P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.dt = desc->dt;
-  P.integ = ltv_integ(desc);
-  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP;
-  P.x0 = x0; P.x_ref = x_ref; P.x_lin = x_lin; P.u_lin = u_lin;
-  P.H = H; P.g = g; P.A = A; P.lb = lb; P.ub = ub; P.lbA = lbA; P.ubA = ubA; P.pred = pred; P.Bt = Bt; P.qconst = qconst;
-  hipError_t e = ltv_build_blocked_launch(P, bm, par_values(par), par_stride(par), desc->batch, (hipStream_t)stream);
-  if (e != hipSuccess) return hipfail(e, "ltv_build_blocked_launch");
+/* ---- one build, one carve, one step: every fsaempc_ltv_build_qp_* / _step_* entry below is a forward ---- */
+// What the optional descriptors make of a call, worked out once.  Unblocked -- and a trivial blocking (n_blocks == N) is the unblocked
+// problem: same kernels, same carve -- the QP has 2N + ns variables and is sized and solved without a slack hint; blocked it has
+// 2M + ns and the hint ns, in the workspace size and in the solve alike.
+struct LtvShape {
+  bool blocked = false, corridor = false;
+  LtvBlockMap bm; CorTable cor;
+  int nV(const fsaempc_ltv_desc* d) const { return blocked ? 2 * bm.M + ltv_ns(d->model) : fsaempc_ltv_nV(d->model, d->N); }
+  int slack_hint(const fsaempc_ltv_desc* d) const { return blocked ? ltv_ns(d->model) : -1; }
+};
+// refusals in the order of the ABI: the corridor's, then the blocking's (its own text for 2N + ns > FSAEMPC_MAX_NV)
+static int ltv_shape(const fsaempc_ltv_desc* desc, const fsaempc_ltv_blocking* blk, const fsaempc_corridor* cor, bool have_pred, LtvShape* s) {
+  if (cor) {
+    if (int rc = cor_check(cor, &s->cor)) return rc;
+    if (!have_pred) return fail(FSAEMPC_ERR_ARG, "null argument (pred is required with a corridor)");
+    s->corridor = true;
+  }
+  if (blk) {
+    bool trivial = false;
+    if (int rc = blk_check(desc, blk, &s->bm, &trivial)) return rc;
+    s->blocked = !trivial;
+  }
   return 0;
 }
 
-// the carve of ltv_carve in blocked sizes; the QP workspace is sized with the same slack hint the solve is given
-static void ltv_carve_b(const fsaempc_ltv_desc* d, int M, LtvCarve* c) {
+// the descriptor pair as the kernels take it; the caller adds the tensors its launch writes
+static LtvParams ltv_params(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const double* x_lin, const double* u_lin) {
+  LtvParams P; memset(&P, 0, sizeof(P));
+  P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.dt = desc->dt; P.integ = ltv_integ(desc);
+  set_spline(&P, sp); P.x_lin = x_lin; P.u_lin = u_lin;
+  return P;
+}
+
+struct LtvQp { double *H, *g, *A, *lb, *ub, *lbA, *ubA, *pred, *Bt, *qconst; };   // the tensors of a built batch
+
+// The build of a checked shape: LTV about (x_lin, u_lin), or exact (the NLP's: no x_lin); with the constants compiled in, or read
+// from par -- par_idx then names the batch instance behind each instance of this (sub-)batch, for the per-instance blocks.
+static int ltv_build_shaped(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par, const LtvShape& s,
+                            const double* x0, const double* x_ref, const double* x_lin, const double* u_lin, const LtvQp& q, void* stream,
+                            bool exact, const int* par_idx) {
+  int rc = ltv_check(desc, sp); if (rc) return rc;
+  const int nx = fsaempc_ltv_nx(desc->model), N = desc->N;
+  const char* too_long = "horizon too long for the LDS staging";
+  if (exact && ltv_build_lds_bytes(nx, N, 256, true) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, too_long);
+  if (!x0 || !x_ref || (!exact && !x_lin) || !u_lin || !q.H || !q.g || !q.A || !q.lb || !q.ub || !q.lbA || !q.ubA || !q.Bt)
+    return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
+  if (s.blocked ? ltv_build_blocked_lds_bytes(nx, N, s.bm.M, 256) > 160 * 1024
+                : par_values(par) && ltv_build_lds_bytes(nx, N, 256, exact, true) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, too_long);
+  if (desc->batch == 0) return 0;
+  LtvParams P = ltv_params(desc, sp, x_lin, u_lin);
+  P.x0 = x0; P.x_ref = x_ref;
+  P.H = q.H; P.g = q.g; P.A = q.A; P.lb = q.lb; P.ub = q.ub; P.lbA = q.lbA; P.ubA = q.ubA; P.pred = q.pred; P.Bt = q.Bt; P.qconst = q.qconst;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = s.blocked        ? ltv_build_blocked_launch(P, s.bm, par_values(par), par_stride(par), desc->batch, st)
+               : par_values(par) ? ltv_build_par_launch(P, par_values(par), par_stride(par), par_idx, desc->batch, st, exact)
+                                 : ltv_build_launch(P, desc->batch, st, exact);
+  if (e != hipSuccess) return hipfail(e, s.blocked ? "ltv_build_blocked_launch" : "ltv_build_launch");
+  return 0;
+}
+
+// the build entries: optional parameter block, blocking and corridor (whose rows overwrite the track rows of the built batch)
+static int ltv_build_impl(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                          const fsaempc_ltv_blocking* blk, const fsaempc_corridor* cor,
+                          const double* x0, const double* x_ref, const double* x_lin, const double* u_lin, const LtvQp& q, void* stream,
+                          bool exact) {
+  LtvShape s;
+  int rc = ltv_shape(desc, blk, cor, q.pred != nullptr, &s); if (rc) return rc;
+  rc = ltv_build_shaped(desc, sp, par, s, x0, x_ref, x_lin, u_lin, q, stream, exact, nullptr);
+  if (rc || !s.corridor) return rc;
+  return cor_rows(desc, s.cor, x_lin, q.pred, q.lbA, q.ubA, stream);
+}
+
+// QP tensors | the solve's point z | the solver's workspace, sized with the slack hint the solve is given
+struct LtvCarve { size_t H, g, A, lb, ub, lbA, ubA, pred, Bt, qc, z, qpws, total; };
+static void ltv_carve(const fsaempc_ltv_desc* d, int nV_, int slack_hint_, LtvCarve* c) {
   const size_t B = d->batch > 0 ? d->batch : 1, nx = fsaempc_ltv_nx(d->model), N = d->N;
-  const size_t nV = 2 * (size_t)M + ltv_ns(d->model), nC = fsaempc_ltv_nC(d->model, d->N), R = nx * N;
+  const size_t nV = nV_, nC = fsaempc_ltv_nC(d->model, d->N), R = nx * N;
   size_t off = 0;
   auto take = [&](size_t cnt) { size_t o = off; off = align64(off + cnt * sizeof(double)); return o; };
   c->H = take(B * nV * nV); c->g = take(B * nV); c->A = take(B * nC * nV); c->lb = take(B * nV); c->ub = take(B * nV);
@@ -665,82 +596,104 @@ static void ltv_carve_b(const fsaempc_ltv_desc* d, int M, LtvCarve* c) {
   off = (off + 255) & ~(size_t)255;
   c->qpws = off;
   fsaempc_qp_desc q{(int)nV, (int)nC, (int)B, 0};
-  long long w = fsaempc_qp_workspace_bytes_s(&q, ltv_ns(d->model));
+  long long w = fsaempc_qp_workspace_bytes_s(&q, slack_hint_);
   c->total = off + (w > 0 ? (size_t)w : 0);
 }
 
-long long fsaempc_ltv_workspace_bytes_b(const fsaempc_ltv_desc* desc, const fsaempc_ltv_blocking* blk) {
-  if (!desc || desc->batch < 0) return FSAEMPC_ERR_ARG;
-  LtvBlockMap bm; bool trivial = false;
-  int rc = blk_check(desc, blk, &bm, &trivial); if (rc) return rc;
-  if (trivial) return fsaempc_ltv_workspace_bytes(desc);
-  LtvCarve c; ltv_carve_b(desc, bm.M, &c);
-  return (long long)c.total;
-}
-
-static int ltv_step_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
-                      const fsaempc_ltv_blocking* blk, const CorTable* cor,
-                      const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
-                      const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                      int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
-                      void* workspace, long long workspace_bytes, void* stream) {
-  LtvBlockMap bm; bool trivial = false;
-  int rc = blk_check(desc, blk, &bm, &trivial); if (rc) return rc;
-  if (trivial) return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream, par, cor);
+// The step: build (+ corridor rows), solve, post-solve in one workspace.  Refusals in the order of the ABI: corridor, blocking,
+// descriptors, nulls, FSAEMPC_MAX_NV, then the empty batch (nothing is written), then the workspace size.
+static int ltv_step_impl(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                         const fsaempc_ltv_blocking* blk, const fsaempc_corridor* cor,
+                         const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                         const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                         int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                         void* workspace, long long workspace_bytes, void* stream) {
+  LtvShape s;
+  int rc = ltv_shape(desc, blk, cor, true, &s); if (rc) return rc;
   rc = ltv_check(desc, sp); if (rc) return rc;
   if (!x0 || !x_ref || !x_lin || !u_lin || !u_opt || !x_opt || !slack || !fval || !exitflag || !iter || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
   if (desc->batch == 0) return 0;
-  LtvCarve c; ltv_carve_b(desc, bm.M, &c);
+  const int nx = fsaempc_ltv_nx(desc->model), ns = ltv_ns(desc->model), nV = s.nV(desc), hint = s.slack_hint(desc);
+  LtvCarve c; ltv_carve(desc, nV, hint, &c);
   if ((long long)c.total > workspace_bytes) return fail(FSAEMPC_ERR_WORKSPACE, "workspace too small");
   char* w = (char*)workspace;
   auto D = [&](size_t off) { return (double*)(w + off); };
-  Range whole("fsaempc.ltv.step_blocked");
+  const LtvQp q{D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA), D(c.pred), D(c.Bt), D(c.qc)};
+  Range whole(s.blocked ? "fsaempc.ltv.step_blocked" : "fsaempc.ltv.step");
   const bool timing = g_timing.load();
   if (timing) { hipError_t e = hipEventRecord(g_evf[0], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
-  { Range r("fsaempc.ltv.build_blocked");
-    rc = fsaempc_ltv_build_qp_batch_device_b(desc, sp, par, blk, x0, x_ref, x_lin, u_lin, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA),
-                                             D(c.pred), D(c.Bt), D(c.qc), stream); }
+  { Range r(s.blocked ? "fsaempc.ltv.build_blocked" : "fsaempc.ltv.build");
+    rc = ltv_build_shaped(desc, sp, par, s, x0, x_ref, x_lin, u_lin, q, stream, false, nullptr); }
   if (rc) return rc;
-  if (cor) { rc = cor_rows(desc, *cor, x_lin, D(c.pred), D(c.lbA), D(c.ubA), stream); if (rc) return rc; }
-  const int ns = ltv_ns(desc->model);
-  fsaempc_qp_desc q{2 * bm.M + ns, fsaempc_ltv_nC(desc->model, desc->N), desc->batch, 0};
-  rc = fsaempc_qp_solve_batch_device_s(&q, ns, D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA), opts, D(c.z), fval, exitflag, iter,
+  if (s.corridor) { rc = cor_rows(desc, s.cor, x_lin, q.pred, q.lbA, q.ubA, stream); if (rc) return rc; }
+  fsaempc_qp_desc qd{nV, fsaempc_ltv_nC(desc->model, desc->N), desc->batch, 0};
+  rc = fsaempc_qp_solve_batch_device_s(&qd, hint, q.H, q.g, q.A, q.lb, q.ub, q.lbA, q.ubA, opts, D(c.z), fval, exitflag, iter,
                                        lambda, aux, w + c.qpws, (long long)(c.total - c.qpws), stream);
   if (rc) return rc;
   hipError_t e;
   { Range r("fsaempc.ltv.post");
-    e = ltv_post_blocked_launch(fsaempc_ltv_nx(desc->model), desc->N, ns, bm, desc->batch, D(c.z), D(c.pred), D(c.Bt), D(c.qc),
-                                u_opt, x_opt, slack, fval, (hipStream_t)stream); }
-  if (e != hipSuccess) return hipfail(e, "ltv_post_blocked_launch");
+    e = s.blocked ? ltv_post_blocked_launch(nx, desc->N, ns, s.bm, desc->batch, D(c.z), q.pred, q.Bt, q.qconst, u_opt, x_opt, slack, fval, (hipStream_t)stream)
+                  : ltv_post_launch(nx, desc->N, ns, desc->batch, D(c.z), q.pred, q.Bt, q.qconst, u_opt, x_opt, slack, fval, (hipStream_t)stream); }
+  if (e != hipSuccess) return hipfail(e, s.blocked ? "ltv_post_blocked_launch" : "ltv_post_launch");
   if (timing) { e = hipEventRecord(g_evf[1], (hipStream_t)stream); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
   return 0;
 }
 
-int fsaempc_ltv_step_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
-                                    const fsaempc_ltv_blocking* blk,
-                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
-                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
-                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
-                                    void* workspace, long long workspace_bytes, void* stream) {
-  return ltv_step_b(desc, sp, par, blk, nullptr, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux,
-                    workspace, workspace_bytes, stream);
-}
-
-/* ---- the build and the step inside a corridor ---- */
+/* ---- the entries: the general one of each family is _c; the others forward to it with NULL for what they do not take ---- */
 int fsaempc_ltv_build_qp_batch_device_c(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
                                         const fsaempc_ltv_blocking* blk, const fsaempc_corridor* cor,
                                         const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
                                         double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
                                         double* pred, double* Bt, double* qconst, void* stream) {
-  CorTable ct;
-  if (cor) {
-    if (int rc = cor_check(cor, &ct)) return rc;
-    if (!pred) return fail(FSAEMPC_ERR_ARG, "null argument (pred is required with a corridor)");
-  }
-  int rc = blk ? fsaempc_ltv_build_qp_batch_device_b(desc, sp, par, blk, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream)
-               : fsaempc_ltv_build_qp_batch_device_p(desc, sp, par, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
-  if (rc || !cor) return rc;
-  return cor_rows(desc, ct, x_lin, pred, lbA, ubA, stream);
+  return ltv_build_impl(desc, sp, par, blk, cor, x0, x_ref, x_lin, u_lin, LtvQp{H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst}, stream, false);
+}
+int fsaempc_ltv_build_qp_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const fsaempc_ltv_blocking* blk,
+                                        const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream) {
+  if (!blk) return fail(FSAEMPC_ERR_ARG, "null argument");   // (this entry is for a blocking)
+  return fsaempc_ltv_build_qp_batch_device_c(desc, sp, par, blk, nullptr, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
+}
+int fsaempc_ltv_build_qp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream) {
+  return fsaempc_ltv_build_qp_batch_device_c(desc, sp, par, nullptr, nullptr, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
+}
+int fsaempc_ltv_build_qp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                                      const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                      double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                      double* pred, double* Bt, double* qconst, void* stream) {
+  return fsaempc_ltv_build_qp_batch_device_c(desc, sp, nullptr, nullptr, nullptr, x0, x_ref, x_lin, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
+}
+int fsaempc_nlp_build_qp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                        const double* x0, const double* x_ref, const double* u_lin,
+                                        double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                        double* pred, double* Bt, double* qconst, void* stream) {
+  return ltv_build_impl(desc, sp, par, nullptr, nullptr, x0, x_ref, nullptr, u_lin, LtvQp{H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst}, stream, true);
+}
+int fsaempc_nlp_build_qp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                                      const double* x0, const double* x_ref, const double* u_lin,
+                                      double* H, double* g, double* A, double* lb, double* ub, double* lbA, double* ubA,
+                                      double* pred, double* Bt, double* qconst, void* stream) {
+  return fsaempc_nlp_build_qp_batch_device_p(desc, sp, nullptr, x0, x_ref, u_lin, H, g, A, lb, ub, lbA, ubA, pred, Bt, qconst, stream);
+}
+
+long long fsaempc_ltv_workspace_bytes(const fsaempc_ltv_desc* desc) {
+  if (!desc || desc->N <= 0 || desc->batch < 0) return FSAEMPC_ERR_ARG;
+  if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return FSAEMPC_ERR_DIM;
+  LtvCarve c; ltv_carve(desc, fsaempc_ltv_nV(desc->model, desc->N), -1, &c);
+  return (long long)c.total;
+}
+long long fsaempc_ltv_workspace_bytes_b(const fsaempc_ltv_desc* desc, const fsaempc_ltv_blocking* blk) {
+  if (!desc || desc->batch < 0) return FSAEMPC_ERR_ARG;
+  if (!blk) return fail(FSAEMPC_ERR_ARG, "null argument");
+  LtvShape s;
+  if (int rc = ltv_shape(desc, blk, nullptr, true, &s)) return rc;
+  LtvCarve c; ltv_carve(desc, s.nV(desc), s.slack_hint(desc), &c);
+  return (long long)c.total;
 }
 
 int fsaempc_ltv_step_batch_device_c(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
@@ -749,12 +702,49 @@ int fsaempc_ltv_step_batch_device_c(const fsaempc_ltv_desc* desc, const fsaempc_
                                     const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
                                     int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
                                     void* workspace, long long workspace_bytes, void* stream) {
-  CorTable ct;
-  if (cor) { if (int rc = cor_check(cor, &ct)) return rc; }
-  const CorTable* c = cor ? &ct : nullptr;
-  if (blk) return ltv_step_b(desc, sp, par, blk, c, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux,
-                             workspace, workspace_bytes, stream);
-  return ltv_step(desc, sp, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux, workspace, workspace_bytes, stream, par, c);
+  return ltv_step_impl(desc, sp, par, blk, cor, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux,
+                       workspace, workspace_bytes, stream);
+}
+int fsaempc_ltv_step_batch_device_b(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const fsaempc_ltv_blocking* blk,
+                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                    void* workspace, long long workspace_bytes, void* stream) {
+  if (!blk) return fail(FSAEMPC_ERR_ARG, "null argument");   // (this entry is for a blocking)
+  return ltv_step_impl(desc, sp, par, blk, nullptr, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux,
+                       workspace, workspace_bytes, stream);
+}
+int fsaempc_ltv_step_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                    const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                    int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                    void* workspace, long long workspace_bytes, void* stream) {
+  return ltv_step_impl(desc, sp, par, nullptr, nullptr, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux,
+                       workspace, workspace_bytes, stream);
+}
+int fsaempc_ltv_step_batch_device_lambda(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                                         const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                         const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                         int* exitflag, int* iter, double* lambda, const fsaempc_qp_aux* aux,
+                                         void* workspace, long long workspace_bytes, void* stream) {
+  if (!lambda) return fail(FSAEMPC_ERR_ARG, "null argument (lambda)");
+  return ltv_step_impl(desc, sp, nullptr, nullptr, nullptr, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, lambda, aux,
+                       workspace, workspace_bytes, stream);
+}
+int fsaempc_ltv_step_batch_device_aux(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                                      const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                      const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                      int* exitflag, int* iter, const fsaempc_qp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
+  return ltv_step_impl(desc, sp, nullptr, nullptr, nullptr, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, nullptr, aux,
+                       workspace, workspace_bytes, stream);
+}
+int fsaempc_ltv_step_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                                  const double* x0, const double* x_ref, const double* x_lin, const double* u_lin,
+                                  const fsaempc_qp_opts* opts, double* u_opt, double* x_opt, double* slack, double* fval,
+                                  int* exitflag, int* iter, void* workspace, long long workspace_bytes, void* stream) {
+  return ltv_step_impl(desc, sp, nullptr, nullptr, nullptr, x0, x_ref, x_lin, u_lin, opts, u_opt, x_opt, slack, fval, exitflag, iter, nullptr, nullptr,
+                       workspace, workspace_bytes, stream);
 }
 
 /* ---- sensitivities of the LTV-MPC step ---- */
@@ -764,17 +754,14 @@ int fsaempc_ltv_affine_maps_batch_device(const fsaempc_ltv_desc* desc, const fsa
   if (!x_lin || !u_lin || !Abar || !Crow) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (ltv_affine_lds_bytes(fsaempc_ltv_nx(desc->model), desc->N) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, "horizon too long for the LDS staging");
   if (desc->batch == 0) return 0;
-  LtvParams P; memset(&P, 0, sizeof(P));
-  P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.dt = desc->dt; P.integ = ltv_integ(desc);
-  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP; P.x_lin = x_lin; P.u_lin = u_lin;
-  hipError_t e = ltv_affine_launch(P, desc->batch, Abar, Crow, (hipStream_t)stream);
+  hipError_t e = ltv_affine_launch(ltv_params(desc, sp, x_lin, u_lin), desc->batch, Abar, Crow, (hipStream_t)stream);
   if (e != hipSuccess) return hipfail(e, "ltv_affine_launch");
   return 0;
 }
 
 struct LtvVjpCarve { LtvCarve f; size_t zbar, fb, gbar, lbAbar, ubAbar, Abar, Crow, vjpws, total; };
 static void ltv_vjp_carve(const fsaempc_ltv_desc* d, int k, LtvVjpCarve* c) {
-  ltv_carve(d, &c->f);
+  ltv_carve(d, fsaempc_ltv_nV(d->model, d->N), -1, &c->f);
   const size_t B = d->batch > 0 ? d->batch : 1, nx = fsaempc_ltv_nx(d->model), N = d->N, K = k > 0 ? k : 1;
   const size_t nV = fsaempc_ltv_nV(d->model, d->N), nC = fsaempc_ltv_nC(d->model, d->N), R = nx * N;
   size_t off = c->f.qpws;   // the forward's QP tensors stay; the solver's workspace is not needed here
@@ -816,8 +803,8 @@ int fsaempc_ltv_step_vjp_batch_device(const fsaempc_ltv_desc* desc, const fsaemp
   hipStream_t st = (hipStream_t)stream;
   Range whole("fsaempc.ltv.step_vjp");
   // the QP of the step (the build is deterministic: the same QP the forward solved) and the affine maps
-  rc = build_qp(desc, sp, x0, x_ref, x_lin, u_lin, D(c.f.H), D(c.f.g), D(c.f.A), D(c.f.lb), D(c.f.ub), D(c.f.lbA), D(c.f.ubA),
-                D(c.f.pred), D(c.f.Bt), D(c.f.qc), stream, false);
+  rc = ltv_build_shaped(desc, sp, nullptr, LtvShape(), x0, x_ref, x_lin, u_lin,
+                        LtvQp{D(c.f.H), D(c.f.g), D(c.f.A), D(c.f.lb), D(c.f.ub), D(c.f.lbA), D(c.f.ubA), D(c.f.pred), D(c.f.Bt), D(c.f.qc)}, stream, false, nullptr);
   if (rc) return rc;
   rc = fsaempc_ltv_affine_maps_batch_device(desc, sp, x_lin, u_lin, D(c.Abar), D(c.Crow), stream);
   if (rc) return rc;
@@ -899,8 +886,7 @@ int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_splin
   hipStream_t st = (hipStream_t)stream;
   const int nx = fsaempc_ltv_nx(desc->model), N = desc->N, nV = fsaempc_ltv_nV(desc->model, N), nC = fsaempc_ltv_nC(desc->model, N);
   SqpParams P; memset(&P, 0, sizeof(P));
-  P.nx = nx; P.N = N; P.integ = ltv_integ(desc); P.B = desc->batch; P.dt = desc->dt;
-  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP;
+  P.nx = nx; P.N = N; P.integ = ltv_integ(desc); P.B = desc->batch; P.dt = desc->dt; set_spline(&P, sp);
   P.x0 = x0; P.x_ref = x_ref; P.u = u_opt; P.x = x_opt; P.s = slack; P.fval = fval; P.status = status; P.sweeps = sweeps;
   P.rho = D(c.rho); P.J = D(c.J); P.viol = D(c.viol); P.vmax = D(c.vmax);
   if (aux) { P.lambda_out = aux->lambda; P.qp_iter = aux->qp_iter; P.step_norm = aux->step_norm; P.hard_viol = aux->hard_viol; P.merit = aux->merit; }
@@ -925,8 +911,8 @@ int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_splin
     if (timing) { e = hipEventRecord(g_evs[1], st); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
     fsaempc_ltv_desc sub = *desc; sub.batch = cnt;
     { Range r("fsaempc.sqp.build");
-      rc = build_qp(&sub, sp, D(c.gx0), D(c.gxr), nullptr, D(c.gu), D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA),
-                    D(c.pred), D(c.Bt), D(c.qc), stream, true, par, Iw(c.idx)); }
+      rc = ltv_build_shaped(&sub, sp, par, LtvShape(), D(c.gx0), D(c.gxr), nullptr, D(c.gu),
+                            LtvQp{D(c.H), D(c.g), D(c.A), D(c.lb), D(c.ub), D(c.lbA), D(c.ubA), D(c.pred), D(c.Bt), D(c.qc)}, stream, true, Iw(c.idx)); }
     if (rc) return rc;
     if (timing) { e = hipEventRecord(g_evs[2], st); if (e != hipSuccess) return hipfail(e, "hipEventRecord"); }
     fsaempc_qp_desc q{nV, nC, cnt, 0};

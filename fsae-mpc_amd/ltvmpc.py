@@ -29,8 +29,9 @@ class LtvBatch:
         (move blocking).  The QP then has nV = 2 * n_blocks + ns variables [v_1 .. v_M; slacks]: build_qp, x_init and
         lam are in these sizes, while u_opt stays (B, 2N), the held values.
         corridor: None, or a Corridor (shared, or one table per instance): the track rows |n_k| <= N_MAX + slack become
-        n_lo(s_k) <= n_k + slack, n_k - slack <= n_hi(s_k) at the rows' linearisation points; build_qp and step go
-        through the _c entries, and the SQP's exact build, the affine maps and the VJPs refuse the batch."""
+        n_lo(s_k) <= n_k + slack, n_k - slack <= n_hi(s_k) at the rows' linearisation points; the SQP's exact build, the
+        affine maps and the VJPs refuse the batch.
+        build_qp and step call the general _c entries, with NULL for whichever of the three the batch has not."""
         self.blocking = Blocking(blocking, N) if blocking is not None else None   # (validated before the library is touched)
         self.corridor = check_corridor(corridor, batch, device)
         import torch
@@ -62,6 +63,10 @@ class LtvBatch:
     def _stream(self, stream):
         return C.c_void_p(stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _optional(self):
+        """The optional descriptors of the general (_c) entries: parameter block, blocking, corridor; None for one the batch has not."""
+        return tuple(d.ref() if d is not None else None for d in (self.params, self.blocking, self.corridor))
+
     def build_qp(self, x0, x_ref, x_lin, u_lin, stream=None):
         """QP tensors of ltvmpc_*.m:38-41 (H,g,A,lb,ub,lbA,ubA, pred = A_bar*x0+d_bar, Bt, const)."""
         B, nx, N, nV, nC = self.batch, self.nx, self.N, self.nV, self.nC
@@ -70,20 +75,9 @@ class LtvBatch:
                  const=self._f64(B))
         P = lambda t: C.c_void_p(t.data_ptr())
         out = (P(q["H"]), P(q["g"]), P(q["A"]), P(q["lb"]), P(q["ub"]), P(q["lbA"]), P(q["ubA"]), P(q["pred"]), P(q["Bt"]), P(q["const"]))
-        if self.corridor is not None:
-            rc = lib().fsaempc_ltv_build_qp_batch_device_c(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
-                                                           self.blocking.ref() if self.blocking is not None else None, self.corridor.ref(),
-                                                           P(x0), P(x_ref), P(x_lin), P(u_lin), *out, self._stream(stream))
-        elif self.blocking is not None:
-            rc = lib().fsaempc_ltv_build_qp_batch_device_b(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
-                                                           self.blocking.ref(), P(x0), P(x_ref), P(x_lin), P(u_lin), *out, self._stream(stream))
-        elif self.params is not None:
-            rc = lib().fsaempc_ltv_build_qp_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref(), P(x0), P(x_ref), P(x_lin),
-                                                           P(u_lin), *out, self._stream(stream))
-        else:
-            rc = lib().fsaempc_ltv_build_qp_batch_device(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(x_lin), P(u_lin), *out,
-                                                         self._stream(stream))
-        check(rc, "fsaempc_ltv_build_qp_batch_device")
+        rc = lib().fsaempc_ltv_build_qp_batch_device_c(C.byref(self.desc), C.byref(self.sp), *self._optional(), P(x0), P(x_ref), P(x_lin), P(u_lin),
+                                                       *out, self._stream(stream))
+        check(rc, "fsaempc_ltv_build_qp_batch_device_c")
         return q
 
     def step(self, x0, x_ref, x_lin, u_lin, stream=None, want_aux=False, x_init=None, difficulty=None, want_lambda=False):
@@ -100,7 +94,7 @@ class LtvBatch:
         else:
             need = lib().fsaempc_ltv_workspace_bytes(C.byref(self.desc))
         if need < 0:
-            check(int(need), "fsaempc_ltv_workspace_bytes")
+            check(int(need), "fsaempc_ltv_workspace_bytes_b" if self.blocking is not None else "fsaempc_ltv_workspace_bytes")
         if self._ws is None or self._ws.numel() * 8 < need:
             self._ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
         out = dict(u_opt=self._f64(B, 2 * self.N), x_opt=self._f64(B, self.nx * self.N), slack=self._f64(B, self.ns), fval=self._f64(B),
@@ -119,34 +113,11 @@ class LtvBatch:
             raise ValueError("difficulty must be a contiguous int32 (batch,) tensor on the GPU")
         df = P(difficulty) if difficulty is not None else None
         aux = QpAux(P(out["kkt"]), P(out["polished"]), xi, df) if want_aux else QpAux(None, None, xi, df)
-        if self.corridor is not None:
-            rc = lib().fsaempc_ltv_step_batch_device_c(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
-                                                       self.blocking.ref() if self.blocking is not None else None, self.corridor.ref(),
-                                                       P(x0), P(x_ref), P(x_lin), P(u_lin),
-                                                       C.byref(self.opts), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]),
-                                                       P(out["exitflag"]), P(out["iter"]), lam, C.byref(aux), P(self._ws),
-                                                       C.c_longlong(self._ws.numel() * 8), self._stream(stream))
-        elif self.blocking is not None:
-            rc = lib().fsaempc_ltv_step_batch_device_b(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
-                                                       self.blocking.ref(), P(x0), P(x_ref), P(x_lin), P(u_lin),
-                                                       C.byref(self.opts), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]),
-                                                       P(out["exitflag"]), P(out["iter"]), lam, C.byref(aux), P(self._ws),
-                                                       C.c_longlong(self._ws.numel() * 8), self._stream(stream))
-        elif self.params is not None:
-            rc = lib().fsaempc_ltv_step_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref(), P(x0), P(x_ref), P(x_lin), P(u_lin),
-                                                       C.byref(self.opts), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]),
-                                                       P(out["exitflag"]), P(out["iter"]), lam, C.byref(aux), P(self._ws),
-                                                       C.c_longlong(self._ws.numel() * 8), self._stream(stream))
-        elif want_lambda:
-            rc = lib().fsaempc_ltv_step_batch_device_lambda(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(x_lin), P(u_lin), C.byref(self.opts),
-                                                            P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]), P(out["exitflag"]),
-                                                            P(out["iter"]), lam, C.byref(aux), P(self._ws), C.c_longlong(self._ws.numel() * 8),
-                                                            self._stream(stream))
-        else:
-            rc = lib().fsaempc_ltv_step_batch_device_aux(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(x_lin), P(u_lin), C.byref(self.opts),
-                                                         P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]), P(out["exitflag"]), P(out["iter"]),
-                                                         C.byref(aux), P(self._ws), C.c_longlong(self._ws.numel() * 8), self._stream(stream))
-        check(rc, "fsaempc_ltv_step_batch_device_aux")
+        rc = lib().fsaempc_ltv_step_batch_device_c(C.byref(self.desc), C.byref(self.sp), *self._optional(), P(x0), P(x_ref), P(x_lin), P(u_lin),
+                                                   C.byref(self.opts), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]),
+                                                   P(out["exitflag"]), P(out["iter"]), lam, C.byref(aux), P(self._ws),
+                                                   C.c_longlong(self._ws.numel() * 8), self._stream(stream))
+        check(rc, "fsaempc_ltv_step_batch_device_c")
         return out
 
 

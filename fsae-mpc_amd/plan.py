@@ -188,16 +188,11 @@ class Plan:
         opts = options if options is not None else default_opts()
         st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
         p = lambda a: C.c_void_p(a.data_ptr())
-        if corridor is not None:
-            rc = lib().fsaempc_plan_raceline_batch_device_c(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
-                                                            corridor.ref(), n_plans, N_s, N_c, C.c_double(margin), C.c_double(v_cap),
-                                                            C.c_double(grip), C.byref(opts), p(line), p(flag), p(table), p(t), p(ws),
-                                                            C.c_longlong(ws.numel() * 8), st)
-        else:
-            rc = lib().fsaempc_plan_raceline_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
-                                                          n_plans, N_s, N_c, C.c_double(margin), C.c_double(v_cap), C.c_double(grip), C.byref(opts),
-                                                          p(line), p(flag), p(table), p(t), p(ws), C.c_longlong(ws.numel() * 8), st)
-        check(rc, "fsaempc_plan_raceline_batch_device")
+        rc = lib().fsaempc_plan_raceline_batch_device_c(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                        corridor.ref() if corridor is not None else None, n_plans, N_s, N_c, C.c_double(margin),
+                                                        C.c_double(v_cap), C.c_double(grip), C.byref(opts), p(line), p(flag), p(table), p(t), p(ws),
+                                                        C.c_longlong(ws.numel() * 8), st)
+        check(rc, "fsaempc_plan_raceline_batch_device_c")
         plan = Plan(table, t, track.L / N_s)
         plan._blocks, plan._ws, plan._corridor = blocks, ws, corridor   # (read by launches that may still be queued)
         plan.line, plan.line_flag = line, flag

@@ -56,13 +56,9 @@ class SqpBatch:
                  lbA=self._f64(B, nC), ubA=self._f64(B, nC), pred=self._f64(B, N * nx), Bt=self._f64(B, nV, N * nx), const=self._f64(B))
         P = lambda t: C.c_void_p(t.data_ptr())
         out = (P(q["H"]), P(q["g"]), P(q["A"]), P(q["lb"]), P(q["ub"]), P(q["lbA"]), P(q["ubA"]), P(q["pred"]), P(q["Bt"]), P(q["const"]))
-        if self.params is not None:
-            rc = lib().fsaempc_nlp_build_qp_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref(), P(x0), P(x_ref), P(u_lin),
-                                                           *out, self._stream(stream))
-        else:
-            rc = lib().fsaempc_nlp_build_qp_batch_device(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(u_lin), *out,
-                                                         self._stream(stream))
-        check(rc, "fsaempc_nlp_build_qp_batch_device")
+        rc = lib().fsaempc_nlp_build_qp_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
+                                                       P(x0), P(x_ref), P(u_lin), *out, self._stream(stream))
+        check(rc, "fsaempc_nlp_build_qp_batch_device_p")
         return q
 
     def _stream(self, stream):
@@ -93,11 +89,9 @@ class SqpBatch:
         aux = SqpAux(P(out["lambda"]), P(out["qp_iter"]), P(out["step_norm"]), P(out["hard_viol"]), P(out["merit"]))
         tail = (C.byref(self.opts), C.byref(o), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]), P(out["status"]),
                 P(out["sweeps"]), C.byref(aux), P(self._ws), C.c_longlong(self._ws.numel() * 8), self._stream(stream))
-        if self.params is not None:
-            rc = lib().fsaempc_sqp_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref(), P(x0), P(x_ref), P(u_init), *tail)
-        else:
-            rc = lib().fsaempc_sqp_batch_device(C.byref(self.desc), C.byref(self.sp), P(x0), P(x_ref), P(u_init), *tail)
-        check(rc, "fsaempc_sqp_batch_device")
+        rc = lib().fsaempc_sqp_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
+                                              P(x0), P(x_ref), P(u_init), *tail)
+        check(rc, "fsaempc_sqp_batch_device_p")
         return out
 
 
