@@ -3,9 +3,11 @@
     min 1/2 x'Hx + x'g   s.t.  lb <= x <= ub,  lbA <= A x <= ubA
 
 make(family, nV, nC, inst) returns H (nV, nV), g, A (nC, nV), lb, ub, lbA, ubA as mathematical matrices plus `x_star` (the closed-form
-minimiser, None where there is none); stack() puts a list of them into the device layout of the C ABI (H (B, nV, nV), A (B, nV, nC) =
-per-instance column-major nC x nV, vectors (B, *)).  Everything is deterministic: the matrices are seeded by (family, nV, nC, ha_inst),
-the vectors by (family, nV, nC, inst); ha_inst defaults to inst, and instances that name the same ha_inst share H and A.
+minimiser, None where there is none) and `lam_star` (its multipliers, nV + nC entries in the solver's convention
+H x + g - lam_b - A' lam_A = 0, None where there is no x_star); stack() puts a list of them into the device layout of the C ABI
+(H (B, nV, nV), A (B, nV, nC) = per-instance column-major nC x nV, vectors (B, *)).  Everything is deterministic: the matrices are
+seeded by (family, nV, nC, ha_inst), the vectors by (family, nV, nC, inst); ha_inst defaults to inst, and instances that name the
+same ha_inst share H and A.
 
 H is symmetric positive definite with eigenvalues log-spaced over 1 .. 1e3 in a random orthogonal basis.  Every QP is feasible by
 construction around a random point xs: bounds xs +- 1, row ranges A xs +- U(0.1, 1), unless the family says otherwise.
@@ -18,6 +20,10 @@ construction around a random point xs: bounds xs +- 1, row ranges A xs +- U(0.1,
      (A xs +- scale U(0.01, 0.3)); every third lbA and every third ubA (offset 1) is infinite, every second ub; variable 3 is fixed.
   S  slack column: the last variable has a zero row and column in H, cost 1e6, lb = 0, ub = inf, and enters every third row with
      coefficient -1; rows are upper-bounded only; the soft rows have ubA = A xs + U(-0.5, 1), so some of them need s > 0.
+  V  R without the duplicate (for the sensitivities, which need independent working rows): every array is R's except row 4, which
+     is a row of its own kind -- dense up to a random last column, its own scale 10^U(-4, 4), lbA = A xs - scale U(0.01, 0.3) and no
+     upper side, as the pattern of R gives row 4 -- drawn from streams of its own, so that R does not move.  Not in FAMILIES:
+     the tests of the forward solve do not run it.
 """
 import numpy as np
 
@@ -27,6 +33,15 @@ FAMILIES = ("F", "E", "R", "S")
 SHAPES = [(15, 3), (16, 16), (18, 7), (35, 50), (52, 70), (66, 33), (96, 130), (116, 40), (117, 30), (130, 65), (147, 257), (180, 64),
           (21, 60), (24, 200)]
 SHAPES_F_ONLY = [(20, 0)]
+# shapes for the tests of the VJP kernel (csrc/qp_sens.hip): those of SHAPES at which the working rows of V come out independent, plus
+# both sides of the switch of its factor from LDS to the workspace slot (np = 128: nV = 128 | 129), the next tile (144 | 145) and
+# FSAEMPC_MAX_NV; (16, 16) and (96, 130) have nV a multiple of 16 (no identity padding), F there has no working row at all
+VJP_SHAPES = [(15, 3), (16, 16), (18, 7), (35, 50), (66, 33), (96, 130), (116, 40), (117, 30), (130, 65), (180, 64),
+              (128, 40), (129, 40), (144, 30), (145, 30), (196, 50)]
+# first instance of the 8 that the VJP tests take, where it is not 0: with the CPU oracle as the forward, V (16, 16) instance 2,
+# (66, 33) instance 5 and (96, 130) instance 1 come back as interior-point iterates (refinement not accepted), and the working set
+# that the rule reads off such an iterate is not a vertex's (tests/test_sens_shapes_cpu.py asserts the conditions on the 8 taken)
+VJP_FIRST = {("V", 16, 16): 3, ("V", 66, 33): 6, ("V", 96, 130): 2}
 FILLER = 1e10          # the reference writes "no bound" as +-1e10 (ltvmpc_*.m); the solvers treat |bound| >= 1e9 as infinite
 KEYS = ("H", "g", "A", "lb", "ub", "lbA", "ubA")
 
@@ -36,7 +51,7 @@ def shapes(family):
 
 
 def _rng(family, nV, nC, inst, stream):
-    return np.random.default_rng([20260, FAMILIES.index(family), nV, nC, inst, stream])
+    return np.random.default_rng([20260, (FAMILIES + ("V",)).index(family), nV, nC, inst, stream])
 
 
 def _spd(rng, n):
@@ -51,9 +66,22 @@ def _no_bound(k, sign):
 
 
 def make(family, nV, nC, inst, ha_inst=None):
+    if family == "V":
+        q = make("R", nV, nC, inst, ha_inst)
+        q["family"] = "V"
+        if nC > 4:
+            rm = _rng("V", nV, nC, inst if ha_inst is None else ha_inst, 0)
+            rv = _rng("V", nV, nC, inst, 1)
+            xs = _rng("R", nV, nC, inst, 1).standard_normal(nV)   # the feasible point of R: the first draw of its vector stream
+            row = rm.standard_normal(nV)
+            row[np.arange(nV) > rm.integers(0, nV)] = 0.0
+            scale = 10.0 ** rm.uniform(-4.0, 4.0)
+            q["A"][4] = scale * row
+            q["lbA"][4], q["ubA"][4] = q["A"][4] @ xs - scale * rv.uniform(0.01, 0.3), np.inf
+        return q
     rm = _rng(family, nV, nC, inst if ha_inst is None else ha_inst, 0)   # matrices
     rv = _rng(family, nV, nC, inst, 1)                                   # vectors
-    x_star = None
+    x_star = lam_star = None
     if family == "S":
         H = np.zeros((nV, nV)); H[:nV - 1, :nV - 1] = _spd(rm, nV - 1)
     else:
@@ -65,6 +93,7 @@ def make(family, nV, nC, inst, ha_inst=None):
         lb, ub = _no_bound(nV, -1.0), _no_bound(nV, 1.0)
         lbA, ubA = _no_bound(nC, -1.0)[::-1].copy(), _no_bound(nC, 1.0)
         x_star = -np.linalg.solve(H, g)
+        lam_star = np.zeros(nV + nC)
     elif family == "E":
         lb, ub = _no_bound(nV, -1.0), _no_bound(nV, 1.0)
         lbA, ubA = _no_bound(nC, -1.0), _no_bound(nC, 1.0)[::-1].copy()
@@ -76,6 +105,8 @@ def make(family, nV, nC, inst, ha_inst=None):
         sol = np.linalg.solve(K, rhs)
         sol += np.linalg.solve(K, rhs - K @ sol)
         x_star = sol[:nV]
+        lam_star = np.zeros(nV + nC)
+        lam_star[nV:nV + k] = sol[nV:]
     elif family == "R":
         last = rm.integers(0, nV, nC)
         A[np.arange(nV)[None, :] > last[:, None]] = 0.0
@@ -108,7 +139,7 @@ def make(family, nV, nC, inst, ha_inst=None):
         lb[nV - 1], ub[nV - 1] = 0.0, np.inf
     else:
         raise ValueError(family)
-    return dict(H=H, g=g, A=A, lb=lb, ub=ub, lbA=lbA, ubA=ubA, x_star=x_star, family=family)
+    return dict(H=H, g=g, A=A, lb=lb, ub=ub, lbA=lbA, ubA=ubA, x_star=x_star, lam_star=lam_star, family=family)
 
 
 def make_infeasible(nV, nC, inst):
@@ -131,8 +162,18 @@ def stack(qps, shared_HA=False):
         out["A"] = np.ascontiguousarray(np.stack([q["A"].T for q in qps]))
     if all(q.get("x_star") is not None for q in qps):
         out["x_star"] = np.stack([q["x_star"] for q in qps])
+        out["lam_star"] = np.stack([q["lam_star"] for q in qps])
     return out
 
 
 def batch(family, nV, nC, B, first=0):
     return stack([make(family, nV, nC, first + i) for i in range(B)])
+
+
+def vjp_first(family, nV, nC):
+    return VJP_FIRST.get((family, nV, nC), 0)
+
+
+def vjp_batch(family, nV, nC, B):
+    """The batch that the VJP tests take of (family, nV, nC): B instances from vjp_first() on."""
+    return batch(family, nV, nC, B, first=vjp_first(family, nV, nC))

@@ -93,13 +93,17 @@ def test_affine_maps_match_the_build(fm, torch_, track, model, N):
 
 @pytest.mark.parametrize("model,N", [(0, 40), (1, 40)])
 def test_feedback_gain_matches_central_differences_of_the_step(fm, torch_, track, model, N):
-    torch = torch_
-    B = 64
+    check_feedback_gain(fm, torch_, track, model, N, 64)
+
+
+def check_feedback_gain(fm, torch, track, model, N, B):
+    """feedback_gain against central differences of the step in each x0 component, on every instance whose working set holds at
+    +-h (tests/test_sens_shapes_gpu.py runs it off N = 40 too).  Returns the figures it asserted on."""
     mpc, x0, xr, xl, ul = _setup(fm, torch, track, model, N, B)
     K, st = fm.feedback_gain(mpc, x0, xr, xl, ul)
     K, st = _np(K), _np(st)
     f0 = fm.ltv_step_lambda(mpc, x0, xr, xl, ul)
-    n_ok = 0
+    n_ok, worst = 0, 0.0
     for j in range(mpc.nx):
         h = 1e-5 * max(1.0, float(_np(x0[:, j].abs()).max()))
         fs, same = [], st == 0
@@ -111,16 +115,22 @@ def test_feedback_gain_matches_central_differences_of_the_step(fm, torch_, track
             fs.append(_np(f1["u_opt"])[:, :2])
         fd = (fs[0] - fs[1]) / (2 * h)
         err = np.abs(fd - K[:, :, j]).max(axis=1) / np.maximum(1.0, np.abs(K[:, :, j]).max(axis=1))
+        worst = max(worst, float(err[same].max()) if same.any() else 0.0)
         assert (err[same] <= 1e-6).all(), (j, np.sort(err[same])[-5:], int(same.sum()))
         n_ok += int(same.sum())
     assert n_ok >= mpc.nx * B // 4, n_ok
     assert (st >= 0).sum() >= B * 9 // 10, np.unique(st, return_counts=True)
+    return dict(nV=mpc.nV, compared=n_ok, of=mpc.nx * B, worst=worst, status=dict(zip(*(a.tolist() for a in np.unique(st, return_counts=True)))))
 
 
 @pytest.mark.parametrize("model,N", [(0, 40), (1, 40)])
 def test_step_vjp_matches_directional_differences_in_x0_and_xref(fm, torch_, track, model, N):
-    torch = torch_
-    B = 64
+    check_step_vjp(fm, torch_, track, model, N, 64)
+
+
+def check_step_vjp(fm, torch, track, model, N, B):
+    """The step VJP against directional differences of the step in x0 and x_ref, on every instance whose working set holds at +-h.
+    Returns the figures it asserted on."""
     mpc, x0, xr, xl, ul = _setup(fm, torch, track, model, N, B)
     rng = np.random.default_rng(1)
     cu = rng.standard_normal((B, 2 * N))
@@ -142,6 +152,8 @@ def test_step_vjp_matches_directional_differences_in_x0_and_xref(fm, torch_, tra
     err = np.abs(fd - an) / np.maximum(1.0, np.maximum(np.abs(an), np.abs(fd)))
     assert same.sum() >= B // 4, int(same.sum())
     assert (err[same] <= 1e-6).all(), (np.sort(err[same])[-5:], int(same.sum()))
+    return dict(nV=mpc.nV, compared=int(same.sum()), of=B, worst=float(err[same].max()),
+                status=dict(zip(*(a.tolist() for a in np.unique(st, return_counts=True)))))
 
 
 def test_ltv_step_function_gradients_equal_the_vjp(fm, torch_, track):
