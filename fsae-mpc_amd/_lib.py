@@ -31,6 +31,7 @@ EXPORTS = [
     "fsaempc_ltv_build_qp_batch_device_c", "fsaempc_ltv_step_batch_device_c", "fsaempc_cl_metrics_batch_device_c",
     "fsaempc_plan_raceline_batch_device_c", "fsaempc_corridor_line_bounds_device",
     "fsaempc_cl_lap_gate_batch_device", "fsaempc_cl_lap_summary",
+    "fsaempc_plan_raceline_cells_workspace_bytes", "fsaempc_plan_raceline_cells_batch_device", "fsaempc_corridor_line_rows_device",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -259,7 +260,13 @@ def lib():
         L.fsaempc_plan_raceline_batch_device_c.argtypes = [C.c_int, C.POINTER(Spline), C.c_double, C.POINTER(LtvParams), C.POINTER(CorridorTable),
                                                            C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(QpOpts),
                                                            vp, vp, vp, vp, vp, ll, vp]
-        L.fsaempc_cl_lap_gate_batch_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 9
+        L.fsaempc_plan_raceline_cells_workspace_bytes.restype = C.c_longlong
+        L.fsaempc_plan_raceline_cells_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.fsaempc_plan_raceline_cells_batch_device.argtypes = [C.c_int, C.POINTER(Spline), C.c_double, C.POINTER(LtvParams), C.POINTER(CorridorTable),
+                                                               C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(QpOpts),
+                                                               vp, vp, vp, vp, vp, vp, ll, vp]
+        L.fsaempc_corridor_line_rows_device.argtypes = [C.POINTER(CorridorTable), C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp]
+        L.fsaempc_cl_lap_gate_batch_device.argtypes =[C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 9
         L.fsaempc_cl_lap_summary.argtypes = [vp, C.c_int, C.c_int, vp]
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p

@@ -1,8 +1,8 @@
 """s-varying track corridors: the two edges of the track as periodic tables over arc length, in place of the one
 width N_MAX.  `Corridor.from_table` takes a user's own tables (a caller with cones resamples them over s first), `Corridor.constant`
 a band of fixed half-width.  A Corridor goes to LtvBatch / ClosedLoop / monte_carlo (`corridor=`: the MPC's track rows and the lap
-report's track violation) and to Plan.raceline (the box of every control point).  The limits are for the car's reference point: the
-caller subtracts the half-width of the car."""
+report's track violation) and to Plan.raceline (the box of every control point, or with rows="cells" one constraint row per cell).
+The limits are for the car's reference point: the caller subtracts the half-width of the car."""
 import ctypes as C
 import math
 
@@ -85,6 +85,23 @@ class Corridor:
                                                         C.c_void_p(lb.data_ptr()), C.c_void_p(ub.data_ptr()), st),
               "fsaempc_corridor_line_bounds_device")
         return lb, ub
+
+    def line_rows(self, N_s, N_c, margin, n_plans=None, stream=None):
+        """(A, lbA, ubA) on the device: the cell-wise rows Plan.raceline(corridor=self, rows="cells") hands to the line QP
+        (fsaempc_corridor_line_rows_device).  A (N_c, N_s) is the memory of the column-major N_s x N_c matrix, A[k, i] the weight of
+        control point k in the offset at cell i, one for the batch; lbA, ubA (n_plans, N_s), NaN where a cell has no room.  n_plans:
+        default the corridor's own count."""
+        import torch
+        n_plans = self.P if n_plans is None else int(n_plans)
+        self.check_batch(n_plans)
+        A = torch.empty((int(N_c), int(N_s)), dtype=torch.float64, device=self.device)
+        lbA = torch.empty((n_plans, int(N_s)), dtype=torch.float64, device=self.device)
+        ubA = torch.empty_like(lbA)
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream)
+        check(lib().fsaempc_corridor_line_rows_device(self.ref(), C.c_double(self.L), n_plans, int(N_s), int(N_c), C.c_double(margin),
+                                                      C.c_void_p(A.data_ptr()), C.c_void_p(lbA.data_ptr()), C.c_void_p(ubA.data_ptr()), st),
+              "fsaempc_corridor_line_rows_device")
+        return A, lbA, ubA
 
     def check_batch(self, B):
         if self.P not in (1, B):

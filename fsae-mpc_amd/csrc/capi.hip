@@ -1280,20 +1280,123 @@ int fsaempc_plan_raceline_batch_device_c(int model, const fsaempc_spline* sp, do
   return plan_raceline(model, sp, L, par, cor, n_plans, N_s, N_c, margin, v_cap, grip, opts, line, flag, table, t, workspace, workspace_bytes, stream);
 }
 
+// the checks of the entries that make the line's bounds or rows alone, after the corridor's and the pointers'
+static int line_rows_check(double L, int n_plans, int N_s, int N_c, double margin) {
+  if (!pos_finite(L)) return fail(FSAEMPC_ERR_ARG, "L must be finite and > 0");
+  if (N_c < FSAEMPC_LINE_MIN_NC || N_c > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_ARG, "N_c must be FSAEMPC_LINE_MIN_NC .. FSAEMPC_MAX_NV");
+  if (N_s < 2 * N_c || N_s > FSAEMPC_LINE_MAX_NS) return fail(FSAEMPC_ERR_ARG, "N_s must be 2 N_c .. FSAEMPC_LINE_MAX_NS");
+  if (n_plans < 1) return fail(FSAEMPC_ERR_ARG, "n_plans must be >= 1");
+  if (!(margin >= 0 && margin < INFINITY)) return fail(FSAEMPC_ERR_ARG, "margin must be finite and >= 0");
+  return 0;
+}
+
 int fsaempc_corridor_line_bounds_device(const fsaempc_corridor* cor, double L, int n_plans, int N_s, int N_c, double margin,
                                         double* lb, double* ub, void* stream) {
   CorLineParams CL;
   if (!cor) return fail(FSAEMPC_ERR_ARG, "null argument (corridor)");
   if (int rc = cor_check(cor, &CL.cor)) return rc;
   if (!lb || !ub) return fail(FSAEMPC_ERR_ARG, "null argument");
-  if (!pos_finite(L)) return fail(FSAEMPC_ERR_ARG, "L must be finite and > 0");
-  if (N_c < FSAEMPC_LINE_MIN_NC || N_c > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_ARG, "N_c must be FSAEMPC_LINE_MIN_NC .. FSAEMPC_MAX_NV");
-  if (N_s < 2 * N_c || N_s > FSAEMPC_LINE_MAX_NS) return fail(FSAEMPC_ERR_ARG, "N_s must be 2 N_c .. FSAEMPC_LINE_MAX_NS");
-  if (n_plans < 1) return fail(FSAEMPC_ERR_ARG, "n_plans must be >= 1");
-  if (!(margin >= 0 && margin < INFINITY)) return fail(FSAEMPC_ERR_ARG, "margin must be finite and >= 0");
+  if (int rc = line_rows_check(L, n_plans, N_s, N_c, margin)) return rc;
   CL.n_plans = n_plans; CL.N_s = N_s; CL.N_c = N_c; CL.L = L; CL.margin = margin; CL.g = nullptr; CL.lb = lb; CL.ub = ub; CL.line = nullptr; CL.flag = nullptr;
   hipError_t e = cor_line_bounds_launch(CL, (hipStream_t)stream);
   if (e != hipSuccess) return hipfail(e, "cor_line_bounds_launch");
+  return 0;
+}
+
+/* ---- the racing line with cell-wise corridor rows ---- */
+// The slack count handed to the solve, always given: N_s = 3 (N_c - 1) and 10 (N_c - 4) carry the signature of the LTV QPs, which must
+// not be read off a line QP.  0 up to twelve column tiles; the last four control points as the border beyond (N_c 193 .. 196, the
+// split the solver gives FSAEMPC_MAX_NV everywhere else): 13 tiles are more than the kernels are built for.
+static int cells_n_slack(int N_c) { return N_c > 16 * QP_MAX_T ? 4 : 0; }
+// workspace of fsaempc_plan_raceline_cells_batch_device:
+//   H | A (N_s x N_c) | g, lb, ub (n_plans x N_c each) | lbA, ubA (n_plans x N_s each) | fval | iter | lambda (n_plans x (N_c + N_s)) | the solver's own
+struct CellsCarve { size_t H, A, g, lb, ub, lbA, ubA, fval, iter, lambda, qp, total; long long qp_bytes; };
+static int cells_carve(int n_plans, int N_s, int N_c, CellsCarve* c) {
+  if (n_plans < 1 || N_c < FSAEMPC_LINE_MIN_NC || N_c > FSAEMPC_MAX_NV || N_s < 2 * N_c || N_s > FSAEMPC_LINE_MAX_NS) return FSAEMPC_ERR_ARG;
+  const fsaempc_qp_desc d = {N_c, N_s, n_plans, 1};
+  c->qp_bytes = fsaempc_qp_workspace_bytes_s(&d, cells_n_slack(N_c));
+  if (c->qp_bytes < 0) return (int)c->qp_bytes;
+  const size_t vec = align64((size_t)n_plans * N_c * sizeof(double)), row = align64((size_t)n_plans * N_s * sizeof(double));
+  size_t off = 0;
+  c->H = off; off += align64((size_t)N_c * N_c * sizeof(double));
+  c->A = off; off += align64((size_t)N_s * N_c * sizeof(double));
+  c->g = off; off += vec;
+  c->lb = off; off += vec;
+  c->ub = off; off += vec;
+  c->lbA = off; off += row;
+  c->ubA = off; off += row;
+  c->fval = off; off += align64((size_t)n_plans * sizeof(double));
+  c->iter = off; off += align64((size_t)n_plans * sizeof(int));
+  c->lambda = off; off += align64((size_t)n_plans * ((size_t)N_c + N_s) * sizeof(double));
+  c->qp = off; off += (size_t)c->qp_bytes;
+  c->total = off;
+  return 0;
+}
+long long fsaempc_plan_raceline_cells_workspace_bytes(int n_plans, int N_s, int N_c) {
+  CellsCarve c;
+  if (int rc = cells_carve(n_plans, N_s, N_c, &c)) return rc;
+  return (long long)c.total;
+}
+// what fsaempc_qp_solve_batch_device_s refuses for its shape, with its codes and texts, before anything is launched
+static int cells_shape_check(int N_s, int N_c) {
+  QpDims d; qp_make_dims(N_c, N_s, &d, cells_n_slack(N_c));
+  if (d.T > QP_MAX_T) return fail(FSAEMPC_ERR_DIM, "more column tiles than the kernels are built for");
+  if ((qp_runs_wavefront_kernel(d) ? d.lds_solve : d.lds_wg) > 160 * 1024 || d.lds_prep > 160 * 1024)
+    return fail(FSAEMPC_ERR_DIM, "problem exceeds the 160 KiB LDS budget of the kernels");
+  return 0;
+}
+
+int fsaempc_plan_raceline_cells_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, const fsaempc_corridor* cor,
+                                             int n_plans, int N_s, int N_c, double margin, double v_cap, double grip, const fsaempc_qp_opts* opts,
+                                             double* line, int* flag, double* table, double* t, double* row_lambda, void* workspace,
+                                             long long workspace_bytes, void* stream) {
+  CorLineRowsParams R;
+  if (!cor) return fail(FSAEMPC_ERR_ARG, "null argument (corridor)");
+  if (int rc = cor_check(cor, &R.cor)) return rc;
+  if (!line || !flag || !table || !t || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (int rc = line_check(sp, L, N_s, N_c)) return rc;
+  if (int rc = line_profile_check(model, par, n_plans, v_cap, grip)) return rc;
+  if (!(margin >= 0 && margin < INFINITY)) return fail(FSAEMPC_ERR_ARG, "margin must be finite and >= 0");
+  if (int rc = cells_shape_check(N_s, N_c)) return rc;
+  CellsCarve c;
+  if (int rc = cells_carve(n_plans, N_s, N_c, &c)) return fail(rc, "bad dimensions");
+  if ((long long)c.total > workspace_bytes) return fail(FSAEMPC_ERR_WORKSPACE, "workspace too small");
+  char* ws = (char*)workspace;
+  double *H = (double*)(ws + c.H), *g = (double*)(ws + c.g), *lambda = row_lambda ? (double*)(ws + c.lambda) : nullptr;
+  hipError_t e = raceline_qp_launch(line_qp_params(sp, L, N_s, N_c, H, g), (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "raceline_qp_launch");
+  R.n_plans = n_plans; R.N_s = N_s; R.N_c = N_c; R.L = L; R.margin = margin; R.A = (double*)(ws + c.A); R.lbA = (double*)(ws + c.lbA); R.ubA = (double*)(ws + c.ubA);
+  R.g = g; R.lb = (double*)(ws + c.lb); R.ub = (double*)(ws + c.ub);
+  e = cor_line_rows_launch(R, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "cor_line_rows_launch");
+  const fsaempc_qp_desc d = {N_c, N_s, n_plans, 1};
+  if (int rc = fsaempc_qp_solve_batch_device_s(&d, cells_n_slack(N_c), H, g, R.A, R.lb, R.ub, R.lbA, R.ubA, opts, line, (double*)(ws + c.fval), flag,
+                                               (int*)(ws + c.iter), lambda, nullptr, ws + c.qp, c.qp_bytes, stream)) return rc;
+  if (row_lambda) {
+    e = cor_line_lambda_launch(lambda, row_lambda, n_plans, N_s, N_c, (hipStream_t)stream);
+    if (e != hipSuccess) return hipfail(e, "cor_line_lambda_launch");
+  }
+  CorLineParams CL; CL.cor = R.cor;
+  CL.n_plans = n_plans; CL.N_s = N_s; CL.N_c = N_c; CL.L = L; CL.margin = margin; CL.g = g; CL.lb = R.lb; CL.ub = R.ub; CL.line = line; CL.flag = flag;
+  e = cor_line_void_launch(CL, (hipStream_t)stream);   // (no centre-line fallback: every plan whose flag is not 0 is NaN)
+  if (e != hipSuccess) return hipfail(e, "cor_line_void_launch");
+  PlanLineParams P = line_profile_params(model, sp, L, n_plans, N_s, N_c, v_cap, grip, table, t);
+  P.line = line; P.line_stride = N_c; P.flag = nullptr; P.line_out = line; P.check_width = 0; P.margin = margin;
+  e = plan_line_profile_launch(P, par_values(par), par_stride(par), (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "plan_line_profile_launch");
+  return 0;
+}
+
+int fsaempc_corridor_line_rows_device(const fsaempc_corridor* cor, double L, int n_plans, int N_s, int N_c, double margin,
+                                      double* A, double* lbA, double* ubA, void* stream) {
+  CorLineRowsParams R;
+  if (!cor) return fail(FSAEMPC_ERR_ARG, "null argument (corridor)");
+  if (int rc = cor_check(cor, &R.cor)) return rc;
+  if (!A || !lbA || !ubA) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (int rc = line_rows_check(L, n_plans, N_s, N_c, margin)) return rc;
+  R.n_plans = n_plans; R.N_s = N_s; R.N_c = N_c; R.L = L; R.margin = margin; R.A = A; R.lbA = lbA; R.ubA = ubA; R.g = nullptr; R.lb = nullptr; R.ub = nullptr;
+  hipError_t e = cor_line_rows_launch(R, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "cor_line_rows_launch");
   return 0;
 }
 

@@ -13,7 +13,8 @@
 //                 coefficients and kappa are linearised at (quirk C-8).  The first-order term -n_hi'(s) (s_k - s_lin,k) is left out:
 //                 the stated approximation of 6l.  The matrix A and the 1e10 / -1e10 fillers of the rows' other sides stay.
 //   lap report    v = max(n - n_hi(s), n_lo(s) - n) in place of |n| - N_MAX
-//   racing line   per control point the tightest limits of the cells whose basis touches it, minus the margin
+//   racing line   per control point the tightest limits of the cells whose basis touches it, minus the margin; or, opt-in, one
+//                 general constraint row per cell with the control points free (cor_line_rows_launch)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -74,3 +75,21 @@ struct CorLineParams {
 };
 hipError_t cor_line_bounds_launch(const CorLineParams& P, hipStream_t st);
 hipError_t cor_line_void_launch(const CorLineParams& P, hipStream_t st);
+
+// The cell-wise form of the line QP's corridor: one general constraint row per cell, lbA_i <= n_i <= ubA_i with
+//   n_i = sum_m w_m(u_i) c[(j_i - 1 + m) mod N_c]  (rl_offset_row of raceline.h),  lbA_i = n_lo(s_i) + margin,  ubA_i = n_hi(s_i) - margin,
+// s_i = i L / N_s.  The matrix depends on (N_s, N_c) alone: one A (N_s x N_c, column-major) for the batch, lbA / ubA per plan.  A cell
+// whose lookup is NaN, or where lbA_i < ubA_i does not hold, gets NaN for both: that plan's QP has non-finite data and the solve
+// answers -1 before its first iteration, for that plan alone.  The control points are free: lb = -1e10, ub = 1e10 (the filler of the
+// LTV rows, beyond the solver's inf_bound).  Every element of every output given is written.
+struct CorLineRowsParams {
+  int n_plans, N_s, N_c;
+  double L, margin;
+  double* A;                           // N_s x N_c, column-major
+  double* lbA; double* ubA;            // n_plans x N_s each
+  double* g; double* lb; double* ub;   // n_plans x N_c each (g: row 0 filled by raceline_qp_launch); all three NULL: rows only
+  CorTable cor;
+};
+hipError_t cor_line_rows_launch(const CorLineRowsParams& P, hipStream_t st);
+// row_lambda[p][i] = lambda[p][N_c + i]: the multipliers of the cell rows out of the solver's nV + nC per plan
+hipError_t cor_line_lambda_launch(const double* lambda, double* row_lambda, int n_plans, int N_s, int N_c, hipStream_t st);

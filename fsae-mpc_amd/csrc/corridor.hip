@@ -7,10 +7,14 @@
 //   cor_line_bounds_kernel  raceline_bounds_kernel (raceline.hip) with the box of every control point from the corridor's cells; a
 //                           control point without a box gets NaN bounds, which the solve answers with flag -1 before its first iteration
 //   cor_line_void_kernel    after the line solve: NaN control points for every plan whose QP did not end with flag 0
+//   cor_line_rows_kernel    the cell-wise form of the line's corridor: the one matrix of the cells' offsets in the control points,
+//                           the bounds of its rows per plan from the corridor, free control points and the plan's copy of g
+//   cor_line_lambda_kernel  the cell rows' multipliers out of the solver's lambda
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "fsaempc.h"
 #include "corridor.h"
+#include "raceline.h"
 #include "mpc_params.h"
 
 namespace {
@@ -122,7 +126,61 @@ __global__ void __launch_bounds__(64) cor_line_void_kernel(CorLineParams P) {
   for (int j = threadIdx.x; j < Nc; j += 64) P.line[(size_t)plan * Nc + j] = NAN;
 }
 
+// The grid is nA = ceil(N_s N_c / 256) workgroups for the matrix, then nP = ceil((N_s + N_c) / 256) workgroups per plan.
+//   matrix   element e = k N_s + i of the column-major A: consecutive lanes are consecutive cells i of one column k, so a wavefront
+//            stores 512 contiguous bytes.  The cell's four columns are distinct (N_c >= 8); every other entry is written as 0.
+//   plan p   item r < N_s: the bounds of row r; item N_s + j: the free box of control point j and the plan's copy of g_j
+__global__ void __launch_bounds__(256) cor_line_rows_kernel(CorLineRowsParams P, int nA, int nP) {
+#pragma clang fp contract(off)
+  const int Ns = P.N_s, Nc = P.N_c;
+  if ((int)blockIdx.x < nA) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)Ns * Nc) return;
+    const int k = (int)(e / Ns), i = (int)(e % Ns);
+    int col0; double w[4];
+    rl_offset_row(i, Ns, Nc, col0, w);
+    int m = k - col0;
+    if (m < 0) m += Nc;
+    P.A[e] = m < 4 ? rl_pick<4>(w, m) : 0.0;
+    return;
+  }
+  const int rel = (int)blockIdx.x - nA, plan = rel / nP, r = (rel % nP) * 256 + (int)threadIdx.x;
+  if (r < Ns) {
+    const double s = (double)r * P.L / (double)Ns;
+    double lo, hi;
+    cor_lookup(P.cor, plan, s, lo, hi);
+    double l = lo + P.margin, h = hi - P.margin;
+    if (!(l < h)) { l = NAN; h = NAN; }   // (a NaN lookup included: the QP of this plan has non-finite data and is not solved)
+    P.lbA[(size_t)plan * Ns + r] = l;
+    P.ubA[(size_t)plan * Ns + r] = h;
+  } else if (r < Ns + Nc && P.lb) {
+    const int j = r - Ns;
+    P.lb[(size_t)plan * Nc + j] = -1e10;
+    P.ub[(size_t)plan * Nc + j] = 1e10;
+    if (plan > 0) P.g[(size_t)plan * Nc + j] = P.g[j];
+  }
+}
+
+__global__ void __launch_bounds__(256) cor_line_lambda_kernel(const double* lambda, double* row_lambda, int n_plans, int Ns, int Nc) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)n_plans * Ns) return;
+  const long long p = t / Ns, i = t % Ns;
+  row_lambda[t] = lambda[p * (Nc + Ns) + Nc + i];
+}
+
 }  // namespace
+
+hipError_t cor_line_rows_launch(const CorLineRowsParams& P, hipStream_t st) {
+  if (P.n_plans == 0) return hipSuccess;
+  const int nA = (int)(((long long)P.N_s * P.N_c + 255) / 256), nP = (P.N_s + P.N_c + 255) / 256;
+  hipLaunchKernelGGL(cor_line_rows_kernel, dim3((unsigned)(nA + (long long)P.n_plans * nP)), dim3(256), 0, st, P, nA, nP);
+  return hipGetLastError();
+}
+hipError_t cor_line_lambda_launch(const double* lambda, double* row_lambda, int n_plans, int N_s, int N_c, hipStream_t st) {
+  if (n_plans == 0) return hipSuccess;
+  hipLaunchKernelGGL(cor_line_lambda_kernel, dim3((unsigned)(((long long)n_plans * N_s + 255) / 256)), dim3(256), 0, st, lambda, row_lambda, n_plans, N_s, N_c);
+  return hipGetLastError();
+}
 
 hipError_t cor_rows_launch(const CorRowsParams& P, hipStream_t st) {
   if (P.batch == 0) return hipSuccess;

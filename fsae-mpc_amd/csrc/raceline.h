@@ -6,6 +6,7 @@
 // of the track, vehicle_models/curvilinear_to_cartesian.m:19-26), n = B c.
 //
 //   rl_basis / rl_weights / rl_dweights   cell -> first control point and the four weights (and their derivatives in u)
+//   rl_offset_row  cell -> the offset n_i as a row of the control points: first column and the four weights
 //   rl_cell        the second difference of the line's points at one cell as a function of the control points: at most five
 //                  consecutive control points take part (N_s >= 2 N_c), so a cell is two local rows of five and the constant d_i
 //   rl_row         one row of the band of H = 2 ds G'G and one entry of g = 2 ds G'd: the sum over the cells that touch the control
@@ -59,6 +60,15 @@ RL_HD void rl_dweights(double u, double* w) {
   w[1] = (9.0 * u * u - 12.0 * u) / 6.0;
   w[2] = (-9.0 * u * u + 6.0 * u + 3.0) / 6.0;
   w[3] = 3.0 * u * u / 6.0;
+}
+
+// The offset at cell i as a row of the control points: n_i = sum_m w[m] c[(col0 + m) mod N_c], col0 = (j_i - 1) mod N_c.  The row of
+// the cell-wise corridor constraints; with N_c >= 4 the four columns are distinct.
+RL_HD void rl_offset_row(int i, int Ns, int Nc, int& col0, double* w) {
+  int j; double u;
+  rl_basis(i, Ns, Nc, j, u);
+  rl_weights(u, w);
+  col0 = j > 0 ? j - 1 : Nc - 1;
 }
 
 // first control point (cyclic) of the five a cell's second difference can touch: cell i - 1 starts the window

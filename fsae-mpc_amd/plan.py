@@ -99,6 +99,7 @@ class Plan:
         self.device = table.device
         self.c = PlanTable(C.c_void_p(table.data_ptr()), C.c_void_p(t.data_ptr()), self.N_s, self.ds, 1 if self.P > 1 else 0)
         self.line, self.line_flag = None, None   # control points of the lateral offset and the flags of their QPs (Plan.raceline)
+        self.row_lambda = None                   # multipliers of the cell rows (Plan.raceline(rows="cells", want_row_lambda=True))
 
     def ref(self):
         return C.byref(self.c)
@@ -149,7 +150,7 @@ class Plan:
 
     @staticmethod
     def raceline(model, track, N_s=500, N_c=100, margin=0.25, v_cap=20.0, grip=1.0, params=None, n_plans=1, options=None, device="cuda:0",
-                 stream=None, corridor=None):
+                 stream=None, corridor=None, rows="points", want_row_lambda=False):
         """Racing-line plans (fsaempc_plan_raceline_batch_device): a minimum-curvature line within +-(N_MAX - margin) of
         the centre line (N_MAX: the block's, default 0.75) as N_c control points of a periodic cubic B-spline, then the profile of
         Plan.profile on it.  Returns a Plan with .line (P, N_c) control points and .line_flag (P,) exit flags of the line QPs; a plan
@@ -157,9 +158,21 @@ class Plan:
         the line stays within [n_lo + margin, n_hi - margin] at every cell (fsaempc_plan_raceline_batch_device_c, DESIGN.md 6l: each
         control point takes the tightest limits of the cells it touches, so a pinch is smeared over four knot spacings).  A plan whose
         corridor leaves a control point no room has flag -1 and is NaN; in a corridor NO plan falls back to the centre line (it may
-        lie outside the corridor): every plan whose flag is not 0 is NaN in table, t and line."""
+        lie outside the corridor): every plan whose flag is not 0 is NaN in table, t and line.
+        rows: "points" (the default: the box of every control point, as above) or "cells": one constraint row per cell,
+        n_lo(s_i) + margin <= n_i <= n_hi(s_i) - margin, with free control points (fsaempc_plan_raceline_cells_batch_device).  The
+        line then uses the width of every single cell, and its control points may lie outside the corridor; it is inside the corridor
+        at the N_s cells, not between them.  "cells" needs a corridor (Corridor.constant(L, half_width) for a band of fixed width).
+        want_row_lambda (rows="cells" only): the plan carries .row_lambda (P, N_s), the multipliers of the cell rows (>= 0 on the
+        right edge n_lo, <= 0 on the left edge n_hi, 0 where the corridor does not bind)."""
         check_profile_args(N_s, v_cap, grip, n_plans)
         check_line_args(N_s, N_c, margin)
+        if rows not in ("points", "cells"):
+            raise ValueError("rows must be \"points\" or \"cells\", got %r" % (rows,))
+        if rows == "cells" and corridor is None:
+            raise ValueError("rows=\"cells\" needs a corridor: Corridor.constant(L, half_width) is the band of fixed width")
+        if want_row_lambda and rows != "cells":
+            raise ValueError("want_row_lambda needs rows=\"cells\"")
         if model not in (0, 1):
             raise ValueError("unknown model %r" % (model,))
         params, n_plans = check_params(params, n_plans)
@@ -177,9 +190,10 @@ class Plan:
         xP, yP = track.device(dev)
         sp = Spline(track.M, track.dl, C.c_void_p(xP.data_ptr()), C.c_void_p(yP.data_ptr()))
         blocks = ParamBlock(params, n_plans, dev) if params is not None else None
-        need = lib().fsaempc_plan_raceline_workspace_bytes(n_plans, N_c)
+        cells = rows == "cells"
+        need = lib().fsaempc_plan_raceline_cells_workspace_bytes(n_plans, N_s, N_c) if cells else lib().fsaempc_plan_raceline_workspace_bytes(n_plans, N_c)
         if need < 0:
-            check(int(need), "fsaempc_plan_raceline_workspace_bytes")
+            check(int(need), "fsaempc_plan_raceline_cells_workspace_bytes" if cells else "fsaempc_plan_raceline_workspace_bytes")
         ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
         line = torch.empty((n_plans, N_c), dtype=torch.float64, device=dev)
         flag = torch.empty(n_plans, dtype=torch.int32, device=dev)
@@ -188,14 +202,24 @@ class Plan:
         opts = options if options is not None else default_opts()
         st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
         p = lambda a: C.c_void_p(a.data_ptr())
-        rc = lib().fsaempc_plan_raceline_batch_device_c(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
-                                                        corridor.ref() if corridor is not None else None, n_plans, N_s, N_c, C.c_double(margin),
-                                                        C.c_double(v_cap), C.c_double(grip), C.byref(opts), p(line), p(flag), p(table), p(t), p(ws),
-                                                        C.c_longlong(ws.numel() * 8), st)
-        check(rc, "fsaempc_plan_raceline_batch_device_c")
+        row_lambda = None
+        if cells:
+            row_lambda = torch.empty((n_plans, N_s), dtype=torch.float64, device=dev) if want_row_lambda else None
+            rc = lib().fsaempc_plan_raceline_cells_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                                corridor.ref(), n_plans, N_s, N_c, C.c_double(margin), C.c_double(v_cap),
+                                                                C.c_double(grip), C.byref(opts), p(line), p(flag), p(table), p(t),
+                                                                p(row_lambda) if row_lambda is not None else None, p(ws),
+                                                                C.c_longlong(ws.numel() * 8), st)
+            check(rc, "fsaempc_plan_raceline_cells_batch_device")
+        else:
+            rc = lib().fsaempc_plan_raceline_batch_device_c(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                            corridor.ref() if corridor is not None else None, n_plans, N_s, N_c, C.c_double(margin),
+                                                            C.c_double(v_cap), C.c_double(grip), C.byref(opts), p(line), p(flag), p(table), p(t), p(ws),
+                                                            C.c_longlong(ws.numel() * 8), st)
+            check(rc, "fsaempc_plan_raceline_batch_device_c")
         plan = Plan(table, t, track.L / N_s)
         plan._blocks, plan._ws, plan._corridor = blocks, ws, corridor   # (read by launches that may still be queued)
-        plan.line, plan.line_flag = line, flag
+        plan.line, plan.line_flag, plan.row_lambda = line, flag, row_lambda
         return plan
 
     @staticmethod

@@ -784,6 +784,41 @@ int fsaempc_plan_raceline_batch_device_c(int model, const fsaempc_spline* sp, do
 int fsaempc_corridor_line_bounds_device(const fsaempc_corridor* cor, double L, int n_plans, int N_s, int N_c, double margin,
                                         double* lb, double* ub, void* stream);
 
+/*
+ * The racing line inside the corridor in its exact, cell-wise form (opt-in; the entries above are unchanged).  The offset at cell i is
+ * n_i = sum_m w_m(u_i) c_{(j_i - 1 + m) mod N_c}, four non-negative weights that sum to one, so the corridor is one general constraint
+ * row per cell and the control points are free variables:
+ *   lbA_i = n_lo(s_i) + margin  <=  n_i  <=  ubA_i = n_hi(s_i) - margin,        s_i = i L / N_s,        lb_j = -1e10, ub_j = 1e10.
+ * The matrix A of the rows (N_s x N_c, column-major; entry (i, k) = w_m(u_i) where k = (j_i - 1 + m) mod N_c, else 0) depends on
+ * (N_s, N_c) alone: one A and one H serve the batch (shared_HA), lbA and ubA are per plan.  The QP goes to
+ * fsaempc_qp_solve_batch_device_s with nV = N_c, nC = N_s and the slack count always given (0; 4 for N_c > 192, where the last four
+ * control points form the border: 13 column tiles are more than the kernels are built for); a shape that solve refuses (column
+ * tiles, LDS budget) is refused here with its code and text, before any launch.  Where the point boxes above smear a pinch over four knot spacings and are
+ * conservative even in a constant band, this form uses every cell's own width; control points may lie outside the corridor.  The
+ * stated approximation: the line is inside the corridor at the N_s cells, not between them, and the speed profile does not know the
+ * corridor.  A cell whose lookup is NaN, or where lbA_i < ubA_i does not hold (n_hi - n_lo <= 2 margin), gets NaN for both bounds:
+ * that plan's QP has non-finite data, its flag is -1 (no iteration) and the plan is NaN in table, t and line; the other plans are
+ * unaffected.  As in the _c entry NO plan falls back to the centre line: every plan whose flag is not 0 is NaN in table, t and line.
+ * cor is required; per_instance: one corridor per plan.  A block's N_MAX is not read.
+ * row_lambda: NULL, or n_plans * N_s (device): the multipliers of the cell rows in the solver's sign convention (>= 0 where n_i sits
+ * on lbA_i, <= 0 on ubA_i, 0 where the corridor does not bind); no other output depends on whether it is given.
+ * workspace: fsaempc_plan_raceline_cells_workspace_bytes(n_plans, N_s, N_c) bytes, carved as
+ *   H | A | g, lb, ub (n_plans x N_c each) | lbA, ubA (n_plans x N_s each) | fval | iter | lambda (n_plans x (N_c + N_s)) | the solver's own;
+ * every element read is written by the call, nothing relies on a zeroed workspace.
+ * FSAEMPC_ERR_ARG before any launch: cor == NULL, the corridor's cases, the cases of fsaempc_plan_raceline_batch_device_c;
+ * FSAEMPC_ERR_WORKSPACE: workspace too small.  The size function answers FSAEMPC_ERR_ARG / FSAEMPC_ERR_DIM (< 0) for such shapes.
+ */
+long long fsaempc_plan_raceline_cells_workspace_bytes(int n_plans, int N_s, int N_c);
+int fsaempc_plan_raceline_cells_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par,
+                                             const fsaempc_corridor* cor,
+                                             int n_plans, int N_s, int N_c, double margin, double v_cap, double grip,
+                                             const fsaempc_qp_opts* opts, double* line, int* flag, double* table, double* t,
+                                             double* row_lambda, void* workspace, long long workspace_bytes, void* stream);
+/* The rows alone, as the call above hands them to the solve (A: N_s * N_c, written once; lbA, ubA: n_plans * N_s each, device; NaN
+ * where a cell has no room): for inspection and timing, the counterpart of fsaempc_corridor_line_bounds_device, with its errors. */
+int fsaempc_corridor_line_rows_device(const fsaempc_corridor* cor, double L, int n_plans, int N_s, int N_c, double margin,
+                                      double* A, double* lbA, double* ubA, void* stream);
+
 /* ---- multi-lap closed loop: the lap gate ---------------------------------------------
  * The loop above ends a car's run the first time the pre-step sees s >= L (main.m:102-104).  The gate carries a car over the line
  * instead, up to `laps` laps: it times the crossing inside the period, hands the lap's record over and takes L off every arc

@@ -8,6 +8,8 @@ driving, the exit-flag tally the way main.m:209,222 reports it ("abnormal exits 
 --report: the lap report (main.m:196-228 over the batch) joins the JSON line as "lap_report".
 --corridor FILE.npz: an s-varying track corridor (fsaempc.Corridor) from arrays n_lo, n_hi of (N_w,) over the lap of the
 track; the controller's track rows, the report's track violation and, with --raceline, the line's bounds are taken against it.
+--line-rows points|cells: with --raceline and --corridor, the form of the line's corridor constraints: the box of every control point (the
+default) or one constraint row per cell (Plan.raceline(rows="cells")).
 --lap: every car starts at s = 0 on the centre line, at rest, with the usual lateral and heading scatter (main.m:63), and the step cap
 defaults to 1000 (main.m:62): a finished car's STEPS * dt is then a lap time.
 --laps K: every car drives K consecutive laps (ClosedLoop(laps=K), DESIGN.md 6m: the lap gate carries it over the line and times the
@@ -15,7 +17,7 @@ crossing to a fraction of dt); with --lap the step cap defaults to 1000 K; the p
 max of its time) joins the JSON line as "lap_summary".
 usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--track fss2019]
                                   [--plan | --raceline [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap] [--laps K]
-                                  [--corridor FILE.npz]"""
+                                  [--corridor FILE.npz [--line-rows points|cells]]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -45,7 +47,11 @@ def main():
     ap.add_argument("--margin", type=float, default=0.25, help="with --raceline: distance the line keeps from N_MAX, m")
     ap.add_argument("--points", type=int, default=100, help="with --raceline: control points of the line (N_c)")
     ap.add_argument("--corridor", default=None, metavar="FILE.npz", help="track corridor: arrays n_lo, n_hi of (N_w,) over the lap (Corridor.from_table)")
+    ap.add_argument("--line-rows", default="points", choices=["points", "cells"],
+                    help="with --raceline --corridor: the line's corridor as boxes on the control points or as one row per cell")
     a = ap.parse_args()
+    if a.line_rows == "cells" and not (a.raceline and a.corridor is not None):
+        ap.error("--line-rows cells needs --raceline and --corridor")
     if a.steps is None:
         a.steps = 1000 * a.laps if a.lap else 200
     model = fm.KINEMATIC if a.model == "kinematic" else fm.DYNAMIC
@@ -56,7 +62,7 @@ def main():
             cor = fm.Corridor.from_table(z["n_lo"], z["n_hi"], tr.L)
     plan = fm.Plan.profile(model, tr, N_s=a.cells, grip=a.grip) if a.plan else None
     if a.raceline:
-        plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip, corridor=cor)
+        plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip, corridor=cor, rows=a.line_rows)
     fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor)          # warm-up (allocations, code load)
     n_max = float(fm.default_params(model)[fm.PARAM_INDEX["N_MAX"]])
     opts = fm.default_opts(max_iter=a.max_iter)
@@ -122,7 +128,7 @@ def main():
                    "mean_ipm_iterations": float(it[ac].mean()) if n_act else 0.0,
                    "cars_past_end_of_track_parameter": int((cl.finished == 1).sum().item()), "cars_lost": int((cl.finished == 2).sum().item()),
                    "mean_speed_end": float(cl.cart[:, 3].mean().item()),
-                   "reference": ("plan: racing line, N_s = %d, N_c = %d, margin %g, grip %g, QP flag %d, lap %.2f s" % (a.cells, a.points, a.margin, a.grip, int(plan.line_flag[0]), float(plan.lap_time()[0]))) if a.raceline
+                   "reference": ("plan: racing line, N_s = %d, N_c = %d, margin %g, grip %g, corridor rows: %s, QP flag %d, lap %.2f s" % (a.cells, a.points, a.margin, a.grip, a.line_rows, int(plan.line_flag[0]), float(plan.lap_time()[0]))) if a.raceline
                                 else ("plan: speed profile, N_s = %d, grip %g, lap %.2f s" % (a.cells, a.grip, float(plan.lap_time()[0]))) if a.plan else "live ramp to 20 m/s",
                    "steps_off_track_abs_n_gt_N_MAX": int(off.item()), "mean_distance_covered_m": float(np.nanmean(dist)),
                    "total_distance_covered_m": float(np.nansum(dist)),

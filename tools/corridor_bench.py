@@ -5,7 +5,11 @@
   default                one JSON line: the fused step with a (constant) corridor (_c entry) against the step without one (kinematic N = 40,
                          B = 4096, same process, median of 20 launches after 5 warm-ups, HIP events), and Plan.raceline with and
                          without a corridor (N_s 500, N_c 100) and the line's control-point bounds kernel alone, measured the same way.
-usage: tools/corridor_bench.py [--make TRACK OUT.npz [--wide W] [--narrow W] [--kappa K] [--cells N_w]] [--batch 4096] [--horizon 40]"""
+  --line-rows            one JSON line: Plan.raceline (N_s 500, N_c 100, fsg2019, the corridor of --make) with rows="cells" against rows="points",
+                         for 1 and 256 plans (a corridor each), and the rows call alone (Corridor.line_rows), measured the same way.
+  --line-rows-once P     P plans through one Plan.raceline(rows="cells") call after one warm-up, for a kernel trace.
+usage: tools/corridor_bench.py [--make TRACK OUT.npz [--wide W] [--narrow W] [--kappa K] [--cells N_w]] [--batch 4096] [--horizon 40]
+                               [--line-rows | --line-rows-once P]"""
 import argparse, json, os, sys
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -44,6 +48,8 @@ def main():
     ap.add_argument("--cells", type=int, default=500)
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--horizon", type=int, default=40)
+    ap.add_argument("--line-rows", action="store_true")
+    ap.add_argument("--line-rows-once", type=int, default=0, metavar="P")
     a = ap.parse_args()
     import fsae_mpc_amd as fm
     if a.make is not None:
@@ -55,6 +61,29 @@ def main():
         return
     import torch
     tr = fm.Track.load("fsg2019")
+    if a.line_rows or a.line_rows_once:
+        s = np.arange(a.cells) * tr.L / a.cells
+        w = np.where(np.abs(kappa_host(tr, s)) < a.kappa, a.wide, a.narrow)
+        cors = {P: fm.Corridor.from_table(np.tile(-w, (P, 1)), np.tile(w, (P, 1)), tr.L) for P in sorted({1, 256, max(1, a.line_rows_once)})}
+        line = lambda P, rows: fm.Plan.raceline(fm.DYNAMIC, tr, N_s=500, N_c=100, corridor=cors[P], rows=rows)
+        if a.line_rows_once:
+            for _ in range(2):
+                plan = line(a.line_rows_once, "cells")
+                torch.cuda.synchronize()
+            print(json.dumps({"plans": a.line_rows_once, "flags_not_0": int((plan.line_flag != 0).sum().item()), "lap_s": float(plan.lap_time()[0])}))
+            return
+        out = {"what": "median / min / max ms of 20 calls after 5 warm-ups, HIP events, one process; fsg2019, dynamic model, N_s 500, N_c 100, "
+                       "+-%g m where |kappa| < %g, +-%g m elsewhere (%d cells), one corridor per plan; whole Plan.raceline call, allocations included"
+                       % (a.wide, a.kappa, a.narrow, a.cells)}
+        for P in (1, 256):
+            out["plans_%d" % P] = {"points_ms": median_ms(torch, lambda: line(P, "points")), "cells_ms": median_ms(torch, lambda: line(P, "cells")),
+                                   "points_again_ms": median_ms(torch, lambda: line(P, "points")),
+                                   "rows_call_alone_ms": median_ms(torch, lambda: cors[P].line_rows(500, 100, 0.25)),
+                                   "bounds_call_alone_ms": median_ms(torch, lambda: cors[P].line_bounds(500, 100, 0.25))}
+            pc, pp = line(P, "cells"), line(P, "points")
+            out["plans_%d" % P].update(flags_not_0=int((pc.line_flag != 0).sum().item()), lap_cells_s=float(pc.lap_time()[0]), lap_points_s=float(pp.lap_time()[0]))
+        print(json.dumps(out))
+        return
     model, N, B = fm.KINEMATIC, a.horizon, a.batch
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
     x0, xl, ul, xr = (dev(v) for v in fm.instances(model, N, 0.05, tr.L, 20190, range(B)))
