@@ -13,7 +13,7 @@ all: $(LIBDIR)/libfsaempc.so oracle o1 dbg
 CC_CHECKED := HIPCC=$(HIPCC) tools/hipcc_checked.sh
 CHECKDEPS := tools/hipcc_checked.sh tools/check_isa_exec_prologue.py
 
-$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/qp_solver.h $(CSRC)/qp_sens.h $(CSRC)/ltv_build.h $(CSRC)/nlp_model.h $(CSRC)/ltv_model.h $(CSRC)/mpc_params.h $(CSRC)/sqp.h $(CSRC)/reference.h $(CSRC)/plant.h $(CSRC)/planner.h $(CSRC)/raceline.h $(CSRC)/corridor.h $(CSRC)/cl_frame.h include/fsaempc.h $(CHECKDEPS)
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/qp_solver.h $(CSRC)/qp_sens.h $(CSRC)/ltv_build.h $(CSRC)/nlp_model.h $(CSRC)/ltv_model.h $(CSRC)/mpc_params.h $(CSRC)/sqp.h $(CSRC)/reference.h $(CSRC)/plant.h $(CSRC)/planner.h $(CSRC)/raceline.h $(CSRC)/corridor.h $(CSRC)/cones.h $(CSRC)/cl_frame.h include/fsaempc.h $(CHECKDEPS)
 	@mkdir -p $(LIBDIR)
 	$(CC_CHECKED) $@ $< $(HIPFLAGS)
 
@@ -41,7 +41,7 @@ $(LIBDIR)/track.o: $(CSRC)/track.cpp include/fsaempc.h
 	@mkdir -p $(LIBDIR)
 	g++ -O2 -std=c++17 -fPIC -Wall -Iinclude -c $< -o $@
 
-COMMON := $(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o $(LIBDIR)/sqp.o $(LIBDIR)/qp_sens.o $(LIBDIR)/reference.o $(LIBDIR)/plant.o $(LIBDIR)/planner.o $(LIBDIR)/raceline.o $(LIBDIR)/corridor.o $(LIBDIR)/capi.o $(LIBDIR)/track.o
+COMMON := $(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o $(LIBDIR)/sqp.o $(LIBDIR)/qp_sens.o $(LIBDIR)/reference.o $(LIBDIR)/plant.o $(LIBDIR)/planner.o $(LIBDIR)/raceline.o $(LIBDIR)/corridor.o $(LIBDIR)/cones.o $(LIBDIR)/capi.o $(LIBDIR)/track.o
 $(LIBDIR)/libfsaempc.so: $(QPOBJ) $(WGOBJ) $(COMMON)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

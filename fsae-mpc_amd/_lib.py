@@ -32,6 +32,7 @@ EXPORTS = [
     "fsaempc_plan_raceline_batch_device_c", "fsaempc_corridor_line_bounds_device",
     "fsaempc_cl_lap_gate_batch_device", "fsaempc_cl_lap_summary",
     "fsaempc_plan_raceline_cells_workspace_bytes", "fsaempc_plan_raceline_cells_batch_device", "fsaempc_corridor_line_rows_device",
+    "fsaempc_corridor_from_cones_device", "fsaempc_track_cones_from_csv", "fsaempc_track_cones_free",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -118,6 +119,17 @@ class PlanTable(C.Structure):   # fsaempc_plan
 
 class CorridorTable(C.Structure):   # fsaempc_corridor
     _fields_ = [("n_lo", C.c_void_p), ("n_hi", C.c_void_p), ("N_w", C.c_int), ("ds", C.c_double), ("per_instance", C.c_int)]
+
+
+NCONEINFO = 8        # FSAEMPC_NCONEINFO
+CONES_MAX = 512      # FSAEMPC_CONES_MAX
+CONES_MAX_M = 512    # FSAEMPC_CONES_MAX_M
+CONE_INFO_INDEX = {name: i for i, name in enumerate(
+    ["KEPT_LEFT", "KEPT_RIGHT", "ABSENT", "UNPROJECTED", "BEYOND_REACH", "CELLS_OFF_SEGMENT", "CELLS_NO_ROOM", "WIDTH_MIN"])}
+
+
+class ConeMaps(C.Structure):   # fsaempc_cones
+    _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("n_left", C.c_int), ("n_right", C.c_int), ("per_corridor", C.c_int)]
 
 
 def check_blocking(blocking, N):
@@ -266,6 +278,12 @@ def lib():
                                                                C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(QpOpts),
                                                                vp, vp, vp, vp, vp, vp, ll, vp]
         L.fsaempc_corridor_line_rows_device.argtypes = [C.POINTER(CorridorTable), C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp]
+        L.fsaempc_corridor_from_cones_device.argtypes = [C.POINTER(Spline), C.c_double, C.POINTER(ConeMaps), C.c_int, C.c_int, C.c_double, C.c_double,
+                                                         vp, vp, vp, vp]
+        L.fsaempc_track_cones_from_csv.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int),
+                                                   C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int)]
+        L.fsaempc_track_cones_free.argtypes = [C.POINTER(C.c_double)]
+        L.fsaempc_track_cones_free.restype = None
         L.fsaempc_cl_lap_gate_batch_device.argtypes =[C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 9
         L.fsaempc_cl_lap_summary.argtypes = [vp, C.c_int, C.c_int, vp]
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]

@@ -1,14 +1,17 @@
 """s-varying track corridors: the two edges of the track as periodic tables over arc length, in place of the one
-width N_MAX.  `Corridor.from_table` takes a user's own tables (a caller with cones resamples them over s first), `Corridor.constant`
-a band of fixed half-width.  A Corridor goes to LtvBatch / ClosedLoop / monte_carlo (`corridor=`: the MPC's track rows and the lap
-report's track violation) and to Plan.raceline (the box of every control point, or with rows="cells" one constraint row per cell).
+width N_MAX.  `Corridor.from_table` takes a user's own tables, `Corridor.constant` a band of fixed half-width, `Corridor.from_cones`
+derives the tables from the cones that mark the track, on the device.  A Corridor goes to LtvBatch / ClosedLoop /
+monte_carlo (`corridor=`: the MPC's track rows and the lap report's track violation) and to Plan.raceline (the box of every control
+point, or with rows="cells" one constraint row per cell).
 The limits are for the car's reference point: the caller subtracts the half-width of the car."""
 import ctypes as C
 import math
 
 import numpy as np
 
-from ._lib import CorridorTable, check, lib
+from ._lib import CONE_INFO_INDEX, CONES_MAX, NCONEINFO, ConeMaps, CorridorTable, Spline, check, lib
+
+_check = check   # (from_cones has a parameter of that name)
 
 
 def _host(a, name):
@@ -47,6 +50,7 @@ class Corridor:
         self.P, self.N_w = int(n_lo.shape[0]), int(n_lo.shape[1])
         self.ds = self.L / self.N_w
         self.device = n_lo.device
+        self.info = None   # from_cones(check=True): the (P, 8) info block of the cone stage
         self.c = CorridorTable(C.c_void_p(n_lo.data_ptr()), C.c_void_p(n_hi.data_ptr()), self.N_w, self.ds, 1 if self.P > 1 else 0)
 
     def ref(self):
@@ -70,6 +74,67 @@ class Corridor:
         if int(N_w) != N_w or N_w < 2:
             raise ValueError("N_w must be an integer >= 2, got %r" % (N_w,))
         return Corridor.from_table(np.full(int(N_w), -float(half_width)), np.full(int(N_w), float(half_width)), L, device=device)
+
+    @staticmethod
+    def from_cones(track, left, right, N_w, margin=0.0, reach=5.0, device="cuda:0", stream=None, check=True):
+        """The corridor of a track from the two rows of cones that mark it, on the device (fsaempc_corridor_from_cones_device,
+        DESIGN.md 6n).  left, right: (K, 2) for one corridor or (P, K, 2) for P of them (a batch on one side, one map on the other:
+        the one map is repeated), numpy arrays or device tensors; a cone with a NaN coordinate is absent, which pads maps of
+        different sizes.  margin: taken off both edges (the car's half-width); reach: cones further from the line are strays.
+        Returns a Corridor whose .info is the (P, 8) host array of CONE_INFO_INDEX.  check=True reads the info once and raises
+        ValueError, naming the corridor and the reason, when a side kept no cone or a cell has no room (n_lo < n_hi fails);
+        check=False synchronises nothing and leaves .info None."""
+        import torch
+        dev = torch.device(device)
+        if int(N_w) != N_w or N_w < 2:
+            raise ValueError("N_w must be an integer >= 2, got %r" % (N_w,))
+        sides = []
+        for a, name in ((left, "left"), (right, "right")):
+            if not isinstance(a, torch.Tensor):
+                try:
+                    a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+                except (TypeError, ValueError):
+                    raise ValueError("%s must be an array of (K, 2) or (P, K, 2) numbers" % name)
+            if a.dim() not in (2, 3) or a.shape[-1] != 2 or (a.dim() == 3 and a.shape[0] < 1):
+                raise ValueError("%s must be (K, 2) or (P, K, 2), got %s" % (name, tuple(a.shape)))
+            if a.shape[-2] > CONES_MAX:
+                raise ValueError("%s holds %d cones per map, at most %d are supported" % (name, a.shape[-2], CONES_MAX))
+            sides.append(a.to(device=dev, dtype=torch.float64))
+        counts = {int(a.shape[0]) for a in sides if a.dim() == 3}
+        if len(counts) > 1:
+            raise ValueError("left and right hold different numbers of maps: %s and %s" % (tuple(sides[0].shape), tuple(sides[1].shape)))
+        P = counts.pop() if counts else 1
+        per = 1 if any(a.dim() == 3 for a in sides) else 0
+        if per:
+            sides = [a if a.dim() == 3 else a.unsqueeze(0).expand(P, -1, -1) for a in sides]
+        le, ri = (a.contiguous() for a in sides)
+        xP, yP = track.device(dev)
+        sp = Spline(track.M, track.dl, C.c_void_p(xP.data_ptr()), C.c_void_p(yP.data_ptr()))
+        maps = ConeMaps(C.c_void_p(le.data_ptr() if le.numel() else None), C.c_void_p(ri.data_ptr() if ri.numel() else None),
+                        int(le.shape[-2]), int(ri.shape[-2]), per)
+        n_lo = torch.empty((P, int(N_w)), dtype=torch.float64, device=dev)
+        n_hi = torch.empty_like(n_lo)
+        info = torch.empty((P, NCONEINFO), dtype=torch.float64, device=dev) if check else None
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+        _check(lib().fsaempc_corridor_from_cones_device(C.byref(sp), C.c_double(track.L), C.byref(maps), P, int(N_w), C.c_double(margin),
+                                                        C.c_double(reach), C.c_void_p(n_lo.data_ptr()), C.c_void_p(n_hi.data_ptr()),
+                                                        C.c_void_p(info.data_ptr() if check else None), st),
+               "fsaempc_corridor_from_cones_device")
+        cor = Corridor(n_lo, n_hi, track.L)
+        cor._cones = (le, ri)   # (the launch is asynchronous: the maps live as long as the tables)
+        if check:
+            if stream is not None:
+                torch.cuda.synchronize(dev)        # (a raw stream handle: the copy below orders itself on torch's current stream only)
+            cor.info = info.cpu().numpy()
+            for p, row in enumerate(cor.info):
+                for slot, side in ((CONE_INFO_INDEX["KEPT_LEFT"], "left"), (CONE_INFO_INDEX["KEPT_RIGHT"], "right")):
+                    if row[slot] == 0:
+                        raise ValueError("corridor %d: no %s cone was kept (absent %d, unprojected %d, beyond reach %d over both sides)"
+                                         % (p, side, row[2], row[3], row[4]))
+                if row[CONE_INFO_INDEX["CELLS_NO_ROOM"]] != 0:
+                    raise ValueError("corridor %d: n_lo < n_hi fails in %d cells (least width %r with margin %r)"
+                                     % (p, row[6], float(row[7]), float(margin)))
+        return cor
 
     def line_bounds(self, N_s, N_c, margin, n_plans=None, stream=None):
         """(lb, ub), each (n_plans, N_c) on the device: the bounds Plan.raceline(corridor=self) hands to the line QP

@@ -22,6 +22,7 @@
 #include "planner.h"
 #include "raceline.h"
 #include "corridor.h"
+#include "cones.h"
 #include "sqp.h"
 #include "qp_sens.h"
 
@@ -1397,6 +1398,38 @@ int fsaempc_corridor_line_rows_device(const fsaempc_corridor* cor, double L, int
   R.n_plans = n_plans; R.N_s = N_s; R.N_c = N_c; R.L = L; R.margin = margin; R.A = A; R.lbA = lbA; R.ubA = ubA; R.g = nullptr; R.lb = nullptr; R.ub = nullptr;
   hipError_t e = cor_line_rows_launch(R, (hipStream_t)stream);
   if (e != hipSuccess) return hipfail(e, "cor_line_rows_launch");
+  return 0;
+}
+
+/* ---- track corridors from cone positions ---- */
+int fsaempc_corridor_from_cones_device(const fsaempc_spline* sp, double L, const fsaempc_cones* cones, int n_corridors,
+                                       int N_w, double margin, double reach, double* n_lo, double* n_hi, double* info, void* stream) {
+  if (!sp) return fail(FSAEMPC_ERR_ARG, "cones: sp is NULL");
+  if (!sp->xP || !sp->yP) return fail(FSAEMPC_ERR_ARG, "cones: the spline tables are NULL");
+  if (!cones) return fail(FSAEMPC_ERR_ARG, "cones: cones is NULL");
+  if (!n_lo) return fail(FSAEMPC_ERR_ARG, "cones: n_lo is NULL");
+  if (!n_hi) return fail(FSAEMPC_ERR_ARG, "cones: n_hi is NULL");
+  if (n_corridors < 1) return fail(FSAEMPC_ERR_ARG, "cones: n_corridors must be >= 1");
+  if (N_w < 2) return fail(FSAEMPC_ERR_ARG, "cones: N_w must be >= 2");
+  if (!pos_finite(L)) return fail(FSAEMPC_ERR_ARG, "cones: L must be finite and > 0");
+  if (!(margin >= 0 && margin < INFINITY)) return fail(FSAEMPC_ERR_ARG, "cones: margin must be finite and >= 0");
+  if (!pos_finite(reach)) return fail(FSAEMPC_ERR_ARG, "cones: reach must be finite and > 0");
+  if (cones->n_left < 0) return fail(FSAEMPC_ERR_ARG, "cones: n_left must be >= 0");
+  if (cones->n_right < 0) return fail(FSAEMPC_ERR_ARG, "cones: n_right must be >= 0");
+  if (!cones->left && cones->n_left > 0) return fail(FSAEMPC_ERR_ARG, "cones: left is NULL with n_left > 0");
+  if (!cones->right && cones->n_right > 0) return fail(FSAEMPC_ERR_ARG, "cones: right is NULL with n_right > 0");
+  if (sp->M < 1 || !pos_finite(sp->dl)) return fail(FSAEMPC_ERR_ARG, "cones: the spline needs M >= 1 and dl finite and > 0");
+  if (cones->n_left > FSAEMPC_CONES_MAX) return fail(FSAEMPC_ERR_DIM, "cones: n_left exceeds FSAEMPC_CONES_MAX");
+  if (cones->n_right > FSAEMPC_CONES_MAX) return fail(FSAEMPC_ERR_DIM, "cones: n_right exceeds FSAEMPC_CONES_MAX");
+  if (sp->M > FSAEMPC_CONES_MAX_M) return fail(FSAEMPC_ERR_DIM, "cones: M exceeds FSAEMPC_CONES_MAX_M");
+  ConesParams P;
+  set_spline(&P, sp);
+  P.L = L; P.left = cones->left; P.right = cones->right; P.n_left = cones->n_left; P.n_right = cones->n_right;
+  P.per_corridor = cones->per_corridor ? 1 : 0; P.n_corridors = n_corridors; P.N_w = N_w; P.margin = margin; P.reach = reach;
+  P.n_lo = n_lo; P.n_hi = n_hi; P.info = info;
+  Range r("fsaempc.corridor.cones");
+  hipError_t e = cor_from_cones_launch(P, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "cor_from_cones_launch");
   return 0;
 }
 

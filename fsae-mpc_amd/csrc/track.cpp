@@ -3,7 +3,8 @@
 // lookup reads (main.m:11-17).  Plain host code (no device work), part of libfsaempc.so; C ABI in include/fsaempc.h.
 //
 // Restates
-//   util/read_raceline_csv.m:6-19      readmatrix of the CSV (one header line), columns 1, 2 = X, Y of the race line
+//   util/read_raceline_csv.m:6-19      readmatrix of the CSV (one header line), columns 1, 2 = X, Y of the race line; columns
+//                                      8-11 = rX, rY, lX, lY, the cones (fsaempc_track_cones_from_csv)
 //   spline/make_spline_periodic.m:9-33 P0 = P, P3 = P shifted; cyclic [1 4 1] system for P1 (b_i = 4 P_i + 2 P_{i+1});
 //                                      P2_i = 2 P_{i+1} - P1_{i+1}
 //   spline/arclength_reparam.m:15-64   segment "lengths" by quadrature of the speed integrand -- which uses the control point
@@ -13,6 +14,7 @@
 // MATLAB's adaptive `integral` (Gauss-Kronrod 7-15, AbsTol 1e-10, RelTol 1e-6) is restated as an adaptive Gauss-Kronrod 7-15
 // with the same tolerances; the integrand is the square root of a quartic, one or two panels resolve it to round-off, and the
 // 0.01 bisection tolerance makes the station sequence insensitive to quadrature differences of that size.
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -155,6 +157,40 @@ void arclength_reparam(const std::vector<double>& xC, const std::vector<double>&
 thread_local char t_err[256] = "";
 int tfail(int code, const char* msg, const char* a = "") { snprintf(t_err, sizeof(t_err), msg, a); return code; }
 
+// The reader of the race-line CSV (util/read_raceline_csv.m:6: readmatrix): every line that starts with a number is a row and goes
+// to row(first column, the text after it), which returns 0 or an error code that ends the read; the header line and blank lines are
+// skipped.
+template <class F> int csv_rows(const char* path, F row) {
+  FILE* f = fopen(path, "r");
+  if (!f) return tfail(FSAEMPC_ERR_ARG, "track: cannot open %s", path);
+  char line[4096];
+  while (fgets(line, sizeof(line), f)) {
+    char* end = nullptr;
+    const double a = strtod(line, &end);
+    if (end == line) continue;   // header line (readmatrix skips it) / blank lines
+    if (const int rc = row(a, end)) { fclose(f); return rc; }
+  }
+  fclose(f);
+  return 0;
+}
+
+// Columns 2 .. ncol of a row, p at the text after column 1: col[k] for column k + 1, NaN for an empty or non-numeric field (as
+// readmatrix fills them).  One separator (',', ';' or a tab) between columns; false if the row has fewer than ncol columns.
+bool csv_fields(char* p, int ncol, double* col) {
+  auto sep = [](char c) { return c == ',' || c == ';' || c == '\t'; };
+  for (int k = 1; k < ncol; ++k) {
+    while (*p == ' ') ++p;
+    if (!sep(*p)) return false;
+    ++p;
+    while (*p == ' ') ++p;
+    char* e = p;
+    const double v = (sep(*p) || *p == '\0' || *p == '\n' || *p == '\r') ? NAN : strtod(p, &e);
+    if (e == p) { col[k] = NAN; while (*p && !sep(*p) && *p != '\n' && *p != '\r') ++p; }
+    else { col[k] = v; p = e; }
+  }
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -178,26 +214,43 @@ int fsaempc_track_from_points(const double* x, const double* y, int n, int M, fs
 
 int fsaempc_track_from_csv(const char* path, int M, fsaempc_track* out) {
   if (!path || !out) return tfail(FSAEMPC_ERR_ARG, "track: null argument");
-  FILE* f = fopen(path, "r");
-  if (!f) return tfail(FSAEMPC_ERR_ARG, "track: cannot open %s", path);
   std::vector<double> x, y;
-  char line[4096];
-  bool first = true;
-  while (fgets(line, sizeof(line), f)) {
-    char* end = nullptr;
-    const double a = strtod(line, &end);
-    if (end == line) { if (first) { first = false; continue; } else continue; }   // header line (readmatrix skips it) / blank lines
-    first = false;
+  const int rc = csv_rows(path, [&](double a, char* end) {
     while (*end == ',' || *end == ' ' || *end == '\t' || *end == ';') ++end;
     char* end2 = nullptr;
     const double b_ = strtod(end, &end2);
-    if (end2 == end) { fclose(f); return tfail(FSAEMPC_ERR_ARG, "track: a row of %s has fewer than two numeric columns", path); }
+    if (end2 == end) return tfail(FSAEMPC_ERR_ARG, "track: a row of %s has fewer than two numeric columns", path);
     x.push_back(a); y.push_back(b_);
-  }
-  fclose(f);
+    return 0;
+  });
+  if (rc) return rc;
   if (x.size() < 3) return tfail(FSAEMPC_ERR_ARG, "track: %s holds fewer than three points", path);
   return fsaempc_track_from_points(x.data(), y.data(), (int)x.size(), M, out);
 }
+
+int fsaempc_track_cones_from_csv(const char* path, double** left, int* n_left, double** right, int* n_right) {
+  if (!path || !left || !n_left || !right || !n_right) return tfail(FSAEMPC_ERR_ARG, "track: null argument");
+  *left = *right = nullptr; *n_left = *n_right = 0;
+  std::vector<double> l, r;
+  const int rc = csv_rows(path, [&](double, char* end) {
+    double col[11];
+    if (!csv_fields(end, 11, col)) return tfail(FSAEMPC_ERR_ARG, "track: a row of %s has fewer than 11 columns (the cones are columns 8-11)", path);
+    if (isfinite(col[7]) && isfinite(col[8])) { r.push_back(col[7]); r.push_back(col[8]); }      // read_raceline_csv.m:16-17
+    if (isfinite(col[9]) && isfinite(col[10])) { l.push_back(col[9]); l.push_back(col[10]); }    // read_raceline_csv.m:18-19
+    return 0;
+  });
+  if (rc) return rc;
+  if (l.size() / 2 > (size_t)INT_MAX || r.size() / 2 > (size_t)INT_MAX) return tfail(FSAEMPC_ERR_ARG, "track: %s holds too many rows", path);
+  double* pl = l.empty() ? nullptr : (double*)malloc(sizeof(double) * l.size());
+  double* pr = r.empty() ? nullptr : (double*)malloc(sizeof(double) * r.size());
+  if ((!l.empty() && !pl) || (!r.empty() && !pr)) { free(pl); free(pr); return tfail(FSAEMPC_ERR_ARG, "track: out of memory"); }
+  if (pl) memcpy(pl, l.data(), sizeof(double) * l.size());
+  if (pr) memcpy(pr, r.data(), sizeof(double) * r.size());
+  *left = pl; *n_left = (int)(l.size() / 2); *right = pr; *n_right = (int)(r.size() / 2);
+  return 0;
+}
+
+void fsaempc_track_cones_free(double* cones) { free(cones); }
 
 void fsaempc_track_free(fsaempc_track* t) { if (t) { free(t->xP); free(t->yP); t->xP = t->yP = nullptr; t->M = 0; } }
 

@@ -84,3 +84,30 @@ def param_draws(model, ids, seed, spread):
     for j in _PAR_LOG:
         out[:, j] *= 10.0 ** (2.0 * _u01(st) - 1.0)
     return out
+
+
+_CONE_SALT = np.uint64(0x8CB92BA72F3D8DD7)
+
+
+def cone_draws(left, right, sigma, P, seed):
+    """P noisy copies of a cone map for a Monte-Carlo over perception noise (Corridor.from_cones takes them as they are): left (K_l, 2)
+    and right (K_r, 2) -> (P, K_l, 2), (P, K_r, 2) with independent Gaussian noise of standard deviation sigma on every coordinate.  A
+    pure function of (the maps, sigma, P, seed): splitmix64 keyed by the copy, as for instances(), with a salt of its own, and
+    Box-Muller on pairs of its uniforms.  sigma = 0 gives P copies."""
+    left, right = np.asarray(left, dtype=np.float64).reshape(-1, 2), np.asarray(right, dtype=np.float64).reshape(-1, 2)
+    if int(P) != P or P < 1:
+        raise ValueError("P must be an integer >= 1, got %r" % (P,))
+    if not (np.isfinite(sigma) and sigma >= 0):
+        raise ValueError("sigma must be finite and >= 0, got %r" % (sigma,))
+    P = int(P)
+    with np.errstate(over="ignore"):
+        st = (np.uint64(seed) ^ (np.arange(P, dtype=np.uint64) * _GOLD)) ^ _CONE_SALT
+    out = []
+    for m in (left, right):
+        z = np.zeros((P,) + m.shape)
+        for k in range(m.shape[0]):
+            u1, u2 = _u01(st), _u01(st)
+            r = np.sqrt(-2.0 * np.log(1.0 - u1))           # (u1 in [0, 1): the logarithm's argument is in (0, 1])
+            z[:, k, 0], z[:, k, 1] = r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)
+        out.append(m[None, :, :] + sigma * z if sigma > 0 else np.repeat(m[None, :, :], P, axis=0))
+    return out[0], out[1]

@@ -49,6 +49,22 @@ class Track:
         return Track._from_table(t, name or os.path.splitext(os.path.basename(path))[0])
 
     @staticmethod
+    def cones_from_csv(path):
+        """(left, right), each (K, 2): the cone columns of a race-line CSV (read_raceline_csv.m:16-19: columns 8, 9 right and 10, 11
+        left) through the library's reader; a row whose pair is empty or non-finite is skipped for that side only."""
+        from ._lib import FsaempcError, lib
+        pl, pr = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+        nl, nr = C.c_int(0), C.c_int(0)
+        rc = lib().fsaempc_track_cones_from_csv(os.fsencode(path), C.byref(pl), C.byref(nl), C.byref(pr), C.byref(nr))
+        if rc != 0:
+            raise FsaempcError("fsaempc_track_cones_from_csv failed (%d): %s" % (rc, lib().fsaempc_track_last_error().decode()))
+        out = []
+        for p, n in ((pl, nl.value), (pr, nr.value)):
+            out.append(np.ctypeslib.as_array(p, (2 * n,)).reshape(n, 2).copy() if n > 0 else np.zeros((0, 2)))
+            lib().fsaempc_track_cones_free(p)
+        return out[0], out[1]
+
+    @staticmethod
     def from_points(x, y, M=100, name="track"):
         from ._lib import FsaempcError, TrackTable, lib
         x = np.ascontiguousarray(x, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)

@@ -716,8 +716,8 @@ int fsaempc_qp_layout(const fsaempc_qp_desc* desc, int n_slack, int out[4]);
  * length, linear between the cells.  Lookup at any finite s, negative values and values past L included: q = s / ds wrapped into
  * [0, N_w), i = floor(q), u = q - i, value = t[i] + u (t[(i + 1) mod N_w] - t[i]); a constant table returns the constant exactly.
  * A non-finite s, or one of the two cells read where n_lo < n_hi does not hold, gives NaN for both limits of that lookup only.
- * The limits are for the car's reference point: the caller subtracts the half-width of the car.  No geometry is derived here: a
- * caller with cones resamples them over s on the host.  The _c entries take `cor` after `blk`; cor == NULL hands over to the entry
+ * The limits are for the car's reference point: the caller subtracts the half-width of the car.  The tables are the caller's own, or come
+ * from cone positions on the device (fsaempc_corridor_from_cones_device below).  The _c entries take `cor` after `blk`; cor == NULL hands over to the entry
  * without a corridor and returns its bits.  Before any launch FSAEMPC_ERR_ARG, with the argument named in fsaempc_last_error: a NULL
  * n_lo or n_hi, N_w < 2, ds not finite or <= 0. */
 typedef struct {
@@ -819,6 +819,43 @@ int fsaempc_plan_raceline_cells_batch_device(int model, const fsaempc_spline* sp
 int fsaempc_corridor_line_rows_device(const fsaempc_corridor* cor, double L, int n_plans, int N_s, int N_c, double margin,
                                       double* A, double* lbA, double* ubA, void* stream);
 
+/* ---- track corridors from cone positions ---------------------------------------------
+ * The tables of an fsaempc_corridor from the two rows of cones that mark the track, on the device and batched: n_corridors cone
+ * maps (P noisy maps of one track, say) give n_corridors corridors, in exactly the layout fsaempc_corridor reads with
+ * per_instance = 1 (or 0 for one).  One 256-thread workgroup per corridor.  Per side (left, right):
+ *   1. Projection of every cone.  A cone with a non-finite coordinate is absent (maps of different sizes are padded with NaN).  The
+ *      coarse start is the nearest of the 4M samples s = (j + 0.5) dl / 4, the first minimum in ascending j; then the Newton
+ *      iteration of spline/closest_point.m (first over second derivative of the squared distance), until a step with
+ *      |delta| <= 1e-10 has been applied, at most 30 iterations.  A cone is unprojected and dropped if the second derivative is
+ *      <= 0, anything becomes non-finite, a step exceeds dl, or the limit is hit.  n is the offset along the unit left normal at the
+ *      foot point; a cone with |n| > reach is dropped as a stray.  s is wrapped into [0, L).
+ *   2. Order.  The kept cones are sorted by (s, input index); the edge is the closed polyline through them in that order.
+ *   3. Cells.  Cell i is at s_i = i (L / N_w); p_i, T_i, N_i are the spline point, unit tangent and unit left normal there.  j is
+ *      the last kept cone with s_j <= s_i (the last cone overall, shifted by -L, when there is none), j + 1 its cyclic successor,
+ *      d = c_{j+1} - c_j.  t = ((p_i - c_j) . T_i) / (d . T_i); if d . T_i > 0 does not hold, t = (s_i - s_j) / (s_{j+1} - s_j)
+ *      with the arc lengths unwrapped.  A t outside [-1e-9, 1 + 1e-9] counts the cell as off its segment; t is clamped to [0, 1]
+ *      and edge_i = (c_j + t d - p_i) . N_i.  With one kept cone the edge is that cone's n in every cell, with none NaN.
+ *   4. Tables.  n_hi[i] = edge_left,i - margin, n_lo[i] = edge_right,i + margin (margin: the car's half-width, say).
+ * The nearest-point rule is the contract: a cone nearer to a foreign stretch of track than to its own is attributed to that stretch.
+ * info (may be NULL): FSAEMPC_NCONEINFO doubles per corridor, counts summed over both sides --
+ *   0 left cones kept, 1 right cones kept, 2 absent, 3 unprojected, 4 beyond reach, 5 cells off their segment,
+ *   6 cells where n_lo < n_hi does not hold (a NaN cell counts), 7 least n_hi - n_lo over the cells (NaN if any cell is NaN).
+ * One corridor's result does not depend on the others of the batch, bit for bit.  Asynchronous on `stream`; no workspace.
+ * FSAEMPC_ERR_ARG before any launch, with the argument named in fsaempc_last_error: a NULL pointer (a side's pointer may be NULL
+ * only with count 0; info may be NULL), n_corridors < 1, N_w < 2, L, margin or reach not finite, L <= 0, margin < 0, reach <= 0, a
+ * negative count.  FSAEMPC_ERR_DIM: a count above FSAEMPC_CONES_MAX or sp->M above FSAEMPC_CONES_MAX_M. */
+#define FSAEMPC_NCONEINFO 8
+#define FSAEMPC_CONES_MAX 512     /* cones per side and map */
+#define FSAEMPC_CONES_MAX_M 512   /* spline segments */
+typedef struct {
+  const double* left;    /* device; n_left x 2 doubles per map, xy interleaved */
+  const double* right;   /* device; n_right x 2 doubles per map */
+  int n_left, n_right;
+  int per_corridor;      /* 0: one map for all corridors; 1: one per corridor, corridor-major */
+} fsaempc_cones;
+int fsaempc_corridor_from_cones_device(const fsaempc_spline* sp, double L, const fsaempc_cones* cones, int n_corridors,
+                                       int N_w, double margin, double reach, double* n_lo, double* n_hi, double* info, void* stream);
+
 /* ---- multi-lap closed loop: the lap gate ---------------------------------------------
  * The loop above ends a car's run the first time the pre-step sees s >= L (main.m:102-104).  The gate carries a car over the line
  * instead, up to `laps` laps: it times the crossing inside the period, hands the lap's record over and takes L off every arc
@@ -881,6 +918,12 @@ void fsaempc_track_free(fsaempc_track* t);
 /* On-disk table format "FSTRK001" (little endian): 8-byte magic, int32 M, int32 0, double dl, double L, xP (4M doubles), yP (4M). */
 int fsaempc_track_save(const fsaempc_track* t, const char* path);
 int fsaempc_track_load(const char* path, fsaempc_track* out);
+/* The cone columns of the same CSV (util/read_raceline_csv.m:16-19: columns 8, 9 = rX, rY, the right cones; 10, 11 = lX, lY, the
+ * left cones), read by the reader of fsaempc_track_from_csv: *left / *right are n x 2 doubles, xy interleaved, host memory owned by
+ * the library (fsaempc_track_cones_free; NULL with a count of 0).  A row whose pair is empty or non-finite is skipped for that side
+ * only.  FSAEMPC_ERR_ARG: a NULL argument, a file that cannot be opened, a row with fewer than 11 columns. */
+int fsaempc_track_cones_from_csv(const char* path, double** left, int* n_left, double** right, int* n_right);
+void fsaempc_track_cones_free(double* cones);
 const char* fsaempc_track_last_error(void);
 
 /* ---- diagnostics ---------------------------------------------------------------------------- */

@@ -10,6 +10,10 @@ driving, the exit-flag tally the way main.m:209,222 reports it ("abnormal exits 
 track; the controller's track rows, the report's track violation and, with --raceline, the line's bounds are taken against it.
 --line-rows points|cells: with --raceline and --corridor, the form of the line's corridor constraints: the box of every control point (the
 default) or one constraint row per cell (Plan.raceline(rows="cells")).
+--cones FILE [--car-half-width W]: the corridor comes from the cones that mark the track (Corridor.from_cones), W (default
+0.7 m) taken off both edges.  FILE is a race-line CSV in the reference's format (cone columns 8-11) or an .npz with arrays left, right of
+(K, 2) -- optionally a string `track`, which must then name --track -- or with TRACK_left, TRACK_right per track as tests/golden/tracks/cones.npz
+has them.  Exclusive with --corridor; everything a corridor composes with composes with it.
 --lap: every car starts at s = 0 on the centre line, at rest, with the usual lateral and heading scatter (main.m:63), and the step cap
 defaults to 1000 (main.m:62): a finished car's STEPS * dt is then a lap time.
 --laps K: every car drives K consecutive laps (ClosedLoop(laps=K), DESIGN.md 6m: the lap gate carries it over the line and times the
@@ -17,7 +21,7 @@ crossing to a fraction of dt); with --lap the step cap defaults to 1000 K; the p
 max of its time) joins the JSON line as "lap_summary".
 usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--track fss2019]
                                   [--plan | --raceline [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap] [--laps K]
-                                  [--corridor FILE.npz [--line-rows points|cells]]"""
+                                  [--corridor FILE.npz | --cones FILE [--car-half-width W]] [--line-rows points|cells]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -47,11 +51,16 @@ def main():
     ap.add_argument("--margin", type=float, default=0.25, help="with --raceline: distance the line keeps from N_MAX, m")
     ap.add_argument("--points", type=int, default=100, help="with --raceline: control points of the line (N_c)")
     ap.add_argument("--corridor", default=None, metavar="FILE.npz", help="track corridor: arrays n_lo, n_hi of (N_w,) over the lap (Corridor.from_table)")
+    ap.add_argument("--cones", default=None, metavar="FILE", help="track corridor from cone positions: a race-line CSV or an .npz (Corridor.from_cones)")
+    ap.add_argument("--car-half-width", type=float, default=0.7, help="with --cones: taken off both edges of the corridor, m")
+    ap.add_argument("--cone-cells", type=int, default=500, help="with --cones: cells of the corridor's tables (N_w)")
     ap.add_argument("--line-rows", default="points", choices=["points", "cells"],
-                    help="with --raceline --corridor: the line's corridor as boxes on the control points or as one row per cell")
+                    help="with --raceline and --corridor or --cones: the line's corridor as boxes on the control points or as one row per cell")
     a = ap.parse_args()
-    if a.line_rows == "cells" and not (a.raceline and a.corridor is not None):
-        ap.error("--line-rows cells needs --raceline and --corridor")
+    if a.corridor is not None and a.cones is not None:
+        ap.error("--cones and --corridor exclude each other")
+    if a.line_rows == "cells" and not (a.raceline and (a.corridor is not None or a.cones is not None)):
+        ap.error("--line-rows cells needs --raceline and --corridor or --cones")
     if a.steps is None:
         a.steps = 1000 * a.laps if a.lap else 200
     model = fm.KINEMATIC if a.model == "kinematic" else fm.DYNAMIC
@@ -60,6 +69,24 @@ def main():
     if a.corridor is not None:
         with np.load(a.corridor) as z:
             cor = fm.Corridor.from_table(z["n_lo"], z["n_hi"], tr.L)
+    cone_info = None
+    if a.cones is not None:
+        if a.cones.endswith(".npz"):
+            with np.load(a.cones) as z:
+                if "left" in z.files:
+                    if "track" in z.files and str(z["track"]) != a.track:
+                        ap.error("%s holds the cones of %s, not of %s" % (a.cones, str(z["track"]), a.track))
+                    left, right = z["left"], z["right"]
+                elif a.track + "_left" in z.files:
+                    left, right = z[a.track + "_left"], z[a.track + "_right"]
+                else:
+                    ap.error("%s holds neither left / right nor %s_left / %s_right" % (a.cones, a.track, a.track))
+        else:
+            left, right = fm.Track.cones_from_csv(a.cones)
+        cor = fm.Corridor.from_cones(tr, left, right, a.cone_cells, margin=a.car_half_width)
+        cone_info = {k: float(cor.info[0, i]) for k, i in fm.CONE_INFO_INDEX.items()}
+        cone_info.update(file=a.cones, car_half_width=a.car_half_width, cells=a.cone_cells, n_hi_min=float(cor.n_hi.min().item()), n_hi_max=float(cor.n_hi.max().item()),
+                         n_lo_min=float(cor.n_lo.min().item()), n_lo_max=float(cor.n_lo.max().item()))
     plan = fm.Plan.profile(model, tr, N_s=a.cells, grip=a.grip) if a.plan else None
     if a.raceline:
         plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip, corridor=cor, rows=a.line_rows)
@@ -113,7 +140,7 @@ def main():
         "config": {"workload": "BASELINE configs[3] share of one GPU: %d cars on %s, %d receding-horizon steps, every step one batch of QPs "
                                "(frame transform + reference + linearise/condense/solve + PID/plant, device-resident loop, no per-step read-back; "
                                "wall time includes the allocation of the run)" % (a.batch, a.track, a.steps),
-                   "track": a.track, "corridor": a.corridor, "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
+                   "track": a.track, "corridor": a.corridor, **({"cones": cone_info} if cone_info is not None else {}), "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
                    # (a mean over an empty set is NaN in the report: null in the JSON line)
                    **({"lap_report": {k: (None if v != v else v) for k, v in cl.report().summary().items()}, "slack_tol": a.slack_tol} if a.report else {}),
                    **({"laps": a.laps, "lap_summary": [{"lap": i + 1, "cars": int(r[0]), "mean_s": None if r[1] != r[1] else float(r[1]),

@@ -8,8 +8,12 @@
   --line-rows            one JSON line: Plan.raceline (N_s 500, N_c 100, fsg2019, the corridor of --make) with rows="cells" against rows="points",
                          for 1 and 256 plans (a corridor each), and the rows call alone (Corridor.line_rows), measured the same way.
   --line-rows-once P     P plans through one Plan.raceline(rows="cells") call after one warm-up, for a kernel trace.
+  --from-cones P         one JSON line: the corridors of P noisy cone maps (fsg2019, 77 cones per side, sigma 0.05 m, N_w =
+                         --cells, margin 0.7) through the C entry alone -- the maps and the outputs are on the device before the
+                         events --, measured the same way; the numpy restatement's time per map next to it (--restate: tests/ is on
+                         the path).  With --once: one call after one warm-up, for a kernel trace.
 usage: tools/corridor_bench.py [--make TRACK OUT.npz [--wide W] [--narrow W] [--kappa K] [--cells N_w]] [--batch 4096] [--horizon 40]
-                               [--line-rows | --line-rows-once P]"""
+                               [--line-rows | --line-rows-once P | --from-cones P [--once] [--restate] [--cones FILE.npz]]"""
 import argparse, json, os, sys
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -50,6 +54,10 @@ def main():
     ap.add_argument("--horizon", type=int, default=40)
     ap.add_argument("--line-rows", action="store_true")
     ap.add_argument("--line-rows-once", type=int, default=0, metavar="P")
+    ap.add_argument("--from-cones", type=int, default=0, metavar="P")
+    ap.add_argument("--once", action="store_true")
+    ap.add_argument("--restate", action="store_true")
+    ap.add_argument("--cones", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "tracks", "cones.npz"))
     a = ap.parse_args()
     import fsae_mpc_amd as fm
     if a.make is not None:
@@ -61,6 +69,45 @@ def main():
         return
     import torch
     tr = fm.Track.load("fsg2019")
+    if a.from_cones:
+        import ctypes as C
+        import time
+        P, N_w = a.from_cones, a.cells
+        with np.load(a.cones) as z:
+            left, right = z["fsg2019_left"], z["fsg2019_right"]
+        dl, dr = (torch.from_numpy(v).cuda() for v in fm.cone_draws(left, right, 0.05, P, 20190))
+        xP, yP = tr.device("cuda:0")
+        sp = fm._lib.Spline(tr.M, tr.dl, C.c_void_p(xP.data_ptr()), C.c_void_p(yP.data_ptr()))
+        maps = fm._lib.ConeMaps(C.c_void_p(dl.data_ptr()), C.c_void_p(dr.data_ptr()), left.shape[0], right.shape[0], 1)
+        lo, hi = torch.empty((P, N_w), dtype=torch.float64, device="cuda"), torch.empty((P, N_w), dtype=torch.float64, device="cuda")
+        info = torch.empty((P, 8), dtype=torch.float64, device="cuda")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def call():
+            rc = fm.lib().fsaempc_corridor_from_cones_device(C.byref(sp), C.c_double(tr.L), C.byref(maps), P, N_w, C.c_double(0.7), C.c_double(5.0),
+                                                             C.c_void_p(lo.data_ptr()), C.c_void_p(hi.data_ptr()), C.c_void_p(info.data_ptr()), st)
+            assert rc == 0, fm.lib().fsaempc_last_error()
+        out = {"what": "fsaempc_corridor_from_cones_device alone: fsg2019, %d + %d cones per map, sigma 0.05 m, N_w %d, margin 0.7, %d maps in one call"
+                       % (left.shape[0], right.shape[0], N_w, P)}
+        if a.once:
+            call(); torch.cuda.synchronize(); call(); torch.cuda.synchronize()
+        else:
+            out["call_ms_median_min_max"] = median_ms(torch, call)
+        h = info.cpu().numpy()
+        out.update(kept_min=[float(h[:, 0].min()), float(h[:, 1].min())], dropped=float(h[:, 2:5].sum()), cells_off_segment=float(h[:, 5].sum()),
+                   cells_no_room=float(h[:, 6].sum()), width_min=float(h[:, 7].min()), width_min_mean=float(h[:, 7].mean()))
+        if a.restate:
+            sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+            import cones_numpy as cq
+            hl, hr = dl.cpu().numpy(), dr.cpu().numpy()
+            t0 = time.perf_counter()
+            n = min(P, 4)
+            for p in range(n):
+                wlo, whi, _ = cq.corridor_from_cones(tr, tr.L, hl[p], hr[p], N_w, 0.7, 5.0)
+            out["numpy_restatement_ms_per_map"] = (time.perf_counter() - t0) / n * 1e3
+            out["max_abs_diff_to_restatement_last_map"] = float(max(np.abs(lo[n - 1].cpu().numpy() - wlo).max(), np.abs(hi[n - 1].cpu().numpy() - whi).max()))
+        print(json.dumps(out))
+        return
     if a.line_rows or a.line_rows_once:
         s = np.arange(a.cells) * tr.L / a.cells
         w = np.where(np.abs(kappa_host(tr, s)) < a.kappa, a.wide, a.narrow)
