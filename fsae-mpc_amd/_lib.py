@@ -33,6 +33,7 @@ EXPORTS = [
     "fsaempc_cl_lap_gate_batch_device", "fsaempc_cl_lap_summary",
     "fsaempc_plan_raceline_cells_workspace_bytes", "fsaempc_plan_raceline_cells_batch_device", "fsaempc_corridor_line_rows_device",
     "fsaempc_corridor_from_cones_device", "fsaempc_track_cones_from_csv", "fsaempc_track_cones_free",
+    "fsaempc_plan_line_lapgrad_batch_device", "fsaempc_plan_minlap_workspace_bytes", "fsaempc_plan_minlap_batch_device",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -111,6 +112,9 @@ PLAN_MAX_NS = 4096   # FSAEMPC_PLAN_MAX_NS
 LINE_MAX_NS = 2048   # FSAEMPC_LINE_MAX_NS
 LINE_MIN_NC = 8      # FSAEMPC_LINE_MIN_NC
 MAX_NV = 196         # FSAEMPC_MAX_NV
+MINLAP_MAX_NS = 1024   # FSAEMPC_MINLAP_MAX_NS
+MINLAP_MAX_RHO = 16    # FSAEMPC_MINLAP_MAX_RHO
+MINLAP_RHO = (1e4, 3e3, 1e3, 300.0, 100.0, 30.0, 10.0, 3.0)   # the default ladder of Plan.minlap
 
 
 class PlanTable(C.Structure):   # fsaempc_plan
@@ -282,6 +286,13 @@ def lib():
                                                          vp, vp, vp, vp]
         L.fsaempc_track_cones_from_csv.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int),
                                                    C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int)]
+        L.fsaempc_plan_line_lapgrad_batch_device.argtypes = [C.c_int, C.POINTER(Spline), C.c_double, C.POINTER(LtvParams), C.c_int, C.c_int, C.c_int,
+                                                             vp, C.c_int, C.c_double, C.c_double, vp, vp, vp]
+        L.fsaempc_plan_minlap_workspace_bytes.restype = C.c_longlong
+        L.fsaempc_plan_minlap_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.fsaempc_plan_minlap_batch_device.argtypes = [C.c_int, C.POINTER(Spline), C.c_double, C.POINTER(LtvParams), C.c_int, C.c_int, C.c_int,
+                                                       C.c_double, C.c_double, C.c_double, C.POINTER(QpOpts), C.c_int, C.POINTER(C.c_double), C.c_int,
+                                                       vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ll, vp]
         L.fsaempc_track_cones_free.argtypes = [C.POINTER(C.c_double)]
         L.fsaempc_track_cones_free.restype = None
         L.fsaempc_cl_lap_gate_batch_device.argtypes =[C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 9

@@ -21,6 +21,7 @@
 #include "plant.h"
 #include "planner.h"
 #include "raceline.h"
+#include "minlap.h"
 #include "corridor.h"
 #include "cones.h"
 #include "sqp.h"
@@ -1231,10 +1232,14 @@ long long fsaempc_plan_raceline_workspace_bytes(int n_plans, int N_c) {
   return (long long)c.total;
 }
 
+// start (optional, fsaempc_plan_minlap_batch_device): the caller's boxes lo, hi (n_plans x N_c each) in place of +-(N_MAX_p - margin) --
+// a plan whose QP is then not solved is NaN, as in a corridor -- and/or the caller's control points c_init in place of the solve.
+struct LineStart { const double* lo; const double* hi; const double* c_init; };
 static int plan_raceline(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, const fsaempc_corridor* cor, int n_plans,
                          int N_s, int N_c, double margin, double v_cap, double grip, const fsaempc_qp_opts* opts, double* line, int* flag,
-                         double* table, double* t, void* workspace, long long workspace_bytes, void* stream) {
-  CorLineParams CL;
+                         double* table, double* t, void* workspace, long long workspace_bytes, void* stream, const LineStart* start = nullptr) {
+  CorLineParams CL; memset(&CL, 0, sizeof(CL));
+  const bool boxed = start && start->lo, given = start && start->c_init;
   if (cor) { if (int rc = cor_check(cor, &CL.cor)) return rc; }
   if (!line || !flag || !table || !t || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (int rc = line_check(sp, L, N_s, N_c)) return rc;
@@ -1247,24 +1252,35 @@ static int plan_raceline(int model, const fsaempc_spline* sp, double L, const fs
   double *H = (double*)(ws + c.H), *g = (double*)(ws + c.g), *lb = (double*)(ws + c.lb), *ub = (double*)(ws + c.ub);
   hipError_t e = raceline_qp_launch(line_qp_params(sp, L, N_s, N_c, H, g), (hipStream_t)stream);
   if (e != hipSuccess) return hipfail(e, "raceline_qp_launch");
+  CL.n_plans = n_plans; CL.N_s = N_s; CL.N_c = N_c; CL.L = L; CL.margin = margin; CL.g = g; CL.lb = lb; CL.ub = ub; CL.line = line; CL.flag = flag;
   if (cor) {
-    CL.n_plans = n_plans; CL.N_s = N_s; CL.N_c = N_c; CL.L = L; CL.margin = margin; CL.g = g; CL.lb = lb; CL.ub = ub; CL.line = line; CL.flag = flag;
     e = cor_line_bounds_launch(CL, (hipStream_t)stream);
     if (e != hipSuccess) return hipfail(e, "cor_line_bounds_launch");
+  } else if (boxed) {
+    MinlapBoxParams B; B.n_plans = n_plans; B.N_c = N_c; B.lo = start->lo; B.hi = start->hi; B.g = g; B.lb = lb; B.ub = ub;
+    e = minlap_box_launch(B, (hipStream_t)stream);
+    if (e != hipSuccess) return hipfail(e, "minlap_box_launch");
   } else {
     RacelineBoundsParams B; B.n_plans = n_plans; B.N_c = N_c; B.margin = margin; B.g = g; B.lb = lb; B.ub = ub;
     e = raceline_bounds_launch(B, par_values(par), par_stride(par), (hipStream_t)stream);
     if (e != hipSuccess) return hipfail(e, "raceline_bounds_launch");
   }
-  const fsaempc_qp_desc d = {N_c, 0, n_plans, 1};
-  if (int rc = fsaempc_qp_solve_batch_device_s(&d, 0, H, g, nullptr, lb, ub, nullptr, nullptr, opts, line, (double*)(ws + c.fval), flag,
-                                               (int*)(ws + c.iter), nullptr, nullptr, ws + c.qp, c.qp_bytes, stream)) return rc;
-  if (cor) {   // a plan whose QP was not solved (no box: flag -1, or any other flag but 0): NaN control points, which the profile turns into a NaN plan
-    e = cor_line_void_launch(CL, (hipStream_t)stream);
-    if (e != hipSuccess) return hipfail(e, "cor_line_void_launch");
+  if (given) {   // the caller's control points: no solve, every flag 0
+    e = hipMemcpyAsync(line, start->c_init, sizeof(double) * (size_t)n_plans * N_c, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int) * (size_t)n_plans, (hipStream_t)stream);
+    if (e != hipSuccess) return hipfail(e, "copy of c_init");
+  } else {
+    const fsaempc_qp_desc d = {N_c, 0, n_plans, 1};
+    if (int rc = fsaempc_qp_solve_batch_device_s(&d, 0, H, g, nullptr, lb, ub, nullptr, nullptr, opts, line, (double*)(ws + c.fval), flag,
+                                                 (int*)(ws + c.iter), nullptr, nullptr, ws + c.qp, c.qp_bytes, stream)) return rc;
+    if (cor || boxed) {   // a plan whose QP was not solved (no box: flag -1, or any other flag but 0): NaN control points, which the profile turns into a NaN plan
+      e = cor_line_void_launch(CL, (hipStream_t)stream);
+      if (e != hipSuccess) return hipfail(e, "cor_line_void_launch");
+    }
   }
+  const bool fallback = !cor && !boxed && !given;   // (in a corridor or a box: no centre-line fallback)
   PlanLineParams P = line_profile_params(model, sp, L, n_plans, N_s, N_c, v_cap, grip, table, t);
-  P.line = line; P.line_stride = N_c; P.flag = cor ? nullptr : flag; P.line_out = line; P.check_width = cor ? 0 : 1; P.margin = margin;   // (in a corridor: no centre-line fallback)
+  P.line = line; P.line_stride = N_c; P.flag = fallback ? flag : nullptr; P.line_out = line; P.check_width = (cor || boxed) ? 0 : 1; P.margin = margin;
   e = plan_line_profile_launch(P, par_values(par), par_stride(par), (hipStream_t)stream);
   if (e != hipSuccess) return hipfail(e, "plan_line_profile_launch");
   return 0;
@@ -1301,6 +1317,127 @@ int fsaempc_corridor_line_bounds_device(const fsaempc_corridor* cor, double L, i
   CL.n_plans = n_plans; CL.N_s = N_s; CL.N_c = N_c; CL.L = L; CL.margin = margin; CL.g = nullptr; CL.lb = lb; CL.ub = ub; CL.line = nullptr; CL.flag = nullptr;
   hipError_t e = cor_line_bounds_launch(CL, (hipStream_t)stream);
   if (e != hipSuccess) return hipfail(e, "cor_line_bounds_launch");
+  return 0;
+}
+
+/* ---- the minimum-time racing line ---- */
+static int minlap_check(const fsaempc_spline* sp, double L, int N_s, int N_c) {
+  if (int rc = line_check(sp, L, N_s, N_c)) return rc;
+  if (N_s > FSAEMPC_MINLAP_MAX_NS) return fail(FSAEMPC_ERR_ARG, "N_s must be <= FSAEMPC_MINLAP_MAX_NS");
+  return 0;
+}
+static MinlapGradParams minlap_grad_params(int model, const fsaempc_spline* sp, double L, int n_waves, int N_s, int N_c, double v_cap, double grip) {
+  MinlapGradParams P; memset(&P, 0, sizeof(P));
+  P.dynamic = model == FSAEMPC_MODEL_DYNAMIC; P.n_waves = n_waves; P.N_s = N_s; P.N_c = N_c; P.cand = 1; P.ds = L / N_s; P.h = L / N_c;
+  P.v_cap = v_cap; P.grip = grip; P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP; P.T_stride = 1;
+  return P;
+}
+
+int fsaempc_plan_line_lapgrad_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, int n_plans, int N_s,
+                                           int N_c, const double* line, int line_per_plan, double v_cap, double grip, double* T, double* grad,
+                                           void* stream) {
+  if (!line || !T || !grad) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (int rc = minlap_check(sp, L, N_s, N_c)) return rc;
+  if (int rc = line_profile_check(model, par, n_plans, v_cap, grip)) return rc;
+  MinlapGradParams P = minlap_grad_params(model, sp, L, n_plans, N_s, N_c, v_cap, grip);
+  P.line = line; P.line_stride = line_per_plan ? N_c : 0; P.T = T; P.grad = grad;
+  hipError_t e = minlap_lapgrad_launch(P, par_values(par), par_stride(par), (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "minlap_lapgrad_launch");
+  return 0;
+}
+
+// workspace of fsaempc_plan_minlap_batch_device: that of fsaempc_plan_raceline_batch_device for n_plans (H, the boxes and the initial
+// solve) | grad (n_plans x N_c) | per candidate (n_plans J): g, lb, ub, x (N_c each), T, fval, iter, flag | gradc (n_plans J x N_c) |
+// the solver's own for n_plans J instances
+struct MinlapCarve { LineCarve line; size_t grad, g, lb, ub, x, T, fval, iter, flag, gradc, qp, total; long long qp_bytes; };
+static int minlap_carve(int n_plans, int N_c, int J, MinlapCarve* c) {
+  if (J < 1 || J > FSAEMPC_MINLAP_MAX_RHO) return FSAEMPC_ERR_ARG;
+  if (int rc = line_carve(n_plans, N_c, &c->line)) return rc;
+  if ((long long)n_plans * J > 0x7fffffffLL) return FSAEMPC_ERR_ARG;
+  const int nJ = n_plans * J;
+  const fsaempc_qp_desc d = {N_c, 0, nJ, 1};
+  c->qp_bytes = fsaempc_qp_workspace_bytes_s(&d, 0);
+  if (c->qp_bytes < 0) return (int)c->qp_bytes;
+  const size_t vec = align64((size_t)nJ * N_c * sizeof(double)), one = align64((size_t)nJ * sizeof(double));
+  size_t off = align64(c->line.total);
+  c->grad = off; off += align64((size_t)n_plans * N_c * sizeof(double));
+  c->g = off; off += vec;
+  c->lb = off; off += vec;
+  c->ub = off; off += vec;
+  c->x = off; off += vec;
+  c->T = off; off += one;
+  c->fval = off; off += one;
+  c->iter = off; off += one;
+  c->flag = off; off += one;
+  c->gradc = off; off += vec;
+  c->qp = off; off += (size_t)c->qp_bytes;
+  c->total = off;
+  return 0;
+}
+long long fsaempc_plan_minlap_workspace_bytes(int n_plans, int N_c, int n_rho) {
+  MinlapCarve c;
+  if (int rc = minlap_carve(n_plans, N_c, n_rho, &c)) return rc;
+  return (long long)c.total;
+}
+
+int fsaempc_plan_minlap_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par, int n_plans, int N_s,
+                                     int N_c, double margin, double v_cap, double grip, const fsaempc_qp_opts* opts, int iters,
+                                     const double* rho, int n_rho, const double* c_init, const double* lo, const double* hi, double* line,
+                                     int* flag, double* table, double* t, double* lap_hist, int* step_hist, void* workspace,
+                                     long long workspace_bytes, void* stream) {
+  if (!line || !flag || !table || !t || !workspace || !rho || !lap_hist) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (int rc = minlap_check(sp, L, N_s, N_c)) return rc;
+  if (int rc = line_profile_check(model, par, n_plans, v_cap, grip)) return rc;
+  if (!(margin >= 0 && margin < INFINITY)) return fail(FSAEMPC_ERR_ARG, "margin must be finite and >= 0");
+  if (iters < 0) return fail(FSAEMPC_ERR_ARG, "iters must be >= 0");
+  if (iters > 0 && !step_hist) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (n_rho < 1 || n_rho > FSAEMPC_MINLAP_MAX_RHO) return fail(FSAEMPC_ERR_ARG, "n_rho must be 1 .. FSAEMPC_MINLAP_MAX_RHO");
+  for (int j = 0; j < n_rho; ++j)
+    if (!pos_finite(rho[j])) return fail(FSAEMPC_ERR_ARG, "every rho must be finite and > 0");
+  if ((lo != nullptr) != (hi != nullptr)) return fail(FSAEMPC_ERR_ARG, "lo and hi come together");
+  MinlapCarve c;
+  if (int rc = minlap_carve(n_plans, N_c, n_rho, &c)) return fail(rc, "bad dimensions");
+  if ((long long)c.total > workspace_bytes) return fail(FSAEMPC_ERR_WORKSPACE, "workspace too small");
+  char* ws = (char*)workspace;
+  const hipStream_t st = (hipStream_t)stream;
+  // the start: fsaempc_plan_raceline_batch_device itself (with K = 0 and neither boxes nor c_init this call is that entry)
+  const LineStart start = {lo, hi, c_init};
+  if (int rc = plan_raceline(model, sp, L, par, nullptr, n_plans, N_s, N_c, margin, v_cap, grip, opts, line, flag, table, t, ws,
+                             (long long)c.line.total, stream, (lo || c_init) ? &start : nullptr)) return rc;
+  const double *H = (const double*)(ws + c.line.H), *blo = (const double*)(ws + c.line.lb), *bhi = (const double*)(ws + c.line.ub);
+  double *grad = (double*)(ws + c.grad), *xc = (double*)(ws + c.x), *Tc = (double*)(ws + c.T), *gradc = (double*)(ws + c.gradc);
+  int* flagc = (int*)(ws + c.flag);
+  const int nJ = n_plans * n_rho, check_width = lo ? 0 : 1;
+  MinlapGradParams G = minlap_grad_params(model, sp, L, n_plans, N_s, N_c, v_cap, grip);
+  G.check_width = check_width; G.margin = margin; G.line = line; G.line_stride = N_c; G.T = lap_hist; G.T_stride = iters + 1; G.grad = grad;
+  hipError_t e = minlap_lapgrad_launch(G, par_values(par), par_stride(par), st);
+  if (e != hipSuccess) return hipfail(e, "minlap_lapgrad_launch");
+  for (int it = 0; it < iters; ++it) {
+    MinlapCandParams Q; memset(&Q, 0, sizeof(Q));
+    Q.n_plans = n_plans; Q.J = n_rho; Q.N_c = N_c; Q.grad = grad; Q.c = line; Q.lo = blo; Q.hi = bhi;
+    for (int j = 0; j < n_rho; ++j) Q.rho[j] = rho[j];
+    Q.g = (double*)(ws + c.g); Q.lb = (double*)(ws + c.lb); Q.ub = (double*)(ws + c.ub);
+    e = minlap_candidates_launch(Q, st);
+    if (e != hipSuccess) return hipfail(e, "minlap_candidates_launch");
+    const fsaempc_qp_desc d = {N_c, 0, nJ, 1};
+    if (int rc = fsaempc_qp_solve_batch_device_s(&d, 0, H, Q.g, nullptr, Q.lb, Q.ub, nullptr, nullptr, opts, xc, (double*)(ws + c.fval), flagc,
+                                                 (int*)(ws + c.iter), nullptr, nullptr, ws + c.qp, c.qp_bytes, stream)) return rc;
+    MinlapGradParams C = minlap_grad_params(model, sp, L, nJ, N_s, N_c, v_cap, grip);   // the candidates: clamp(c + d, lo, hi), each with its plan's block
+    C.cand = n_rho; C.check_width = check_width; C.margin = margin; C.line = xc; C.line_stride = N_c; C.base = line; C.lo = blo; C.hi = bhi;
+    C.line_out = xc; C.T = Tc; C.grad = gradc;
+    e = minlap_lapgrad_launch(C, par_values(par), par_stride(par), st);
+    if (e != hipSuccess) return hipfail(e, "minlap_lapgrad_launch");
+    MinlapSelectParams S; S.n_plans = n_plans; S.J = n_rho; S.N_c = N_c; S.it = it; S.K = iters; S.Tc = Tc; S.flagc = flagc; S.cc = xc; S.gradc = gradc;
+    S.c = line; S.grad = grad; S.lap_hist = lap_hist; S.step_hist = step_hist;
+    e = minlap_select_launch(S, st);
+    if (e != hipSuccess) return hipfail(e, "minlap_select_launch");
+  }
+  if (iters > 0) {   // the table of the final control points, by the line-profile path
+    PlanLineParams P = line_profile_params(model, sp, L, n_plans, N_s, N_c, v_cap, grip, table, t);
+    P.line = line; P.line_stride = N_c; P.flag = nullptr; P.line_out = line; P.check_width = check_width; P.margin = margin;
+    e = plan_line_profile_launch(P, par_values(par), par_stride(par), st);
+    if (e != hipSuccess) return hipfail(e, "plan_line_profile_launch");
+  }
   return 0;
 }
 

@@ -2,14 +2,16 @@
 dynamic_minimum_time_planner, main.m:115 resamples it with obtain_reference).  `Plan.profile` fills one on the device with the
 planner stand-in (a quasi-steady-state minimum-time speed profile on the centre line), `Plan.from_table` takes a user's own;
 `plan.reference` and ClosedLoop(reference=plan) resample it in time for a batch of cars.  `Plan.raceline` chooses a minimum-curvature
-line first and makes the profile on it; `Plan.profile(line=c)` takes a user's own control points."""
+line first and makes the profile on it; `Plan.profile(line=c)` takes a user's own control points.  `Plan.minlap` lowers
+the lap time of that profile over the control points from there; `Plan.lap_gradient` is the lap time and its gradient."""
 import ctypes as C
 import math
 
 import numpy as np
 
 from .corridor import Corridor, check_corridor
-from ._lib import LINE_MAX_NS, LINE_MIN_NC, MAX_NV, NPAR, PLAN_MAX_NS, ParamBlock, PlanTable, Spline, check, default_opts, lib
+from ._lib import (LINE_MAX_NS, LINE_MIN_NC, MAX_NV, MINLAP_MAX_NS, MINLAP_MAX_RHO, MINLAP_RHO, NPAR, PLAN_MAX_NS, ParamBlock, PlanTable, Spline, check,
+                   default_opts, lib)
 
 
 def check_profile_args(N_s, v_cap, grip, n_plans):
@@ -33,6 +35,23 @@ def check_line_args(N_s, N_c, margin=None):
         raise ValueError("N_s must be an integer in 2 N_c = %d .. %d, got %r" % (2 * N_c, LINE_MAX_NS, N_s))
     if margin is not None and not (isinstance(margin, (int, float, np.floating, np.integer)) and math.isfinite(margin) and margin >= 0):
         raise ValueError("margin must be finite and >= 0, got %r" % (margin,))
+
+
+def check_minlap_args(N_s, iters, rho):
+    """Validates the cell cap, iteration count and ladder of Plan.minlap (no library call); returns the ladder as a tuple of floats."""
+    if N_s > MINLAP_MAX_NS:
+        raise ValueError("N_s must be <= %d for the minimum-time line, got %r" % (MINLAP_MAX_NS, N_s))
+    if isinstance(iters, bool) or int(iters) != iters or iters < 0:
+        raise ValueError("iters must be an integer >= 0, got %r" % (iters,))
+    try:
+        rho = tuple(float(r) for r in rho)
+    except (TypeError, ValueError):
+        raise ValueError("rho must be a sequence of numbers")
+    if not 1 <= len(rho) <= MINLAP_MAX_RHO:
+        raise ValueError("rho must hold 1 .. %d values, got %d" % (MINLAP_MAX_RHO, len(rho)))
+    if not all(math.isfinite(r) and r > 0 for r in rho):
+        raise ValueError("every rho must be finite and > 0, got %r" % (rho,))
+    return rho
 
 
 def check_params(params, n_plans):
@@ -100,6 +119,7 @@ class Plan:
         self.c = PlanTable(C.c_void_p(table.data_ptr()), C.c_void_p(t.data_ptr()), self.N_s, self.ds, 1 if self.P > 1 else 0)
         self.line, self.line_flag = None, None   # control points of the lateral offset and the flags of their QPs (Plan.raceline)
         self.row_lambda = None                   # multipliers of the cell rows (Plan.raceline(rows="cells", want_row_lambda=True))
+        self.control_points, self.lap_history, self.step_history = None, None, None   # Plan.minlap: .line and the record of its iterations
 
     def ref(self):
         return C.byref(self.c)
@@ -221,6 +241,113 @@ class Plan:
         plan._blocks, plan._ws, plan._corridor = blocks, ws, corridor   # (read by launches that may still be queued)
         plan.line, plan.line_flag, plan.row_lambda = line, flag, row_lambda
         return plan
+
+    @staticmethod
+    def minlap(model, track, N_s=500, N_c=100, iters=12, rho=None, margin=0.25, corridor=None, params=None, grip=1.0, v_cap=20.0, c_init=None,
+               n_plans=1, options=None, device="cuda:0", stream=None):
+        """Minimum-time racing-line plans (fsaempc_plan_minlap_batch_device): from the line of Plan.raceline (or c_init,
+        (N_c,) or (P, N_c)), `iters` iterations that lower the lap time of the profile on the line, T(c) = sum t, by steps
+        d = argmin 1/2 rho d'H d + grad T'd inside the box of the control points, the best of the ladder `rho` per iteration (default:
+        MINLAP_RHO).  The line depends on model, grip, v_cap and the parameter block, because T does.  corridor: None (the box
+        +-(N_MAX - margin)) or a Corridor: the per-control-point boxes of Plan.raceline(corridor=).  Returns a Plan with .line
+        (= .control_points, (P, N_c)), .line_flag (P,) of the initial QPs, .lap_history (P, iters + 1), non-increasing, and
+        .step_history (P, iters): the index of the rho taken, -1 = stayed.  Still the quasi-steady-state profile (y_d = 0), a fixed
+        number of local steps, no IPOPT: not the reference's minimum_time_planner."""
+        check_profile_args(N_s, v_cap, grip, n_plans)
+        check_line_args(N_s, N_c, margin)
+        rho = check_minlap_args(N_s, iters, MINLAP_RHO if rho is None else rho)
+        if model not in (0, 1):
+            raise ValueError("unknown model %r" % (model,))
+        params, n_plans = check_params(params, n_plans)
+        shared_block = params is not None and len(tuple(params.shape)) == 1
+        if corridor is not None:
+            if not isinstance(corridor, Corridor):
+                raise ValueError("corridor must be None or a Corridor")
+            if corridor.P > 1 and shared_block:
+                raise ValueError("a shared parameter block makes one plan, the corridor holds %d" % corridor.P)
+            if corridor.P > 1 and params is None and n_plans == 1:
+                n_plans = corridor.P
+            check_corridor(corridor, n_plans, device)
+        if c_init is not None:
+            c_init, n_ci, n_line = check_line(c_init, N_s, n_plans)
+            if n_ci != N_c:
+                raise ValueError("c_init holds %d control points, N_c = %d" % (n_ci, N_c))
+            if n_line != n_plans:
+                if shared_block:
+                    raise ValueError("a shared parameter block makes one plan, c_init holds %d" % n_line)
+                n_plans = n_line
+        import torch
+        dev = torch.device(device)
+        N_s, N_c, n_plans, iters, J = int(N_s), int(N_c), int(n_plans), int(iters), len(rho)
+        xP, yP = track.device(dev)
+        sp = Spline(track.M, track.dl, C.c_void_p(xP.data_ptr()), C.c_void_p(yP.data_ptr()))
+        blocks = ParamBlock(params, n_plans, dev) if params is not None else None
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda a: C.c_void_p(a.data_ptr())
+        lo = hi = ci = None
+        if corridor is not None:
+            lo = torch.empty((n_plans, N_c), dtype=torch.float64, device=dev)
+            hi = torch.empty((n_plans, N_c), dtype=torch.float64, device=dev)
+            rc = lib().fsaempc_corridor_line_bounds_device(corridor.ref(), C.c_double(track.L), n_plans, N_s, N_c, C.c_double(margin), p(lo), p(hi), st)
+            check(rc, "fsaempc_corridor_line_bounds_device")
+        if c_init is not None:
+            ci = c_init if isinstance(c_init, torch.Tensor) else torch.from_numpy(np.array(c_init, dtype=np.float64))
+            ci = ci.to(device=dev, dtype=torch.float64).reshape(-1, N_c).expand(n_plans, N_c).contiguous()
+        need = lib().fsaempc_plan_minlap_workspace_bytes(n_plans, N_c, J)
+        if need < 0:
+            check(int(need), "fsaempc_plan_minlap_workspace_bytes")
+        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+        line = torch.empty((n_plans, N_c), dtype=torch.float64, device=dev)
+        flag = torch.empty(n_plans, dtype=torch.int32, device=dev)
+        table = torch.empty((n_plans, N_s, 8), dtype=torch.float64, device=dev)
+        t = torch.empty((n_plans, N_s), dtype=torch.float64, device=dev)
+        lap = torch.empty((n_plans, iters + 1), dtype=torch.float64, device=dev)
+        step = torch.empty((n_plans, iters), dtype=torch.int32, device=dev)
+        opts = options if options is not None else default_opts()
+        rho_c = (C.c_double * J)(*rho)
+        rc = lib().fsaempc_plan_minlap_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                    n_plans, N_s, N_c, C.c_double(margin), C.c_double(v_cap), C.c_double(grip), C.byref(opts), iters,
+                                                    rho_c, J, p(ci) if ci is not None else None, p(lo) if lo is not None else None,
+                                                    p(hi) if hi is not None else None, p(line), p(flag), p(table), p(t), p(lap),
+                                                    p(step) if iters > 0 else None, p(ws), C.c_longlong(ws.numel() * 8), st)
+        check(rc, "fsaempc_plan_minlap_batch_device")
+        plan = Plan(table, t, track.L / N_s)
+        plan._blocks, plan._ws, plan._corridor, plan._box = blocks, ws, corridor, (lo, hi, ci)   # (read by launches that may still be queued)
+        plan.line, plan.line_flag = line, flag
+        plan.control_points, plan.lap_history, plan.step_history, plan.rho = line, lap, step, rho
+        return plan
+
+    @staticmethod
+    def lap_gradient(model, track, c, N_s=500, v_cap=20.0, grip=1.0, params=None, n_plans=1, device="cuda:0", stream=None):
+        """(T, grad): the lap time (P,) of the profile of Plan.profile(line=c) and its gradient (P, N_c) in the control points c, (N_c,)
+        shared by the plans or (P, N_c), on the device (fsaempc_plan_line_lapgrad_batch_device).  A NaN plan has T = NaN
+        and a NaN gradient."""
+        check_profile_args(N_s, v_cap, grip, n_plans)
+        check_minlap_args(N_s, 0, MINLAP_RHO)
+        if model not in (0, 1):
+            raise ValueError("unknown model %r" % (model,))
+        params, n_plans = check_params(params, n_plans)
+        c, N_c, n_line = check_line(c, N_s, n_plans)
+        if n_line != n_plans:
+            if params is not None and len(tuple(params.shape)) == 1:
+                raise ValueError("a shared parameter block makes one plan, c holds %d" % n_line)
+            n_plans = n_line
+        import torch
+        dev = torch.device(device)
+        N_s, N_c, n_plans = int(N_s), int(N_c), int(n_plans)
+        xP, yP = track.device(dev)
+        sp = Spline(track.M, track.dl, C.c_void_p(xP.data_ptr()), C.c_void_p(yP.data_ptr()))
+        blocks = ParamBlock(params, n_plans, dev) if params is not None else None
+        cd = (c if isinstance(c, torch.Tensor) else torch.from_numpy(np.array(c, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()
+        T = torch.empty(n_plans, dtype=torch.float64, device=dev)
+        grad = torch.empty((n_plans, N_c), dtype=torch.float64, device=dev)
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+        rc = lib().fsaempc_plan_line_lapgrad_batch_device(int(model), C.byref(sp), C.c_double(track.L), blocks.ref() if blocks is not None else None,
+                                                          n_plans, N_s, N_c, C.c_void_p(cd.data_ptr()), 1 if cd.dim() == 2 else 0, C.c_double(v_cap),
+                                                          C.c_double(grip), C.c_void_p(T.data_ptr()), C.c_void_p(grad.data_ptr()), st)
+        check(rc, "fsaempc_plan_line_lapgrad_batch_device")
+        T._keep = (blocks, cd)   # (read by a launch that may still be queued)
+        return T, grad
 
     @staticmethod
     def from_table(table, t, ds, device="cuda:0"):

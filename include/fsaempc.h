@@ -819,6 +819,65 @@ int fsaempc_plan_raceline_cells_batch_device(int model, const fsaempc_spline* sp
 int fsaempc_corridor_line_rows_device(const fsaempc_corridor* cor, double L, int n_plans, int N_s, int N_c, double margin,
                                       double* A, double* lbA, double* ubA, void* stream);
 
+/* ---- a minimum-time racing line --------------------------------------------------
+ * What the reference's planners are for (minimum_time_planner.m, dynamic_minimum_time_planner.m: the line that minimises the lap
+ * time), approximated on the quasi-steady-state profile of fsaempc_plan_line_profile_batch_device: the lap time of a line is
+ * T(c) = sum_i t_i of that profile, a function of the control points c through the line's length and curvature per cell, and it is
+ * lowered by projected, H-preconditioned gradient steps from the minimum-curvature line.  What it is not: the reference's optimal
+ * control problem.  The speed is still the quasi-steady-state profile (y_d = 0: no lateral dynamics, no yaw dynamics, no tyre
+ * model), the line is searched in the B-spline's N_c control points inside a box, no IPOPT: a fixed number of steps, each no worse
+ * than the last, from one start -- a local improvement, not a certified minimum. */
+#define FSAEMPC_MINLAP_MAX_NS 1024   /* the lap-gradient kernel keeps eight doubles and the two win flags of a cell in LDS: 68 bytes per cell */
+#define FSAEMPC_MINLAP_MAX_RHO 16    /* candidates per plan and iteration */
+
+/*
+ * T (n_plans) and grad = dT/dc (n_plans * N_c) of the lines `line`, inputs as fsaempc_plan_line_profile_batch_device.  The forward
+ * arithmetic is that entry's, so T is the sum of its t (to the rounding of the sum: each lane adds its cells i = lane, lane + 64, ..
+ * in ascending order, then the wave adds the 64 partial sums in a butterfly).  The gradient is the adjoint of the profile: the two
+ * passes are undone in reverse order along the branches the forward run took (which argument won each min; the polygon edge and
+ * the U_ACC_MAX / y = 1 branches of the longitudinal limit; |k| against 1e-12; the corner speed against v_cap), then the cell's
+ * curvature, length and heading offset, then the basis.  T is piecewise smooth in c: where two arguments of a min tie, grad is the
+ * one-sided derivative of the branch taken.  Every grad_j is a sum over its cells in ascending order: the same bits on every call.
+ * A plan that fsaempc_plan_line_profile_batch_device makes NaN has T = NaN and a NaN gradient; the other plans are unaffected.
+ * FSAEMPC_ERR_ARG before any launch: the cases of fsaempc_plan_line_profile_batch_device; N_s > FSAEMPC_MINLAP_MAX_NS.
+ */
+int fsaempc_plan_line_lapgrad_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par,
+                                           int n_plans, int N_s, int N_c, const double* line, int line_per_plan,
+                                           double v_cap, double grip, double* T, double* grad, void* stream);
+
+/*
+ * Minimum-time plans in one call, asynchronous on `stream`, with no host read inside: the start, then `iters` iterations, then the
+ * table of the final control points by the path of fsaempc_plan_line_profile_batch_device.
+ *   start      c_init == NULL: fsaempc_plan_raceline_batch_device (the minimum-curvature line).  c_init (n_plans * N_c, device):
+ *              those control points, no solve, every flag 0.
+ *   boxes      lo == hi == NULL: +-(N_MAX_p - margin), as in fsaempc_plan_raceline_batch_device.  lo, hi (n_plans * N_c each, device,
+ *              both or neither; from fsaempc_corridor_line_bounds_device for instance): the box of every control point, for the
+ *              initial QP and every step; margin and the block's N_MAX are then not read.  A plan with lo_j < hi_j false anywhere has
+ *              flag -1 and is NaN; with boxes no plan falls back to the centre line (every plan whose flag is not 0 is NaN).
+ *   iteration  per plan p and rho_j (rho: n_rho values on the HOST, 1 .. FSAEMPC_MINLAP_MAX_RHO, finite and > 0):
+ *              d_pj = argmin 1/2 d'H d + (grad_p / rho_j)'d, lo_p - c_p <= d <= hi_p - c_p, with the H of
+ *              fsaempc_raceline_build_qp_device -- one H for all n_plans * n_rho instances of fsaempc_qp_solve_batch_device_s, `opts`
+ *              as given; candidates clamp(c_p + d_pj, lo_p, hi_p); their lap times and gradients from one launch of the
+ *              lap-gradient kernel, each with its plan's block; the least finite T among the candidates whose QP flag is 0 (first
+ *              index on ties) replaces the incumbent if strictly smaller, with its gradient.  A NaN plan never moves.
+ * Outputs: line (n_plans * N_c) the final control points, flag (n_plans) of the initial QPs, table / t of the final line (bit for
+ * bit fsaempc_plan_line_profile_batch_device on `line`), lap_hist (n_plans * (iters + 1), non-increasing in every finite row:
+ * [p * (iters + 1)] is the start's T), step_hist (n_plans * iters: the index of the rho taken, -1 = stayed; may be NULL when
+ * iters = 0).  With iters = 0 and neither boxes nor c_init line, flag, table and t are fsaempc_plan_raceline_batch_device's bits.
+ * workspace: fsaempc_plan_minlap_workspace_bytes(n_plans, N_c, n_rho) bytes (< 0: FSAEMPC_ERR_ARG for such shapes); every element
+ * read is written by the call.
+ * FSAEMPC_ERR_ARG before any launch: the cases of fsaempc_plan_raceline_batch_device; N_s > FSAEMPC_MINLAP_MAX_NS; iters < 0; n_rho
+ * outside 1 .. FSAEMPC_MINLAP_MAX_RHO; a rho that is not finite and > 0; lo without hi or hi without lo; a null pointer.
+ * FSAEMPC_ERR_WORKSPACE: workspace too small (the code every entry of this library answers that with).
+ */
+long long fsaempc_plan_minlap_workspace_bytes(int n_plans, int N_c, int n_rho);
+int fsaempc_plan_minlap_batch_device(int model, const fsaempc_spline* sp, double L, const fsaempc_ltv_params* par,
+                                     int n_plans, int N_s, int N_c, double margin, double v_cap, double grip,
+                                     const fsaempc_qp_opts* opts, int iters, const double* rho, int n_rho,
+                                     const double* c_init, const double* lo, const double* hi,
+                                     double* line, int* flag, double* table, double* t, double* lap_hist, int* step_hist,
+                                     void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- track corridors from cone positions ---------------------------------------------
  * The tables of an fsaempc_corridor from the two rows of cones that mark the track, on the device and batched: n_corridors cone
  * maps (P noisy maps of one track, say) give n_corridors corridors, in exactly the layout fsaempc_corridor reads with

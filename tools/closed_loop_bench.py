@@ -5,6 +5,8 @@ no per-step read-back (fsae_mpc_amd.monte_carlo).  Prints one JSON line: QP solv
 driving, the exit-flag tally the way main.m:209,222 reports it ("abnormal exits %"), iterations, progress.
 --plan: the cars track a plan of the planner stand-in (fsaempc.Plan.profile) instead of the live ramp to 20 m/s.
 --raceline: the plan is made on a minimum-curvature racing line (fsaempc.Plan.raceline) instead of the centre line.
+--minlap K: the plan is made on a minimum-time racing line (fsaempc.Plan.minlap): K iterations from the minimum-curvature
+line; takes --margin, --points, --grip, --cells and --corridor / --cones (the boxes of the control points) as --raceline does.
 --report: the lap report (main.m:196-228 over the batch) joins the JSON line as "lap_report".
 --corridor FILE.npz: an s-varying track corridor (fsaempc.Corridor) from arrays n_lo, n_hi of (N_w,) over the lap of the
 track; the controller's track rows, the report's track violation and, with --raceline, the line's bounds are taken against it.
@@ -20,7 +22,7 @@ defaults to 1000 (main.m:62): a finished car's STEPS * dt is then a lap time.
 crossing to a fraction of dt); with --lap the step cap defaults to 1000 K; the per-lap summary (cars that completed the lap, mean, min and
 max of its time) joins the JSON line as "lap_summary".
 usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--track fss2019]
-                                  [--plan | --raceline [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap] [--laps K]
+                                  [--plan | --raceline | --minlap K [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap] [--laps K]
                                   [--corridor FILE.npz | --cones FILE [--car-half-width W]] [--line-rows points|cells]"""
 import argparse, json, os, sys, time
 import numpy as np
@@ -48,6 +50,7 @@ def main():
     ap.add_argument("--grip", type=float, default=1.0, help="with --plan: share of the lateral / longitudinal limits the plan uses, (0, 1]")
     ap.add_argument("--cells", type=int, default=500, help="with --plan: cells per lap (N_s)")
     ap.add_argument("--raceline", action="store_true", help="track a plan on a minimum-curvature racing line (Plan.raceline); takes --grip and --cells too")
+    ap.add_argument("--minlap", type=int, default=None, metavar="K", help="track a plan on a minimum-time racing line (Plan.minlap, K iterations); takes what --raceline takes")
     ap.add_argument("--margin", type=float, default=0.25, help="with --raceline: distance the line keeps from N_MAX, m")
     ap.add_argument("--points", type=int, default=100, help="with --raceline: control points of the line (N_c)")
     ap.add_argument("--corridor", default=None, metavar="FILE.npz", help="track corridor: arrays n_lo, n_hi of (N_w,) over the lap (Corridor.from_table)")
@@ -61,6 +64,8 @@ def main():
         ap.error("--cones and --corridor exclude each other")
     if a.line_rows == "cells" and not (a.raceline and (a.corridor is not None or a.cones is not None)):
         ap.error("--line-rows cells needs --raceline and --corridor or --cones")
+    if a.minlap is not None and (a.raceline or a.minlap < 0):
+        ap.error("--minlap K needs K >= 0 and excludes --raceline")
     if a.steps is None:
         a.steps = 1000 * a.laps if a.lap else 200
     model = fm.KINEMATIC if a.model == "kinematic" else fm.DYNAMIC
@@ -90,6 +95,8 @@ def main():
     plan = fm.Plan.profile(model, tr, N_s=a.cells, grip=a.grip) if a.plan else None
     if a.raceline:
         plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip, corridor=cor, rows=a.line_rows)
+    if a.minlap is not None:
+        plan = fm.Plan.minlap(model, tr, N_s=a.cells, N_c=a.points, iters=a.minlap, margin=a.margin, grip=a.grip, corridor=cor)
     fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor)          # warm-up (allocations, code load)
     n_max = float(fm.default_params(model)[fm.PARAM_INDEX["N_MAX"]])
     opts = fm.default_opts(max_iter=a.max_iter)
@@ -156,6 +163,9 @@ def main():
                    "cars_past_end_of_track_parameter": int((cl.finished == 1).sum().item()), "cars_lost": int((cl.finished == 2).sum().item()),
                    "mean_speed_end": float(cl.cart[:, 3].mean().item()),
                    "reference": ("plan: racing line, N_s = %d, N_c = %d, margin %g, grip %g, corridor rows: %s, QP flag %d, lap %.2f s" % (a.cells, a.points, a.margin, a.grip, a.line_rows, int(plan.line_flag[0]), float(plan.lap_time()[0]))) if a.raceline
+                                else ("plan: minimum-time line, N_s = %d, N_c = %d, margin %g, grip %g, %d iterations, QP flag %d, lap %.3f s -> %.3f s, steps %s" % (
+                                    a.cells, a.points, a.margin, a.grip, a.minlap, int(plan.line_flag[0]), float(plan.lap_history[0, 0]), float(plan.lap_history[0, -1]),
+                                    plan.step_history[0].tolist())) if a.minlap is not None
                                 else ("plan: speed profile, N_s = %d, grip %g, lap %.2f s" % (a.cells, a.grip, float(plan.lap_time()[0]))) if a.plan else "live ramp to 20 m/s",
                    "steps_off_track_abs_n_gt_N_MAX": int(off.item()), "mean_distance_covered_m": float(np.nanmean(dist)),
                    "total_distance_covered_m": float(np.nansum(dist)),
