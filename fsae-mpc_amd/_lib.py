@@ -34,6 +34,7 @@ EXPORTS = [
     "fsaempc_plan_raceline_cells_workspace_bytes", "fsaempc_plan_raceline_cells_batch_device", "fsaempc_corridor_line_rows_device",
     "fsaempc_corridor_from_cones_device", "fsaempc_track_cones_from_csv", "fsaempc_track_cones_free",
     "fsaempc_plan_line_lapgrad_batch_device", "fsaempc_plan_minlap_workspace_bytes", "fsaempc_plan_minlap_batch_device",
+    "fsaempc_cl_noise_batch_device", "fsaempc_cl_observe_batch_device", "fsaempc_cl_history_slot",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -58,6 +59,9 @@ REPORT_INDEX = {name: i for i, name in enumerate(
 MAX_LAPS = 64
 NLAPSTATE = 4
 LAP_STATE_INDEX = {name: i for i, name in enumerate(["DONE", "STEPS", "S_PREV", "T_CROSS"])}
+
+
+CL_MAX_DELAY = 4     # FSAEMPC_CL_MAX_DELAY
 
 
 def check_laps(laps):
@@ -102,6 +106,11 @@ class LtvDesc(C.Structure):
 
 class LtvParams(C.Structure):
     _fields_ = [("values", C.c_void_p), ("per_instance", C.c_int)]
+
+
+class ClLatency(C.Structure):   # fsaempc_cl_latency
+    _fields_ = [("delay", C.c_int), ("compensate", C.c_int), ("sigma", C.c_void_p), ("sigma_per_instance", C.c_int),
+                ("seed", C.c_ulonglong), ("id0", C.c_longlong)]
 
 
 class LtvBlocking(C.Structure):
@@ -297,6 +306,9 @@ def lib():
         L.fsaempc_track_cones_free.restype = None
         L.fsaempc_cl_lap_gate_batch_device.argtypes =[C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int] + [vp] * 9
         L.fsaempc_cl_lap_summary.argtypes = [vp, C.c_int, C.c_int, vp]
+        L.fsaempc_cl_noise_batch_device.argtypes = [C.c_int, C.c_int, C.c_ulonglong, ll, ll, vp, vp]
+        L.fsaempc_cl_observe_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(ClLatency), ll] + [vp] * 6
+        L.fsaempc_cl_history_slot.argtypes = [C.c_int, ll, C.c_int]
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p
         L.fsaempc_track_from_csv.argtypes = [C.c_char_p, C.c_int, C.POINTER(TrackTable)]

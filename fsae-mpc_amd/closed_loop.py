@@ -4,8 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (LAP_STATE_INDEX, METRIC_INDEX, NLAPSTATE, NMETRIC, NREPORT, REPORT_INDEX, ParamBlock, Spline, check, check_blocking,
-                   check_laps, lib)
+from ._lib import (CL_MAX_DELAY, LAP_STATE_INDEX, METRIC_INDEX, NLAPSTATE, NMETRIC, NREPORT, REPORT_INDEX, ClLatency, ParamBlock, Spline, check,
+                   check_blocking, check_laps, lib)
 from .ltvmpc import LtvBatch, dims
 from .corridor import check_corridor
 from .plan import Plan
@@ -57,6 +57,74 @@ class LapReport:
         return {name.lower(): float(out[i]) for name, i in REPORT_INDEX.items()}
 
 
+class Latency:
+    """The imperfections of a closed loop, validated here without a library call.  delay: whole MPC periods (0 ..
+    CL_MAX_DELAY) between the state a plan is solved from and the period in which the plant follows it.  compensate: solve from the
+    observed state predicted over those periods (needs delay >= 1).  sigma: None, or the standard deviations of the state-estimate
+    noise in the model's state layout, (nx,) for the batch or (B, nx) per car, finite and >= 0 (a zero leaves the component exact).
+    seed, id0: the noise of car b depends on (seed, id0 + b, period, component) only -- id0 is a shard's first global id."""
+
+    def __init__(self, delay=0, compensate=False, sigma=None, seed=0, id0=0):
+        def integer(v, name):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError("%s must be an integer" % name)
+            return int(v)
+        self.delay = integer(delay, "delay")
+        if not 0 <= self.delay <= CL_MAX_DELAY:
+            raise ValueError("delay must be 0 .. %d" % CL_MAX_DELAY)
+        if not isinstance(compensate, (bool, np.bool_)) and compensate not in (0, 1):
+            raise ValueError("compensate must be True or False")
+        self.compensate = bool(compensate)
+        if self.compensate and self.delay < 1:
+            raise ValueError("compensate needs delay >= 1")
+        self.seed = integer(seed, "seed")
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2^64)")
+        self.id0 = integer(id0, "id0")
+        if not 0 <= self.id0 < 2 ** 63:
+            raise ValueError("id0 must be >= 0 (and below 2^63)")
+        if sigma is not None:
+            try:
+                sigma = np.array(sigma, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("sigma must be an array of numbers")
+            if sigma.ndim not in (1, 2) or sigma.shape[-1] not in (5, 7):
+                raise ValueError("sigma must be (nx,) or (B, nx), got %s" % (sigma.shape,))
+            if not np.isfinite(sigma).all() or (sigma < 0).any():
+                raise ValueError("sigma must be finite and >= 0")
+        self.sigma = sigma
+
+    @property
+    def engaged(self):
+        return self.delay > 0 or self.sigma is not None
+
+    def check_batch(self, nx, B):
+        """The shape of sigma against the model and the batch of the loop that takes it."""
+        if self.sigma is not None and self.sigma.shape not in ((nx,), (B, nx)):
+            raise ValueError("sigma must be (nx = %d,) or (B = %d, %d), got %s" % (nx, B, nx, self.sigma.shape))
+
+
+def check_latency(latency, nx, B):
+    """Validates ClosedLoop's latency argument (no library call): None or a Latency whose sigma fits (nx,) or (B, nx)."""
+    if latency is None:
+        return None
+    if not isinstance(latency, Latency):
+        raise ValueError("latency must be None or a Latency")
+    latency.check_batch(nx, B)
+    return latency
+
+
+def cl_noise(nx, B, seed, id0, step, device="cuda:0"):
+    """The (B, nx) standard normals the observation of period `step` draws for cars id0 .. id0 + B - 1
+    (fsaempc_cl_noise_batch_device), a device tensor."""
+    import torch
+    z = torch.empty((int(B), int(nx)), dtype=torch.float64, device=device)
+    check(lib().fsaempc_cl_noise_batch_device(int(nx), int(B), C.c_ulonglong(int(seed)), C.c_longlong(int(id0)), C.c_longlong(int(step)),
+                                              C.c_void_p(z.data_ptr()), C.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)),
+          "fsaempc_cl_noise_batch_device")
+    return z
+
+
 class ClosedLoop:
     """B cars on one track.  cart0: (B, 7) Cartesian states [x, y, theta, x_d, y_d, theta_d, delta] (main.m:63 starts
     from zeros(7,1)).  step() advances every car by one MPC period dt, all on the device and without reading anything
@@ -64,7 +132,8 @@ class ClosedLoop:
     plan -- and the exit flags are only tallied.  Cars that completed the lap (s >= L) or left the track keep their state."""
 
     def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
-                 params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6, corridor=None, laps=1):
+                 params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6, corridor=None, laps=1,
+                 latency=None):
         """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
         None = the same as params (both None: the reference's constants compiled into the kernels).  blocking: block lengths of the
         controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2).  reference: None = the live
@@ -76,7 +145,12 @@ class ClosedLoop:
         (DESIGN.md 6l).  laps: 1 = the run of a car ends the first time s >= L (main.m:102-104); K > 1 = the lap gate (lap_gate(), one more
         kernel per step between pre() and the MPC step) carries it over the line K - 1 times: self.lap_times (B, K) holds the laps' times
         to a fraction of dt (NaN: not completed), self.lap_state (B, 4) the gate's state (LAP_STATE_INDEX), and with metrics
-        self.lap_records (B, K, 16) the closed laps' records while self.metrics is the record of the lap being driven."""
+        self.lap_records (B, K, 16) the closed laps' records while self.metrics is the record of the lap being driven.
+        latency: None or a Latency.  None, or one with delay 0 and no sigma, is the ideal loop: step() launches what it
+        launches without the argument.  Otherwise step() observes the state after pre() and the lap gate (self.x0_obs = x0 + noise),
+        predicts it over the delay if asked to (self.x0_mpc), regenerates x_ref from x0_mpc, solves from x0_mpc, and the plant follows
+        the plan accepted `delay` periods ago (self.plant_plan, a view of self.x_hist (delay + 1, B, N, nx); self.u_hist likewise).
+        self.x0 stays the true state (the gate and the metrics read it); self.x_opt / self.u_opt stay the newest plan."""
         if not (float(slack_tol) >= 0):
             raise ValueError("slack_tol must be >= 0")
         self.laps = check_laps(laps)   # (before the library is touched)
@@ -89,6 +163,9 @@ class ClosedLoop:
             reference.check_device(device)
         self.reference = reference
         check_corridor(corridor, np.asarray(cart0).size // 7, device)   # (before the library is touched)
+        self.latency = check_latency(latency, 5 if model == 0 else 7, np.asarray(cart0).size // 7)   # (likewise)
+        if self.latency is not None and not self.latency.engaged:
+            self.latency = None
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -119,6 +196,19 @@ class ClosedLoop:
         self.u_last = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)
         self.steps = 0
         self.slack_tol = float(slack_tol)
+        self.x0_obs = self.x0_mpc = self.x_hist = self.u_hist = None
+        self.plant_plan = self.x_opt
+        if self.latency is not None:
+            lat = self.latency
+            self.x0_obs = torch.empty_like(self.x0)
+            self.x0_mpc = torch.empty_like(self.x0)
+            self._s0_mpc = torch.empty(self.B, dtype=torch.float64, device=self.device)
+            self._sigma = torch.from_numpy(lat.sigma).to(self.device).contiguous() if lat.sigma is not None else None
+            self._lat = ClLatency(lat.delay, int(lat.compensate), C.c_void_p(self._sigma.data_ptr()) if self._sigma is not None else None,
+                                  1 if self._sigma is not None and self._sigma.dim() == 2 else 0, lat.seed, lat.id0)
+            if lat.delay > 0:   # the history is filled from x_opt / u_opt at the first step(): callers edit the initial guess before it
+                self.x_hist = torch.empty((lat.delay + 1, self.B, N, self.nx), dtype=torch.float64, device=self.device)
+                self.u_hist = torch.empty((lat.delay + 1, self.B, N, 2), dtype=torch.float64, device=self.device)
         self.metrics = torch.zeros((self.B, NMETRIC), dtype=torch.float64, device=self.device) if metrics else None
         self.lap_state = self.lap_times = self.lap_records = None   # laps == 1: nothing is allocated unless lap_gate() is called
         if self.laps > 1:
@@ -170,12 +260,32 @@ class ClosedLoop:
                                                      P(self.metrics) if self.lap_records is not None else None, P(self.lap_records),
                                                      self._stream(stream)), "fsaempc_cl_lap_gate_batch_device")
 
-    def plant(self, exitflag, stream=None):
+    def plant(self, exitflag, stream=None, plan=None):
+        """plan: the (B, N, nx) plan the set points are read from; None = self.x_opt."""
         P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         rc = lib().fsaempc_cl_plant_batch_device_p(self.model, self.N, C.c_double(self.dt), self.B,
                                                    self.plant_params.ref() if self.plant_params is not None else None, P(self.cart), P(self.pid),
-                                                   P(self.x_opt), P(self.finished), P(exitflag), P(self.u_last), self._stream(stream))
+                                                   P(self.x_opt if plan is None else plan), P(self.finished), P(exitflag), P(self.u_last),
+                                                   self._stream(stream))
         check(rc, "fsaempc_cl_plant_batch_device_p")
+
+    def observe(self, stream=None):
+        """Observation and prediction of this period on what pre() and the lap gate left in self.x0 (fsaempc_cl_observe_batch_device),
+        then x_ref regenerated from x0_mpc by the reference the loop runs on."""
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if self.u_hist is not None and self.steps == 0:
+            self.x_hist.copy_(self.x_opt.unsqueeze(0).expand_as(self.x_hist))
+            self.u_hist.copy_(self.u_opt.unsqueeze(0).expand_as(self.u_hist))
+        check(lib().fsaempc_cl_observe_batch_device(C.byref(self.mpc.desc), C.byref(self.mpc.sp), self.mpc.params.ref() if self.mpc.params is not None else None,
+                                                    C.byref(self._lat), self.steps, P(self.x0), P(self.finished), P(self.u_hist), P(self.x0_obs),
+                                                    P(self.x0_mpc), self._stream(stream)), "fsaempc_cl_observe_batch_device")
+        if self.reference is not None:
+            self._s0_mpc.copy_(self.x0_mpc[:, 0])
+            check(lib().fsaempc_plan_reference_batch_device(self.model, self.reference.ref(), P(self._s0_mpc), C.c_double(self.dt), self.N, self.B,
+                                                            P(self.x_ref), self._stream(stream)), "fsaempc_plan_reference_batch_device")
+        else:
+            check(lib().fsaempc_reference_live_batch_device(self.nx, self.N, C.c_double(self.dt), C.c_double(self.target_vel), self.B, P(self.x0_mpc),
+                                                            P(self.x_ref), self._stream(stream)), "fsaempc_reference_live_batch_device")
 
     def step(self, stream=None):
         torch = self.torch
@@ -195,7 +305,11 @@ class ClosedLoop:
                 x_init[:, 2 * (N - 1): 2 * N].copy_(self.u_opt[:, N - 1, :])
             if self._slack is not None:
                 x_init[:, nu:].copy_(self._slack)
-        out = self.mpc.step(self.x0, self.x_ref, self.x_opt, self.u_opt, stream=stream, x_init=x_init,
+        x0 = self.x0
+        if self.latency is not None:
+            self.observe(stream)
+            x0 = self.x0_mpc
+        out = self.mpc.step(x0, self.x_ref, self.x_opt, self.u_opt, stream=stream, x_init=x_init,
                             difficulty=self._last_iter if self.launch_hint else None)   # linearised about the previous plan (main.m:121-125)
         if self.warm_start:
             self._slack = out["slack"]
@@ -203,7 +317,14 @@ class ClosedLoop:
         P = lambda t: C.c_void_p(t.data_ptr())
         check(lib().fsaempc_cl_accept_batch_device(self.model, self.N, self.B, P(out["x_opt"]), P(out["u_opt"]), P(out["exitflag"]), P(self.x_opt), P(self.u_opt),
                                                    self._stream(stream)), "fsaempc_cl_accept_batch_device")
-        self.plant(None, stream)
+        if self.u_hist is not None:   # the newest plan into its slot, the plant on the one accepted `delay` periods ago
+            d = self.latency.delay
+            self.x_hist[self.steps % (d + 1)].copy_(self.x_opt)
+            self.u_hist[self.steps % (d + 1)].copy_(self.u_opt)
+            self.plant_plan = self.x_hist[(self.steps - d) % (d + 1)]
+            self.plant(None, stream, self.plant_plan)
+        else:
+            self.plant(None, stream)
         if self.metrics is not None:
             check(lib().fsaempc_cl_metrics_batch_device_c(self.model, self.N, C.c_double(self.dt), C.c_double(self.slack_tol), self.B,
                                                           self.mpc.params.ref() if self.mpc.params is not None else None,
@@ -245,16 +366,17 @@ def monte_carlo_carts(track, B, seed, lap=False):
 
 
 def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
-                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1):
+                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1, latency=None):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
     reference: None (the live ramp) or a Plan the cars track (ClosedLoop).  metrics: ClosedLoop(metrics=True); cl.report() afterwards.
-    corridor: None or a Corridor (ClosedLoop).  laps: ClosedLoop(laps=...); cl.lap_times afterwards.
+    corridor: None or a Corridor (ClosedLoop).  laps: ClosedLoop(laps=...); cl.lap_times afterwards.  latency: None or a Latency (ClosedLoop).
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
     import torch
     cart0, s_init = monte_carlo_carts(track, B, seed)
     cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
-                    params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics, corridor=corridor, laps=laps)
+                    params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics, corridor=corridor, laps=laps,
+                    latency=latency)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

@@ -19,6 +19,7 @@
 #include "ltv_build.h"
 #include "reference.h"
 #include "plant.h"
+#include "cl_latency.h"
 #include "planner.h"
 #include "raceline.h"
 #include "minlap.h"
@@ -1102,6 +1103,52 @@ int fsaempc_cl_lap_summary(const double* lap_times_host, int batch, int laps, do
     out[4 * l] = cnt; out[4 * l + 1] = cnt > 0 ? sum / cnt : NAN; out[4 * l + 2] = lo; out[4 * l + 3] = hi;
   }
   return 0;
+}
+
+/* ---- closed loop: measurement noise, plan latency and delay compensation ---- */
+static int cl_draw_check(long long id0, long long step) {
+  if (id0 < 0) return fail(FSAEMPC_ERR_ARG, "id0 must be >= 0");
+  if (step < 0 || step >= (1LL << 32)) return fail(FSAEMPC_ERR_ARG, "step must be 0 .. 2^32 - 1");
+  return 0;
+}
+
+int fsaempc_cl_noise_batch_device(int nx, int batch, unsigned long long seed, long long id0, long long step, double* z, void* stream) {
+  if (nx != 5 && nx != 7) return fail(FSAEMPC_ERR_ARG, "nx must be 5 or 7");
+  if (batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (int rc = cl_draw_check(id0, step)) return rc;
+  if (!z) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (batch == 0) return 0;
+  hipError_t e = cl_noise_launch(nx, batch, seed, (unsigned long long)id0, (unsigned long long)step, z, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "cl_noise_launch");
+  return 0;
+}
+
+int fsaempc_cl_observe_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const fsaempc_cl_latency* lat, long long step, const double* x0_true, const int* finished,
+                                    const double* u_hist, double* x0_obs, double* x0_mpc, void* stream) {
+  if (int rc = ltv_check(desc, sp)) return rc;
+  if (!lat) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (lat->delay < 0 || lat->delay > FSAEMPC_CL_MAX_DELAY) return fail(FSAEMPC_ERR_ARG, "delay must be 0 .. FSAEMPC_CL_MAX_DELAY");
+  if (lat->compensate != 0 && lat->compensate != 1) return fail(FSAEMPC_ERR_ARG, "compensate must be 0 or 1");
+  if (int rc = cl_draw_check(lat->id0, step)) return rc;
+  if (lat->delay > 0 && !u_hist) return fail(FSAEMPC_ERR_ARG, "null argument (u_hist is required with delay > 0)");
+  if (!x0_true || !x0_obs || !x0_mpc) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (desc->batch == 0) return 0;
+  ClObserveParams P;
+  P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.batch = desc->batch; P.integ = ltv_integ(desc);
+  P.delay = lat->delay; P.compensate = lat->compensate; P.sigma_per_instance = lat->sigma_per_instance ? 1 : 0; P.dt = desc->dt;
+  P.seed = lat->seed; P.id0 = (unsigned long long)lat->id0; P.step = (unsigned long long)step;
+  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP;
+  P.sigma = lat->sigma; P.x0_true = x0_true; P.finished = finished; P.u_hist = u_hist; P.x0_obs = x0_obs; P.x0_mpc = x0_mpc;
+  hipError_t e = cl_observe_launch(P, (hipStream_t)stream, par_values(par), par_stride(par));
+  if (e != hipSuccess) return hipfail(e, "cl_observe_launch");
+  return 0;
+}
+
+// Host.
+int fsaempc_cl_history_slot(int delay, long long step, int lag) {
+  if (delay < 0 || delay > FSAEMPC_CL_MAX_DELAY || step < 0 || lag < 0 || lag > delay) return -1;
+  return cll_slot(delay, step, lag);
 }
 
 /* ---- s-domain plans ---- */

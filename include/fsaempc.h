@@ -955,6 +955,59 @@ int fsaempc_cl_lap_gate_batch_device(int nx, int N, double dt, double L, int lap
  * batch < 0, laps outside 1 .. FSAEMPC_MAX_LAPS. */
 int fsaempc_cl_lap_summary(const double* lap_times_host, int batch, int laps, double* out);
 
+/* ---- closed loop: measurement noise, plan latency and delay compensation --------------
+ * The loop above reads the exact state and computes in zero time: the plan solved from the state at t_k steers the plant during
+ * [t_k, t_k + dt).  These entries replace nothing in main.m (like the lap gate); they add the two standard imperfections and the
+ * standard remedy for the second.  Opt-in: a loop that never calls them is the ideal loop.
+ *   observation   x0_obs[i] = x0_true[i] + sigma[i] z_i(seed, id, step) for every state component with sigma[i] > 0; a component with
+ *                 sigma[i] == 0 is copied, not added to (keeps -0.0; "noise off" is exact).  A negative or non-finite sigma[i] lives
+ *                 on the device and cannot be seen before the launch: it is treated as 0 (copy).
+ *   draws         counter based, so a car's noise depends on (seed, id, step, i) only, never on the batch it sits in: Philox4x32-10
+ *                 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key (seed & 0xffffffff, seed >> 32),
+ *                 counter (step, j, id & 0xffffffff, id >> 32) with id = id0 + b; call j = 0 serves components 0 .. 3, call j = 1
+ *                 components 4 .. 6.  Words (w0, w1, w2, w3) to normals: u1 = (w0 + 0.5) 2^-32, u2 = (w1 + 0.5) 2^-32,
+ *                 r = sqrt(-2 ln u1), z0 = r cos(2 pi u2), z1 = r sin(2 pi u2); (w2, w3) give (z2, z3) the same way.
+ *   latency       the plan accepted in period k reaches the plant `delay` periods later: the caller keeps delay + 1 plans, writes
+ *                 the plan of period k to slot fsaempc_cl_history_slot(delay, k, 0) after the solve and hands the plant the slot
+ *                 fsaempc_cl_history_slot(delay, k, delay); for k < delay that slot holds what the history was filled with.
+ *   compensation  x0_mpc = x0_obs rolled over the `delay` periods that pass before this period's plan takes effect:
+ *                 x <- Psi(x, u_hist[slot(delay, k, delay - j)][b][stage 1]) for j = 0 .. delay - 1, Psi the rollout step of the NLP
+ *                 (fsaempc_nlp_build_qp_batch_device) with desc->integrator and the controller's block `par`.  If an input read or
+ *                 a component of the result is not finite, or the block cannot describe a car, x0_mpc[b] = x0_obs[b] bit for bit.
+ *                 With compensate == 0 or delay == 0, x0_mpc = x0_obs bit for bit.
+ * A car with finished[b] != 0 keeps its state in both outputs.  sigma is in the model's state layout: kinematic
+ * [s, n, mu, v, delta], dynamic [s, n, mu, x_d, y_d, theta_d, delta]. */
+#define FSAEMPC_CL_MAX_DELAY 4
+typedef struct {
+  int delay;                 /* whole periods, 0 .. FSAEMPC_CL_MAX_DELAY */
+  int compensate;            /* 0 / 1 */
+  const double* sigma;       /* device; nx values, or batch * nx (sigma_per_instance); NULL: no noise */
+  int sigma_per_instance;
+  unsigned long long seed;
+  long long id0;             /* id of instance 0 (a shard's first global id) */
+} fsaempc_cl_latency;
+
+/* z (batch x nx, instance-major): the nx standard normals of (seed, id0 + b, step), the draws the observation uses.
+ * FSAEMPC_ERR_ARG before any launch: nx not 5 or 7, batch < 0, id0 < 0, step < 0 or >= 2^32, z NULL.  batch == 0 succeeds
+ * without a launch. */
+int fsaempc_cl_noise_batch_device(int nx, int batch, unsigned long long seed, long long id0, long long step,
+                                  double* z /* batch x nx */, void* stream);
+/* One call per MPC period, after the pre-step (and the lap gate) and before the step, on the same stream: observation and
+ * prediction as above, x0_obs and x0_mpc (batch x nx each) written for every car.  The step then takes x0_mpc, and a reference
+ * regenerated from it (fsaempc_plan_reference_batch_device with s0 = x0_mpc[:, 0], or fsaempc_reference_live_batch_device); the
+ * metrics entry keeps reading x0_true.  finished is optional (NULL: every car drives).  u_hist is read only with compensate and
+ * delay >= 1.  x0_obs and x0_mpc must not overlap x0_true or each other.
+ * FSAEMPC_ERR_ARG before any launch: what the LTV entries refuse in desc and sp, lat NULL, delay outside
+ * 0 .. FSAEMPC_CL_MAX_DELAY, compensate not 0 or 1, step < 0 or >= 2^32, id0 < 0, u_hist NULL with delay > 0, x0_true, x0_obs or
+ * x0_mpc NULL.  desc->batch == 0 succeeds without a launch. */
+int fsaempc_cl_observe_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const fsaempc_cl_latency* lat, long long step, const double* x0_true, const int* finished,
+                                    const double* u_hist /* (delay+1) x batch x N x 2, NULL iff delay == 0 */,
+                                    double* x0_obs, double* x0_mpc, void* stream);
+/* Host: the slot of plan_{step - lag} in a history of delay + 1 plans, (step - lag) mod (delay + 1), lag 0 .. delay.
+ * Returns -1 for delay outside 0 .. FSAEMPC_CL_MAX_DELAY, step < 0 or lag outside 0 .. delay. */
+int fsaempc_cl_history_slot(int delay, long long step, int lag);
+
 /* ---- track pipeline (host side) --------------------------------------------------- */
 
 /* Spline table of a track as main.m:11-17 produces it: M arc-length segments, xP / yP = M x 4 Bezier control points per axis

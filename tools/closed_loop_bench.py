@@ -21,9 +21,13 @@ defaults to 1000 (main.m:62): a finished car's STEPS * dt is then a lap time.
 --laps K: every car drives K consecutive laps (ClosedLoop(laps=K), DESIGN.md 6m: the lap gate carries it over the line and times the
 crossing to a fraction of dt); with --lap the step cap defaults to 1000 K; the per-lap summary (cars that completed the lap, mean, min and
 max of its time) joins the JSON line as "lap_summary".
+--delay D [--compensate] [--noise s1,...,snx [--noise-seed S]]: the imperfect loop (fsaempc.Latency): a plan reaches the plant
+D periods after the state it was solved from; --compensate solves from that state predicted over the D periods; --noise adds
+state-estimate noise with these standard deviations (the model's state layout: 5 values kinematic, 7 dynamic).  Echoed as "latency".
 usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--track fss2019]
                                   [--plan | --raceline | --minlap K [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap] [--laps K]
-                                  [--corridor FILE.npz | --cones FILE [--car-half-width W]] [--line-rows points|cells]"""
+                                  [--corridor FILE.npz | --cones FILE [--car-half-width W]] [--line-rows points|cells]
+                                  [--delay D [--compensate]] [--noise s1,...,snx [--noise-seed S]]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -59,7 +63,22 @@ def main():
     ap.add_argument("--cone-cells", type=int, default=500, help="with --cones: cells of the corridor's tables (N_w)")
     ap.add_argument("--line-rows", default="points", choices=["points", "cells"],
                     help="with --raceline and --corridor or --cones: the line's corridor as boxes on the control points or as one row per cell")
+    ap.add_argument("--delay", type=int, default=0, metavar="D", help="whole periods between the state a plan is solved from and the plant following it (Latency)")
+    ap.add_argument("--compensate", action="store_true", help="with --delay >= 1: solve from the observed state predicted over the delay")
+    ap.add_argument("--noise", default=None, metavar="s1,...,snx", help="standard deviations of the state-estimate noise, one per state component")
+    ap.add_argument("--noise-seed", type=int, default=0, metavar="S", help="with --noise: seed of the counter-based generator")
     a = ap.parse_args()
+    sigma = None
+    if a.noise is not None:
+        try:
+            sigma = [float(v) for v in a.noise.split(",")]
+        except ValueError:
+            ap.error("--noise takes comma-separated numbers")
+    try:
+        lat = fm.Latency(delay=a.delay, compensate=a.compensate, sigma=sigma, seed=a.noise_seed)
+        lat.check_batch(5 if a.model == "kinematic" else 7, a.batch)
+    except ValueError as e:
+        ap.error(str(e))
     if a.corridor is not None and a.cones is not None:
         ap.error("--cones and --corridor exclude each other")
     if a.line_rows == "cells" and not (a.raceline and (a.corridor is not None or a.cones is not None)):
@@ -97,7 +116,7 @@ def main():
         plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip, corridor=cor, rows=a.line_rows)
     if a.minlap is not None:
         plan = fm.Plan.minlap(model, tr, N_s=a.cells, N_c=a.points, iters=a.minlap, margin=a.margin, grip=a.grip, corridor=cor)
-    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor)          # warm-up (allocations, code load)
+    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor, latency=lat)          # warm-up (allocations, code load)
     n_max = float(fm.default_params(model)[fm.PARAM_INDEX["N_MAX"]])
     opts = fm.default_opts(max_iter=a.max_iter)
     t0 = time.perf_counter()
@@ -105,7 +124,7 @@ def main():
     # every car while it drives
     cart0, s_init = fm.monte_carlo_carts(tr, a.batch, a.seed, lap=a.lap)
     cl = fm.ClosedLoop(model, a.horizon, 0.05, tr, cart0, options=opts, warm_start=a.warm, launch_hint=not a.no_launch_hint, reference=plan,
-                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps)
+                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps, latency=lat)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]
     fl_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
@@ -147,7 +166,8 @@ def main():
         "config": {"workload": "BASELINE configs[3] share of one GPU: %d cars on %s, %d receding-horizon steps, every step one batch of QPs "
                                "(frame transform + reference + linearise/condense/solve + PID/plant, device-resident loop, no per-step read-back; "
                                "wall time includes the allocation of the run)" % (a.batch, a.track, a.steps),
-                   "track": a.track, "corridor": a.corridor, **({"cones": cone_info} if cone_info is not None else {}), "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
+                   "track": a.track, "corridor": a.corridor,
+                   "latency": {"delay": a.delay, "compensate": bool(a.compensate), "noise": sigma, "noise_seed": a.noise_seed}, **({"cones": cone_info} if cone_info is not None else {}), "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
                    # (a mean over an empty set is NaN in the report: null in the JSON line)
                    **({"lap_report": {k: (None if v != v else v) for k, v in cl.report().summary().items()}, "slack_tol": a.slack_tol} if a.report else {}),
                    **({"laps": a.laps, "lap_summary": [{"lap": i + 1, "cars": int(r[0]), "mean_s": None if r[1] != r[1] else float(r[1]),
