@@ -35,6 +35,7 @@ EXPORTS = [
     "fsaempc_corridor_from_cones_device", "fsaempc_track_cones_from_csv", "fsaempc_track_cones_free",
     "fsaempc_plan_line_lapgrad_batch_device", "fsaempc_plan_minlap_workspace_bytes", "fsaempc_plan_minlap_batch_device",
     "fsaempc_cl_noise_batch_device", "fsaempc_cl_observe_batch_device", "fsaempc_cl_history_slot",
+    "fsaempc_cl_estimate_batch_device",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -111,6 +112,10 @@ class LtvParams(C.Structure):
 class ClLatency(C.Structure):   # fsaempc_cl_latency
     _fields_ = [("delay", C.c_int), ("compensate", C.c_int), ("sigma", C.c_void_p), ("sigma_per_instance", C.c_int),
                 ("seed", C.c_ulonglong), ("id0", C.c_longlong)]
+
+
+class ClEstimator(C.Structure):   # fsaempc_cl_estimator
+    _fields_ = [("q", C.c_void_p), ("q_per_instance", C.c_int), ("r", C.c_void_p), ("r_per_instance", C.c_int), ("p0", C.c_void_p), ("L", C.c_double)]
 
 
 class LtvBlocking(C.Structure):
@@ -309,6 +314,8 @@ def lib():
         L.fsaempc_cl_noise_batch_device.argtypes = [C.c_int, C.c_int, C.c_ulonglong, ll, ll, vp, vp]
         L.fsaempc_cl_observe_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(ClLatency), ll] + [vp] * 6
         L.fsaempc_cl_history_slot.argtypes = [C.c_int, ll, C.c_int]
+        L.fsaempc_cl_estimate_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(ClEstimator),
+                                                       vp, vp, vp, ll] + [vp] * 10
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p
         L.fsaempc_track_from_csv.argtypes = [C.c_char_p, C.c_int, C.POINTER(TrackTable)]

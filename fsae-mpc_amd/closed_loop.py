@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CL_MAX_DELAY, LAP_STATE_INDEX, METRIC_INDEX, NLAPSTATE, NMETRIC, NREPORT, REPORT_INDEX, ClLatency, ParamBlock, Spline, check,
+from ._lib import (CL_MAX_DELAY, LAP_STATE_INDEX, METRIC_INDEX, NLAPSTATE, NMETRIC, NREPORT, REPORT_INDEX, ClEstimator, ClLatency, ParamBlock, Spline, check,
                    check_blocking, check_laps, lib)
 from .ltvmpc import LtvBatch, dims
 from .corridor import check_corridor
@@ -114,6 +114,71 @@ def check_latency(latency, nx, B):
     return latency
 
 
+class Estimator:
+    """The state estimator of a closed loop: one extended Kalman filter per car between the observation and the MPC
+    step, validated here without a library call.  All variances are in the model's state layout.  q: process variances per MPC
+    period, (nx,) for the batch or (B, nx) per car, finite and >= 0.  r: measurement variances, (nx,) or (B, nx), each finite and
+    >= 0 or +inf ("this component is not measured"); None = the squares of the loop's Latency.sigma.  p0: initial variances, (nx,),
+    finite and > 0; None = r where r is finite and > 0, else 1.0 (needs an r for the batch)."""
+
+    def __init__(self, q, r=None, p0=None):
+        def array(v, name):
+            try:
+                a = np.array(v, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("%s must be an array of numbers" % name)
+            return a
+        q = array(q, "q")
+        if q.ndim not in (1, 2) or q.shape[-1] not in (5, 7):
+            raise ValueError("q must be (nx,) or (B, nx), got %s" % (q.shape,))
+        if not np.isfinite(q).all() or (q < 0).any():
+            raise ValueError("q must be finite and >= 0")
+        if r is not None:
+            r = array(r, "r")
+            if r.ndim not in (1, 2) or r.shape[-1] != q.shape[-1]:
+                raise ValueError("r must be (nx,) or (B, nx) with the nx of q, got %s" % (r.shape,))
+            if np.isnan(r).any() or (r < 0).any():
+                raise ValueError("r must be >= 0 (+inf: the component is not measured)")
+        if p0 is not None:
+            p0 = array(p0, "p0")
+            if p0.shape != (q.shape[-1],):
+                raise ValueError("p0 must be (nx,), got %s" % (p0.shape,))
+            if not np.isfinite(p0).all() or (p0 <= 0).any():
+                raise ValueError("p0 must be finite and > 0")
+        elif r is not None and r.ndim != 1:
+            raise ValueError("p0 must be given with a per-car r")
+        self.q, self.r, self.p0 = q, r, p0
+
+    def resolve(self, latency, nx, B, laps=1):
+        """(q, r, p0) for a loop of B cars with nx states: shapes checked, r and p0 filled in from their defaults."""
+        if self.q.shape not in ((nx,), (B, nx)):
+            raise ValueError("q must be (nx = %d,) or (B = %d, %d), got %s" % (nx, B, nx, self.q.shape))
+        r = self.r
+        if r is None:
+            if latency is None or latency.sigma is None:
+                raise ValueError("Estimator(r=None) takes the variances of a Latency with sigma")
+            r = latency.sigma ** 2
+        if r.shape not in ((nx,), (B, nx)):
+            raise ValueError("r must be (nx = %d,) or (B = %d, %d), got %s" % (nx, B, nx, r.shape))
+        p0 = self.p0
+        if p0 is None:
+            if r.ndim != 1:
+                raise ValueError("p0 must be given with a per-car r")
+            p0 = np.where(np.isfinite(r) & (r > 0), r, 1.0)
+        if laps > 1 and np.isinf(r[..., 0]).any():
+            raise ValueError("laps > 1 needs a measured arc length (r[0] finite): the estimate is re-based on it at the line")
+        return self.q, r, p0
+
+
+def check_estimator(estimator, latency, nx, B, laps=1):
+    """Validates ClosedLoop's estimator argument (no library call): None, or an Estimator resolved to (q, r, p0)."""
+    if estimator is None:
+        return None
+    if not isinstance(estimator, Estimator):
+        raise ValueError("estimator must be None or an Estimator")
+    return estimator.resolve(latency, nx, B, laps)
+
+
 def cl_noise(nx, B, seed, id0, step, device="cuda:0"):
     """The (B, nx) standard normals the observation of period `step` draws for cars id0 .. id0 + B - 1
     (fsaempc_cl_noise_batch_device), a device tensor."""
@@ -133,7 +198,7 @@ class ClosedLoop:
 
     def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
                  params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6, corridor=None, laps=1,
-                 latency=None):
+                 latency=None, estimator=None):
         """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
         None = the same as params (both None: the reference's constants compiled into the kernels).  blocking: block lengths of the
         controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2).  reference: None = the live
@@ -150,7 +215,13 @@ class ClosedLoop:
         launches without the argument.  Otherwise step() observes the state after pre() and the lap gate (self.x0_obs = x0 + noise),
         predicts it over the delay if asked to (self.x0_mpc), regenerates x_ref from x0_mpc, solves from x0_mpc, and the plant follows
         the plan accepted `delay` periods ago (self.plant_plan, a view of self.x_hist (delay + 1, B, N, nx); self.u_hist likewise).
-        self.x0 stays the true state (the gate and the metrics read it); self.x_opt / self.u_opt stay the newest plan."""
+        self.x0 stays the true state (the gate and the metrics read it); self.x_opt / self.u_opt stay the newest plan.
+        estimator: None or an Estimator.  None launches what the loop launches without the argument.  Otherwise step()
+        observes with the noise alone (self.x0_obs; without a latency the measurement is x0), filters it (self.x0_est, with the carried
+        self.est_x, self.est_P (B, nx, nx), self.est_count (B, 2); self.est_innov, self.est_nis and self.est_resets of the period), predicts
+        x0_est over the delay if the latency compensates (self.x0_mpc; otherwise self.x0_mpc is self.x0_est), regenerates x_ref from the
+        state the solve reads and solves from it.  The filter's input is the first input of the plan the plant followed in the period
+        just past."""
         if not (float(slack_tol) >= 0):
             raise ValueError("slack_tol must be >= 0")
         self.laps = check_laps(laps)   # (before the library is touched)
@@ -164,6 +235,8 @@ class ClosedLoop:
         self.reference = reference
         check_corridor(corridor, np.asarray(cart0).size // 7, device)   # (before the library is touched)
         self.latency = check_latency(latency, 5 if model == 0 else 7, np.asarray(cart0).size // 7)   # (likewise)
+        self._est_arrays = check_estimator(estimator, latency, 5 if model == 0 else 7, np.asarray(cart0).size // 7, self.laps)   # (likewise)
+        self.estimator = estimator
         if self.latency is not None and not self.latency.engaged:
             self.latency = None
         import torch
@@ -209,6 +282,27 @@ class ClosedLoop:
             if lat.delay > 0:   # the history is filled from x_opt / u_opt at the first step(): callers edit the initial guess before it
                 self.x_hist = torch.empty((lat.delay + 1, self.B, N, self.nx), dtype=torch.float64, device=self.device)
                 self.u_hist = torch.empty((lat.delay + 1, self.B, N, 2), dtype=torch.float64, device=self.device)
+        self.x0_est = self.est_x = self.est_P = self.est_count = self.est_innov = self.est_nis = self.est_x_start = None
+        if self.estimator is not None:
+            q, r, p0 = self._est_arrays
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
+            self._est_q, self._est_r, self._est_p0 = dev(q), dev(r), dev(p0)
+            self._est = ClEstimator(C.c_void_p(self._est_q.data_ptr()), 1 if q.ndim == 2 else 0, C.c_void_p(self._est_r.data_ptr()), 1 if r.ndim == 2 else 0,
+                                    C.c_void_p(self._est_p0.data_ptr()), self.track.L if self.laps > 1 else 0.0)
+            self.x0_est, self.est_x, self.est_innov, self.est_x_start = f64(self.B, self.nx), f64(self.B, self.nx), f64(self.B, self.nx), f64(self.B, self.nx)
+            self.est_P, self.est_nis = f64(self.B, self.nx, self.nx), f64(self.B)
+            self.est_count = torch.zeros((self.B, 2), dtype=torch.int32, device=self.device)
+            if self.latency is None:
+                self._s0_mpc = torch.empty(self.B, dtype=torch.float64, device=self.device)
+                self.x0_mpc = self.x0_est
+            else:   # the two existing observe calls of an engaged period: noise alone (delay 0), then the predictor alone (no sigma)
+                lat = self.latency
+                self._obs_scratch = torch.empty_like(self.x0)
+                self._lat_noise = ClLatency(0, 0, self._lat.sigma, self._lat.sigma_per_instance, lat.seed, lat.id0)
+                self._lat_pred = ClLatency(lat.delay, int(lat.compensate), None, 0, lat.seed, lat.id0)
+                if not lat.compensate:
+                    self.x0_mpc = self.x0_est
         self.metrics = torch.zeros((self.B, NMETRIC), dtype=torch.float64, device=self.device) if metrics else None
         self.lap_state = self.lap_times = self.lap_records = None   # laps == 1: nothing is allocated unless lap_gate() is called
         if self.laps > 1:
@@ -272,20 +366,64 @@ class ClosedLoop:
     def observe(self, stream=None):
         """Observation and prediction of this period on what pre() and the lap gate left in self.x0 (fsaempc_cl_observe_batch_device),
         then x_ref regenerated from x0_mpc by the reference the loop runs on."""
-        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._fill_history()
+        self._observe_call(self._lat, self.x0, self.x0_obs, self.x0_mpc, stream)
+        self._reference_from(self.x0_mpc, stream)
+
+    def _fill_history(self):
         if self.u_hist is not None and self.steps == 0:
             self.x_hist.copy_(self.x_opt.unsqueeze(0).expand_as(self.x_hist))
             self.u_hist.copy_(self.u_opt.unsqueeze(0).expand_as(self.u_hist))
+
+    def _observe_call(self, lat, x0_true, x0_obs, x0_mpc, stream):
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         check(lib().fsaempc_cl_observe_batch_device(C.byref(self.mpc.desc), C.byref(self.mpc.sp), self.mpc.params.ref() if self.mpc.params is not None else None,
-                                                    C.byref(self._lat), self.steps, P(self.x0), P(self.finished), P(self.u_hist), P(self.x0_obs),
-                                                    P(self.x0_mpc), self._stream(stream)), "fsaempc_cl_observe_batch_device")
+                                                    C.byref(lat), self.steps, P(x0_true), P(self.finished), P(self.u_hist), P(x0_obs),
+                                                    P(x0_mpc), self._stream(stream)), "fsaempc_cl_observe_batch_device")
+
+    def _reference_from(self, x0_mpc, stream):
+        """x_ref regenerated from the state the solve reads, by the reference the loop runs on."""
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         if self.reference is not None:
-            self._s0_mpc.copy_(self.x0_mpc[:, 0])
+            self._s0_mpc.copy_(x0_mpc[:, 0])
             check(lib().fsaempc_plan_reference_batch_device(self.model, self.reference.ref(), P(self._s0_mpc), C.c_double(self.dt), self.N, self.B,
                                                             P(self.x_ref), self._stream(stream)), "fsaempc_plan_reference_batch_device")
         else:
-            check(lib().fsaempc_reference_live_batch_device(self.nx, self.N, C.c_double(self.dt), C.c_double(self.target_vel), self.B, P(self.x0_mpc),
+            check(lib().fsaempc_reference_live_batch_device(self.nx, self.N, C.c_double(self.dt), C.c_double(self.target_vel), self.B, P(x0_mpc),
                                                             P(self.x_ref), self._stream(stream)), "fsaempc_reference_live_batch_device")
+
+    @property
+    def est_resets(self):
+        """Re-initialisations of every car's filter so far, (B,) int32 on the device (None without an estimator)."""
+        return self.est_count[:, 1] if self.est_count is not None else None
+
+    def prev_input(self):
+        """The (B, N, 2) plan whose first input the plant followed in the period just past: slot (k - 1 - d) mod (d + 1) of the history, u_opt
+        (still plan k - 1 before the solve) with d = 0."""
+        if self.u_hist is None:
+            return self.u_opt
+        d = self.latency.delay
+        return self.u_hist[(self.steps - 1 - d) % (d + 1)]
+
+    def estimate(self, stream=None):
+        """Observation, filter and prediction of this period on what pre() and the lap gate left in self.x0, then x_ref
+        regenerated from the state the solve reads, which is returned."""
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._fill_history()
+        z = self.x0
+        if self.latency is not None:
+            self._observe_call(self._lat_noise, self.x0, self.x0_obs, self._obs_scratch, stream)
+            z = self.x0_obs
+        if self.steps == 0:
+            self.est_x_start.copy_(z)
+        check(lib().fsaempc_cl_estimate_batch_device(C.byref(self.mpc.desc), C.byref(self.mpc.sp), self.mpc.params.ref() if self.mpc.params is not None else None,
+                                                     C.byref(self._est), P(z), P(self.est_x_start), P(self.prev_input()), 2 * self.N, P(self.finished),
+                                                     P(self.est_x), P(self.est_P), P(self.est_count), P(self.x0_est), P(self.est_innov), P(self.est_nis),
+                                                     None, None, self._stream(stream)), "fsaempc_cl_estimate_batch_device")
+        if self.latency is not None and self.latency.compensate:
+            self._observe_call(self._lat_pred, self.x0_est, self._obs_scratch, self.x0_mpc, stream)
+        self._reference_from(self.x0_mpc, stream)
+        return self.x0_mpc
 
     def step(self, stream=None):
         torch = self.torch
@@ -306,7 +444,9 @@ class ClosedLoop:
             if self._slack is not None:
                 x_init[:, nu:].copy_(self._slack)
         x0 = self.x0
-        if self.latency is not None:
+        if self.estimator is not None:
+            x0 = self.estimate(stream)
+        elif self.latency is not None:
             self.observe(stream)
             x0 = self.x0_mpc
         out = self.mpc.step(x0, self.x_ref, self.x_opt, self.u_opt, stream=stream, x_init=x_init,
@@ -366,17 +506,17 @@ def monte_carlo_carts(track, B, seed, lap=False):
 
 
 def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
-                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1, latency=None):
+                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1, latency=None, estimator=None):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
     reference: None (the live ramp) or a Plan the cars track (ClosedLoop).  metrics: ClosedLoop(metrics=True); cl.report() afterwards.
-    corridor: None or a Corridor (ClosedLoop).  laps: ClosedLoop(laps=...); cl.lap_times afterwards.  latency: None or a Latency (ClosedLoop).
+    corridor: None or a Corridor (ClosedLoop).  laps: ClosedLoop(laps=...); cl.lap_times afterwards.  latency: None or a Latency (ClosedLoop).  estimator: None or an Estimator (ClosedLoop).
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
     import torch
     cart0, s_init = monte_carlo_carts(track, B, seed)
     cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
                     params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics, corridor=corridor, laps=laps,
-                    latency=latency)
+                    latency=latency, estimator=estimator)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

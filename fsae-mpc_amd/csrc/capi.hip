@@ -20,6 +20,7 @@
 #include "reference.h"
 #include "plant.h"
 #include "cl_latency.h"
+#include "cl_estimator.h"
 #include "planner.h"
 #include "raceline.h"
 #include "minlap.h"
@@ -1149,6 +1150,50 @@ int fsaempc_cl_observe_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_
 int fsaempc_cl_history_slot(int delay, long long step, int lag) {
   if (delay < 0 || delay > FSAEMPC_CL_MAX_DELAY || step < 0 || lag < 0 || lag > delay) return -1;
   return cll_slot(delay, step, lag);
+}
+
+/* ---- closed loop: the state estimator ---- */
+namespace { struct ByteRange { const char* name; const void* p; size_t bytes; }; }
+static bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
+  if (!a.p || !b.p || a.bytes == 0 || b.bytes == 0) return false;
+  const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+  return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+
+int fsaempc_cl_estimate_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                     const fsaempc_cl_estimator* est, const double* z, const double* x_start, const double* u_prev,
+                                     long long u_stride, const int* finished, double* est_x, double* est_P, int* est_count, double* x0_est,
+                                     double* innov, double* nis, double* F_out, double* x_prior, void* stream) {
+  if (int rc = ltv_check(desc, sp)) return rc;
+  if (!est || !est->q || !est->r || !est->p0) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (!(est->L >= 0 && est->L < INFINITY)) return fail(FSAEMPC_ERR_ARG, "L must be finite and >= 0");
+  if (u_stride < 2) return fail(FSAEMPC_ERR_ARG, "u_stride must be >= 2");
+  if (!z || !x_start || !u_prev || !est_x || !est_P || !est_count || !x0_est || !innov || !nis) return fail(FSAEMPC_ERR_ARG, "null argument");
+  const size_t B = (size_t)desc->batch, nx = (size_t)fsaempc_ltv_nx(desc->model), d = sizeof(double);
+  const ByteRange out[] = {{"est_x", est_x, B * nx * d}, {"est_P", est_P, B * nx * nx * d}, {"est_count", est_count, B * 2 * sizeof(int)},
+                           {"x0_est", x0_est, B * nx * d}, {"innov", innov, B * nx * d}, {"nis", nis, B * d},
+                           {"F_out", F_out, B * nx * nx * d}, {"x_prior", x_prior, B * nx * d}};
+  const ByteRange in[] = {{"z", z, B * nx * d}, {"x_start", x_start, B * nx * d},
+                          {"u_prev", u_prev, B ? ((B - 1) * (size_t)u_stride + 2) * d : 0}, {"finished", finished, B * sizeof(int)},
+                          {"q", est->q, (est->q_per_instance ? B : 1) * nx * d}, {"r", est->r, (est->r_per_instance ? B : 1) * nx * d},
+                          {"p0", est->p0, nx * d}};
+  const int n_out = (int)(sizeof(out) / sizeof(out[0])), n_in = (int)(sizeof(in) / sizeof(in[0]));
+  for (int i = 0; i < n_out; ++i) {
+    for (int k = i + 1; k < n_out; ++k)
+      if (ranges_overlap(out[i], out[k])) return fail(FSAEMPC_ERR_ARG, "overlapping outputs");
+    for (int k = 0; k < n_in; ++k)
+      if (ranges_overlap(out[i], in[k])) return fail(FSAEMPC_ERR_ARG, "an output overlaps an input");
+  }
+  if (desc->batch == 0) return 0;
+  ClEstimateParams P;
+  P.nx = (int)nx; P.batch = desc->batch; P.integ = ltv_integ(desc); P.q_per_instance = est->q_per_instance ? 1 : 0;
+  P.r_per_instance = est->r_per_instance ? 1 : 0; P.dt = desc->dt; P.L = est->L;
+  P.spM = sp->M; P.spdl = sp->dl; P.xP = sp->xP; P.yP = sp->yP;
+  P.q = est->q; P.r = est->r; P.p0 = est->p0; P.z = z; P.x_start = x_start; P.u_prev = u_prev; P.u_stride = u_stride; P.finished = finished;
+  P.est_x = est_x; P.est_P = est_P; P.est_count = est_count; P.x0_est = x0_est; P.innov = innov; P.nis = nis; P.F_out = F_out; P.x_prior = x_prior;
+  hipError_t e = cl_estimate_launch(P, (hipStream_t)stream, par_values(par), par_stride(par));
+  if (e != hipSuccess) return hipfail(e, "cl_estimate_launch");
+  return 0;
 }
 
 /* ---- s-domain plans ---- */

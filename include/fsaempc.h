@@ -1008,6 +1008,49 @@ int fsaempc_cl_observe_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_
  * Returns -1 for delay outside 0 .. FSAEMPC_CL_MAX_DELAY, step < 0 or lag outside 0 .. delay. */
 int fsaempc_cl_history_slot(int delay, long long step, int lag);
 
+/* ---- closed loop: the state estimator -------------------------------------------------
+ * What a driverless car puts between its sensors and its MPC: one extended Kalman filter per car, run once per MPC period between
+ * the observation and the step, on the stream, with no host read.  Opt-in like the entries above.  Per car the caller keeps the
+ * estimate est_x (nx), its covariance est_P (nx x nx, row-major, symmetric) and two counters est_count[b] = {periods since the last
+ * (re-)initialisation, re-initialisations}, zeroed before the first call.  The model is the controller's: Psi is the rollout step of
+ * fsaempc_nlp_build_qp_batch_device with desc->integrator and the block `par`, F = dPsi/dx its exact Jacobian (forward mode through
+ * the same code, kappa'(s) of the spline table included).  Q = diag(q) per period, R = diag(r), P0 = diag(p0), all in the model's
+ * state layout (kinematic [s, n, mu, v, delta], dynamic [s, n, mu, x_d, y_d, theta_d, delta]); q and r for the batch or per car.
+ * Component i is measured iff r[i] is finite and >= 0; r[i] = +Inf says "not measured" (a NaN or a negative r[i] lives on the device
+ * and cannot be seen before the launch: it is treated as not measured).  Per period and car, in this order:
+ *   1 finished    finished[b] != 0: x0_est[b] = z[b] bit for bit, innov = 0, nis = 0 (F_out = I, x_prior = z); est_x, est_P, est_count
+ *                 are not written.
+ *   2 first       est_count[b][0] == 0: the prior is x- = x_start[b], P- = diag(p0); no prediction, F_out = I.
+ *   3 prediction  otherwise: x- = Psi(est_x, u), F = dPsi/dx(est_x, u), M = (F P) F', P- = (M + M') / 2 + diag(q) (exactly symmetric).
+ *                 u = u_prev[b * u_stride + 0 .. 1], the input the plant followed in the period just past.
+ *   4 reset       if the block cannot describe a car, u is not finite, an entry of x- or P- is not finite, or a P-_ii <= 0 (in a
+ *                 first period too): x- = z, P- = diag(p0), est_count[b][1] += 1 and est_count[b][0] restarts.
+ *   5 re-basing   if L > 0 and s is measured: x-[0] += L rint((z[0] - x-[0]) / L) (ties to even): the lap gate takes L off the arc
+ *                 length before the observation and the estimate follows.  x_prior is x- at this point.
+ *   6 update      sequentially for i = 0 .. nx - 1, measured components only: nu_i = z_i - x_i, s_i = P_ii + r_i; unless s_i > 0 the
+ *                 component is skipped; c = P[:, i], x_a += c_a nu_i / s_i, P_ab -= (c_a c_b) / s_i (exactly symmetric).
+ *                 innov_i = nu_i (0 for an unmeasured component), nis = sum of nu_i^2 / s_i over the components applied.  For
+ *                 diagonal R this is the joint Kalman update, and the nu_i are its whitened innovations.
+ *   7 check       a non-finite entry of the result, or a P_ii < 0: reset as in 4, then 6 again (every nu is 0: x = z bit for bit).
+ *   8 write back  est_x = x0_est = x, est_P = P, est_count[b][0] += 1.
+ * F_out is the F of step 2 / 3 whether or not step 4 then discards the prediction.
+ * FSAEMPC_ERR_ARG before any launch: what the LTV entries refuse in desc and sp; est, q, r or p0 NULL; L negative or not finite;
+ * u_stride < 2; z, x_start, u_prev, est_x, est_P, est_count, x0_est, innov or nis NULL; an output that overlaps another output or
+ * an input.  desc->batch == 0 succeeds without a launch. */
+typedef struct {
+  const double* q;  int q_per_instance;   /* device; nx or batch*nx */
+  const double* r;  int r_per_instance;   /* device; nx or batch*nx; +inf = not measured */
+  const double* p0;                       /* device; nx */
+  double L;                               /* lap length for re-basing s; 0 = none */
+} fsaempc_cl_estimator;
+
+int fsaempc_cl_estimate_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                     const fsaempc_cl_estimator* est, const double* z /* batch x nx */, const double* x_start /* batch x nx */,
+                                     const double* u_prev, long long u_stride /* doubles between cars */, const int* finished /* optional */,
+                                     double* est_x, double* est_P, int* est_count /* batch x 2, zeroed by the caller */,
+                                     double* x0_est, double* innov, double* nis /* batch */,
+                                     double* F_out /* optional, batch x nx x nx */, double* x_prior /* optional, batch x nx */, void* stream);
+
 /* ---- track pipeline (host side) --------------------------------------------------- */
 
 /* Spline table of a track as main.m:11-17 produces it: M arc-length segments, xP / yP = M x 4 Bezier control points per axis

@@ -24,10 +24,15 @@ max of its time) joins the JSON line as "lap_summary".
 --delay D [--compensate] [--noise s1,...,snx [--noise-seed S]]: the imperfect loop (fsaempc.Latency): a plan reaches the plant
 D periods after the state it was solved from; --compensate solves from that state predicted over the D periods; --noise adds
 state-estimate noise with these standard deviations (the model's state layout: 5 values kinematic, 7 dynamic).  Echoed as "latency".
+--estimator q1,...,qnx [--meas-var r1,...,rnx] [--unmeasured i,j]: the state estimator (fsaempc.Estimator) between the observation
+and the solve: process variances per period, measurement variances (default: the squares of --noise) and the indices of components that
+are not measured (their variance becomes +inf).  Echoed as "estimator", with the batch's re-initialisations and the mean NIS over the
+driving cars' periods.
 usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--track fss2019]
                                   [--plan | --raceline | --minlap K [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap] [--laps K]
                                   [--corridor FILE.npz | --cones FILE [--car-half-width W]] [--line-rows points|cells]
-                                  [--delay D [--compensate]] [--noise s1,...,snx [--noise-seed S]]"""
+                                  [--delay D [--compensate]] [--noise s1,...,snx [--noise-seed S]]
+                                  [--estimator q1,...,qnx [--meas-var r1,...,rnx] [--unmeasured i,j]]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -67,6 +72,9 @@ def main():
     ap.add_argument("--compensate", action="store_true", help="with --delay >= 1: solve from the observed state predicted over the delay")
     ap.add_argument("--noise", default=None, metavar="s1,...,snx", help="standard deviations of the state-estimate noise, one per state component")
     ap.add_argument("--noise-seed", type=int, default=0, metavar="S", help="with --noise: seed of the counter-based generator")
+    ap.add_argument("--estimator", default=None, metavar="q1,...,qnx", help="run the EKF state estimator with these process variances per period (Estimator)")
+    ap.add_argument("--meas-var", default=None, metavar="r1,...,rnx", help="with --estimator: measurement variances (default: the squares of --noise)")
+    ap.add_argument("--unmeasured", default=None, metavar="i,j", help="with --estimator: state components that are not measured (variance +inf)")
     a = ap.parse_args()
     sigma = None
     if a.noise is not None:
@@ -79,6 +87,28 @@ def main():
         lat.check_batch(5 if a.model == "kinematic" else 7, a.batch)
     except ValueError as e:
         ap.error(str(e))
+    est = None
+    nx_ = 5 if a.model == "kinematic" else 7
+    if a.estimator is None and (a.meas_var is not None or a.unmeasured is not None):
+        ap.error("--meas-var and --unmeasured need --estimator")
+    if a.estimator is not None:
+        try:
+            q = [float(v) for v in a.estimator.split(",")]
+            r = [float(v) for v in a.meas_var.split(",")] if a.meas_var is not None else ([v * v for v in sigma] if sigma is not None else None)
+            skip = [int(v) for v in a.unmeasured.split(",")] if a.unmeasured is not None else []
+        except ValueError:
+            ap.error("--estimator and --meas-var take comma-separated numbers, --unmeasured comma-separated indices")
+        if r is None:
+            ap.error("--estimator needs --meas-var or --noise")
+        if len(r) != nx_ or any(not 0 <= i < nx_ for i in skip):
+            ap.error("--meas-var takes %d values, --unmeasured indices 0 .. %d" % (nx_, nx_ - 1))
+        for i in skip:
+            r[i] = float("inf")
+        try:
+            est = fm.Estimator(q, r)
+            est.resolve(lat, nx_, a.batch, a.laps)
+        except ValueError as e:
+            ap.error(str(e))
     if a.corridor is not None and a.cones is not None:
         ap.error("--cones and --corridor exclude each other")
     if a.line_rows == "cells" and not (a.raceline and (a.corridor is not None or a.cones is not None)):
@@ -116,7 +146,7 @@ def main():
         plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip, corridor=cor, rows=a.line_rows)
     if a.minlap is not None:
         plan = fm.Plan.minlap(model, tr, N_s=a.cells, N_c=a.points, iters=a.minlap, margin=a.margin, grip=a.grip, corridor=cor)
-    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor, latency=lat)          # warm-up (allocations, code load)
+    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor, latency=lat, estimator=est)          # warm-up (allocations, code load)
     n_max = float(fm.default_params(model)[fm.PARAM_INDEX["N_MAX"]])
     opts = fm.default_opts(max_iter=a.max_iter)
     t0 = time.perf_counter()
@@ -124,13 +154,15 @@ def main():
     # every car while it drives
     cart0, s_init = fm.monte_carlo_carts(tr, a.batch, a.seed, lap=a.lap)
     cl = fm.ClosedLoop(model, a.horizon, 0.05, tr, cart0, options=opts, warm_start=a.warm, launch_hint=not a.no_launch_hint, reference=plan,
-                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps, latency=lat)
+                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps, latency=lat, estimator=est)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]
     fl_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
     it_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
     ac_d = torch.zeros((a.steps, a.batch), dtype=torch.bool, device=cl.device)
     off = torch.zeros((), dtype=torch.int64, device=cl.device)
+    nis_sum = torch.zeros((), dtype=torch.float64, device=cl.device)
+    nis_cnt = torch.zeros((), dtype=torch.int64, device=cl.device)
     s_first = s_last = None
     for t in range(a.steps):
         out = cl.step()
@@ -140,6 +172,8 @@ def main():
             s_first = cl.x0[:, 0].clone(); s_last = cl.x0[:, 0].clone()
         off += ((cl.x0[:, 1].abs() > n_max) & drv).sum()
         s_last = torch.where(drv, cl.x0[:, 0], s_last)
+        if est is not None:   # (a car that stopped driving in this very period still had its filter run)
+            nis_sum += cl.est_nis.sum(); nis_cnt += (cl.est_nis != 0).sum()
     torch.cuda.synchronize(cl.device)
     fl, it, ac = fl_d.cpu().numpy(), it_d.cpu().numpy(), ac_d.cpu().numpy()
     dt_wall = time.perf_counter() - t0
@@ -167,7 +201,12 @@ def main():
                                "(frame transform + reference + linearise/condense/solve + PID/plant, device-resident loop, no per-step read-back; "
                                "wall time includes the allocation of the run)" % (a.batch, a.track, a.steps),
                    "track": a.track, "corridor": a.corridor,
-                   "latency": {"delay": a.delay, "compensate": bool(a.compensate), "noise": sigma, "noise_seed": a.noise_seed}, **({"cones": cone_info} if cone_info is not None else {}), "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
+                   "latency": {"delay": a.delay, "compensate": bool(a.compensate), "noise": sigma, "noise_seed": a.noise_seed},
+                   **({"estimator": {"q": q, "r": [None if v == float("inf") else v for v in r], "unmeasured": skip, "resets": int(cl.est_resets.sum().item()),
+                                     "cars_reset": int((cl.est_resets > 0).sum().item()),
+                                     "nis_mean": float((nis_sum / nis_cnt.clamp(min=1)).item()), "nis_periods": int(nis_cnt.item()),
+                                     "measured_components": nx_ - len(skip)}} if est is not None else {}),
+                   **({"cones": cone_info} if cone_info is not None else {}), "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
                    # (a mean over an empty set is NaN in the report: null in the JSON line)
                    **({"lap_report": {k: (None if v != v else v) for k, v in cl.report().summary().items()}, "slack_tol": a.slack_tol} if a.report else {}),
                    **({"laps": a.laps, "lap_summary": [{"lap": i + 1, "cars": int(r[0]), "mean_s": None if r[1] != r[1] else float(r[1]),
