@@ -17,14 +17,18 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/qp_solver.h $(CSRC)/qp_sens.h $(CSRC)/ltv_b
 	@mkdir -p $(LIBDIR)
 	$(CC_CHECKED) $@ $< $(HIPFLAGS)
 
-# the minimum-time line: its own header, read by its unit and the C ABI only
-$(LIBDIR)/minlap.o $(LIBDIR)/capi.o: $(CSRC)/minlap.h
+# the C ABI (host-side glue, one unit per subsystem, built by the rule above): what the units share is read by them only
+CAPIOBJ := $(LIBDIR)/capi_qp.o $(LIBDIR)/capi_ltv.o $(LIBDIR)/capi_cl.o $(LIBDIR)/capi_plan.o
+$(CAPIOBJ): $(CSRC)/capi_common.h
 
-# measurement noise, plan latency and delay compensation of the closed loop: likewise
-$(LIBDIR)/cl_latency.o $(LIBDIR)/capi.o: $(CSRC)/cl_latency.h
+# the minimum-time line: its own header, read by its unit and the C ABI's planning unit only
+$(LIBDIR)/minlap.o $(LIBDIR)/capi_plan.o: $(CSRC)/minlap.h
+
+# measurement noise, plan latency and delay compensation of the closed loop: likewise, the C ABI's closed-loop unit
+$(LIBDIR)/cl_latency.o $(LIBDIR)/capi_cl.o: $(CSRC)/cl_latency.h
 
 # the state estimator of the closed loop: likewise
-$(LIBDIR)/cl_estimator.o $(LIBDIR)/capi.o: $(CSRC)/cl_estimator.h
+$(LIBDIR)/cl_estimator.o $(LIBDIR)/capi_cl.o: $(CSRC)/cl_estimator.h
 
 # WGFLAGS (both solve kernels): without machine LICM and with sinking-to-avoid-spills the T = 8 workgroup kernel spills 20 VGPRs
 # instead of 166 (256 are its budget at two waves per SIMD) and the one-wavefront kernels need no scratch at all (T = 5: 140..504
@@ -50,7 +54,7 @@ $(LIBDIR)/track.o: $(CSRC)/track.cpp include/fsaempc.h
 	@mkdir -p $(LIBDIR)
 	g++ -O2 -std=c++17 -fPIC -Wall -Iinclude -c $< -o $@
 
-COMMON := $(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o $(LIBDIR)/sqp.o $(LIBDIR)/qp_sens.o $(LIBDIR)/reference.o $(LIBDIR)/plant.o $(LIBDIR)/cl_latency.o $(LIBDIR)/cl_estimator.o $(LIBDIR)/planner.o $(LIBDIR)/raceline.o $(LIBDIR)/minlap.o $(LIBDIR)/corridor.o $(LIBDIR)/cones.o $(LIBDIR)/capi.o $(LIBDIR)/track.o
+COMMON := $(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o $(LIBDIR)/sqp.o $(LIBDIR)/qp_sens.o $(LIBDIR)/reference.o $(LIBDIR)/plant.o $(LIBDIR)/cl_latency.o $(LIBDIR)/cl_estimator.o $(LIBDIR)/planner.o $(LIBDIR)/raceline.o $(LIBDIR)/minlap.o $(LIBDIR)/corridor.o $(LIBDIR)/cones.o $(CAPIOBJ) $(LIBDIR)/track.o
 $(LIBDIR)/libfsaempc.so: $(QPOBJ) $(WGOBJ) $(COMMON)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

@@ -1,0 +1,246 @@
+// capi_cl.hip -- the C ABI of libfsaempc.so (include/fsaempc.h), closed-loop part: reference, pre, plant and accept, the metrics
+// and the lap gate with their two host-side reports, measurement noise, observation and the state estimator.  Host-side glue only:
+// argument checks and kernel launches.
+#include "capi_common.h"
+#include "reference.h"
+#include "plant.h"
+#include "cl_latency.h"
+#include "cl_estimator.h"
+using namespace capi;
+
+extern "C" {
+
+int fsaempc_obtain_reference_batch_device(const double* plan, double ds, int N_s, const double* t, const double* s0, double dt,
+                                          int N_t, int batch, double* x_ref, void* stream) {
+  if (!plan || !t || !s0 || !x_ref) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (N_s <= 0 || N_t <= 0 || batch < 0 || !(ds > 0) || !(dt > 0)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  RefParams P; P.plan = plan; P.t = t; P.s0 = s0; P.x_ref = x_ref; P.ds = ds; P.dt = dt; P.N_s = N_s; P.N_t = N_t; P.batch = batch;
+  return launched(obtain_reference_launch(P, (hipStream_t)stream), "obtain_reference_launch");
+}
+
+int fsaempc_reference_live_batch_device(int nx, int N, double dt, double target_vel, int batch, const double* x0, double* x_ref, void* stream) {
+  if (!x0 || !x_ref) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if ((nx != 5 && nx != 7) || N <= 0 || batch < 0 || !(dt > 0)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  return launched(reference_live_launch(nx, N, dt, target_vel, batch, x0, x_ref, (hipStream_t)stream), "reference_live_launch");
+}
+
+int fsaempc_cl_pre_batch_device(int model, int N, double dt, double target_vel, double L, const fsaempc_spline* sp, const double* cart,
+                                const double* s_guess, int batch, double* x0, double* x_ref, int* finished, void* stream) {
+  if (!sp || !sp->xP || !sp->yP || !cart || !s_guess || !x0 || !x_ref || !finished) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (N <= 0 || batch < 0 || !(dt > 0) || sp->M <= 0 || !(sp->dl > 0) || !(L > 0)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  ClPreParams P; P.nx = fsaempc_ltv_nx(model); P.N = N; P.batch = batch; P.dt = dt; P.target_vel = target_vel; P.L = L;
+  set_spline(&P, sp); P.cart = cart; P.s_guess = s_guess; P.x0 = x0; P.x_ref = x_ref; P.finished = finished;
+  return launched(cl_pre_launch(P, (hipStream_t)stream), "cl_pre_launch");
+}
+
+int fsaempc_cl_plant_batch_device(int model, int N, double dt, int batch, double* cart, double* pid, const double* x_opt,
+                                  const int* finished, const int* exitflag, double* u_last, void* stream) {
+  return fsaempc_cl_plant_batch_device_p(model, N, dt, batch, nullptr, cart, pid, x_opt, finished, exitflag, u_last, stream);
+}
+
+int fsaempc_cl_plant_batch_device_p(int model, int N, double dt, int batch, const fsaempc_ltv_params* par, double* cart, double* pid,
+                                    const double* x_opt, const int* finished, const int* exitflag, double* u_last, void* stream) {
+  if (!cart || !pid || !x_opt) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (N <= 0 || batch < 0 || !(dt > 0)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  ClPlantParams P; P.nx = fsaempc_ltv_nx(model); P.N = N; P.batch = batch; P.dt = dt; P.cart = cart; P.pid = pid; P.x_opt = x_opt;
+  P.finished = finished; P.exitflag = exitflag; P.u_last = u_last;
+  return launched(cl_plant_launch(P, (hipStream_t)stream, par_values(par), par_stride(par)), "cl_plant_launch");
+}
+
+int fsaempc_cl_accept_batch_device(int model, int N, int batch, const double* x_new, const double* u_new, const int* exitflag, double* x_keep, double* u_keep, void* stream) {
+  if (!x_new || !u_new || !x_keep || !u_keep) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (N <= 0 || batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  return launched(cl_accept_launch(fsaempc_ltv_nx(model) * N, 2 * N, batch, x_new, u_new, exitflag, x_keep, u_keep, (hipStream_t)stream), "cl_accept_launch");
+}
+
+/* ---- lap report ---- */
+static int cl_metrics(int model, int N, double dt, double slack_tol, int batch, const fsaempc_ltv_params* par, const fsaempc_corridor* cor,
+                      const double* x0, const int* finished, const int* exitflag, const int* iter, const double* fval,
+                      const double* slack, const double* u_drive, const double* cart, double* metrics, void* stream) {
+  CorTable ct;
+  if (cor) { if (int rc = cor_check(cor, &ct)) return rc; }
+  if (!x0 || !finished || !exitflag || !iter || !fval || !slack || !u_drive || !cart || !metrics) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (N <= 0 || batch < 0 || !pos_finite(dt)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (!(slack_tol >= 0)) return fail(FSAEMPC_ERR_ARG, "slack_tol must be >= 0");
+  if (batch == 0) return 0;
+  ClMetricsParams P; P.ns = ltv_ns(model); P.N = N; P.batch = batch; P.tyre = model == FSAEMPC_MODEL_DYNAMIC ? 3 : 0;
+  P.dt = dt; P.slack_tol = slack_tol; P.nx = fsaempc_ltv_nx(model); P.x0 = x0; P.finished = finished; P.exitflag = exitflag; P.iter = iter;
+  P.fval = fval; P.slack = slack; P.u_drive = u_drive; P.cart = cart; P.metrics = metrics;
+  hipError_t e = cor ? cor_metrics_launch(P, ct, (hipStream_t)stream, par_values(par), par_stride(par))
+                     : cl_metrics_launch(P, (hipStream_t)stream, par_values(par), par_stride(par));
+  return launched(e, cor ? "cor_metrics_launch" : "cl_metrics_launch");
+}
+int fsaempc_cl_metrics_batch_device(int model, int N, double dt, double slack_tol, int batch, const fsaempc_ltv_params* par,
+                                    const double* x0, const int* finished, const int* exitflag, const int* iter, const double* fval,
+                                    const double* slack, const double* u_drive, const double* cart, double* metrics, void* stream) {
+  return cl_metrics(model, N, dt, slack_tol, batch, par, nullptr, x0, finished, exitflag, iter, fval, slack, u_drive, cart, metrics, stream);
+}
+int fsaempc_cl_metrics_batch_device_c(int model, int N, double dt, double slack_tol, int batch, const fsaempc_ltv_params* par,
+                                      const fsaempc_corridor* cor,
+                                      const double* x0, const int* finished, const int* exitflag, const int* iter, const double* fval,
+                                      const double* slack, const double* u_drive, const double* cart, double* metrics, void* stream) {
+  return cl_metrics(model, N, dt, slack_tol, batch, par, cor, x0, finished, exitflag, iter, fval, slack, u_drive, cart, metrics, stream);
+}
+
+// Host.  Every sum runs over the cars in index order.  Means over an empty set are NaN (MATLAB's mean([])).
+int fsaempc_cl_report(const double* metrics_host, int batch, double dt, double* out) {
+  if (!out || (!metrics_host && batch != 0)) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (batch < 0 || !pos_finite(dt)) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  double cars[3] = {0, 0, 0}, lap_sum = 0, lap_min = NAN, lap_max = NAN, steps = 0, abn = 0, sl_n = 0, sl_t = 0, obj = 0, obj_cnt = 0;
+  double recorded = 0, nv_sum = 0, nv_big = 0, nv_max = 0, el_sum = 0, el_big = 0, el_max = 0, it_sum = 0, it_max = 0, n_abs = 0;
+  for (int b = 0; b < batch; ++b) {
+    const double* m = metrics_host + (size_t)b * FSAEMPC_NMETRIC;
+    const int st = m[FSAEMPC_M_STATUS] == 1.0 ? 1 : (m[FSAEMPC_M_STATUS] == 2.0 ? 2 : 0);
+    cars[st] += 1;
+    if (st == 1) {
+      const double lap = m[FSAEMPC_M_STEPS] * dt;
+      lap_sum += lap;
+      if (!(lap_min <= lap)) lap_min = lap;
+      if (!(lap_max >= lap)) lap_max = lap;
+    }
+    steps += m[FSAEMPC_M_STEPS]; abn += m[FSAEMPC_M_ABNORMAL]; sl_n += m[FSAEMPC_M_SLACK_N_CNT]; sl_t += m[FSAEMPC_M_SLACK_TYRE_CNT];
+    obj += m[FSAEMPC_M_OBJ_SUM]; obj_cnt += m[FSAEMPC_M_OBJ_CNT]; it_sum += m[FSAEMPC_M_ITER_SUM];
+    if (m[FSAEMPC_M_STEPS] > 0) { recorded += 1; nv_sum += m[FSAEMPC_M_N_VIOL_INT]; el_sum += m[FSAEMPC_M_ELL_VIOL_INT]; }
+    if (m[FSAEMPC_M_N_VIOL_INT] > nv_big) nv_big = m[FSAEMPC_M_N_VIOL_INT];
+    if (m[FSAEMPC_M_N_VIOL_MAX] > nv_max) nv_max = m[FSAEMPC_M_N_VIOL_MAX];
+    if (m[FSAEMPC_M_ELL_VIOL_INT] > el_big) el_big = m[FSAEMPC_M_ELL_VIOL_INT];
+    if (m[FSAEMPC_M_ELL_VIOL_MAX] > el_max) el_max = m[FSAEMPC_M_ELL_VIOL_MAX];
+    if (m[FSAEMPC_M_ITER_MAX] > it_max) it_max = m[FSAEMPC_M_ITER_MAX];
+    if (m[FSAEMPC_M_N_ABS_MAX] > n_abs) n_abs = m[FSAEMPC_M_N_ABS_MAX];
+  }
+  out[FSAEMPC_R_CARS_DRIVING] = cars[0]; out[FSAEMPC_R_CARS_FINISHED] = cars[1]; out[FSAEMPC_R_CARS_LOST] = cars[2];
+  out[FSAEMPC_R_LAP_MEAN] = cars[1] > 0 ? lap_sum / cars[1] : NAN; out[FSAEMPC_R_LAP_MIN] = lap_min; out[FSAEMPC_R_LAP_MAX] = lap_max;
+  out[FSAEMPC_R_STEPS] = steps;
+  out[FSAEMPC_R_ABNORMAL_PCT] = steps > 0 ? abn / steps * 100 : NAN;
+  out[FSAEMPC_R_SLACK_N_PCT] = steps > 0 ? sl_n / steps * 100 : NAN;
+  out[FSAEMPC_R_SLACK_TYRE_PCT] = steps > 0 ? sl_t / steps * 100 : NAN;
+  out[FSAEMPC_R_OBJ_MEAN] = obj_cnt > 0 ? obj / obj_cnt : NAN;
+  out[FSAEMPC_R_N_VIOL_INT_MEAN] = recorded > 0 ? nv_sum / recorded : NAN; out[FSAEMPC_R_N_VIOL_INT_MAX] = nv_big; out[FSAEMPC_R_N_VIOL_MAX] = nv_max;
+  out[FSAEMPC_R_ELL_VIOL_INT_MEAN] = recorded > 0 ? el_sum / recorded : NAN; out[FSAEMPC_R_ELL_VIOL_INT_MAX] = el_big; out[FSAEMPC_R_ELL_VIOL_MAX] = el_max;
+  out[FSAEMPC_R_ITER_MEAN] = steps > 0 ? it_sum / steps : NAN; out[FSAEMPC_R_ITER_MAX] = it_max; out[FSAEMPC_R_N_ABS_MAX] = n_abs;
+  return 0;
+}
+
+/* ---- multi-lap closed loop: the lap gate ---- */
+int fsaempc_cl_lap_gate_batch_device(int nx, int N, double dt, double L, int laps, int batch, double* x0, double* x_ref, double* x_keep,
+                                     int* finished, double* lap_state, double* lap_times, double* metrics, double* lap_records, void* stream) {
+  if (laps < 1 || laps > FSAEMPC_MAX_LAPS) return fail(FSAEMPC_ERR_ARG, "laps must be 1 .. FSAEMPC_MAX_LAPS");
+  if (nx != 5 && nx != 7) return fail(FSAEMPC_ERR_ARG, "nx must be 5 or 7");
+  if (N < 1 || batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (!pos_finite(dt) || !pos_finite(L)) return fail(FSAEMPC_ERR_ARG, "dt and L must be finite and > 0");
+  if (!x0 || !x_ref || !x_keep || !finished || !lap_state || !lap_times) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if ((metrics == nullptr) != (lap_records == nullptr)) return fail(FSAEMPC_ERR_ARG, "metrics and lap_records are given together or not at all");
+  if (batch == 0) return 0;
+  ClLapGateParams P; P.nx = nx; P.N = N; P.laps = laps; P.batch = batch; P.dt = dt; P.L = L; P.x0 = x0; P.x_ref = x_ref; P.x_keep = x_keep;
+  P.finished = finished; P.lap_state = lap_state; P.lap_times = lap_times; P.metrics = metrics; P.lap_records = lap_records;
+  return launched(cl_lap_gate_launch(P, (hipStream_t)stream), "cl_lap_gate_launch");
+}
+
+// Host.  Every sum runs over the cars in index order; a lap nobody completed has NaN mean, min and max.
+int fsaempc_cl_lap_summary(const double* lap_times_host, int batch, int laps, double* out) {
+  if (!out || (!lap_times_host && batch != 0)) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (laps < 1 || laps > FSAEMPC_MAX_LAPS) return fail(FSAEMPC_ERR_ARG, "laps must be 1 .. FSAEMPC_MAX_LAPS");
+  for (int l = 0; l < laps; ++l) {
+    double cnt = 0, sum = 0, lo = NAN, hi = NAN;
+    for (int b = 0; b < batch; ++b) {
+      const double t = lap_times_host[(size_t)b * laps + l];
+      if (t != t) continue;
+      cnt += 1; sum += t;
+      if (!(lo <= t)) lo = t;
+      if (!(hi >= t)) hi = t;
+    }
+    out[4 * l] = cnt; out[4 * l + 1] = cnt > 0 ? sum / cnt : NAN; out[4 * l + 2] = lo; out[4 * l + 3] = hi;
+  }
+  return 0;
+}
+
+/* ---- closed loop: measurement noise, plan latency and delay compensation ---- */
+static int cl_draw_check(long long id0, long long step) {
+  if (id0 < 0) return fail(FSAEMPC_ERR_ARG, "id0 must be >= 0");
+  if (step < 0 || step >= (1LL << 32)) return fail(FSAEMPC_ERR_ARG, "step must be 0 .. 2^32 - 1");
+  return 0;
+}
+
+int fsaempc_cl_noise_batch_device(int nx, int batch, unsigned long long seed, long long id0, long long step, double* z, void* stream) {
+  if (nx != 5 && nx != 7) return fail(FSAEMPC_ERR_ARG, "nx must be 5 or 7");
+  if (batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (int rc = cl_draw_check(id0, step)) return rc;
+  if (!z) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (batch == 0) return 0;
+  return launched(cl_noise_launch(nx, batch, seed, (unsigned long long)id0, (unsigned long long)step, z, (hipStream_t)stream), "cl_noise_launch");
+}
+
+int fsaempc_cl_observe_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                    const fsaempc_cl_latency* lat, long long step, const double* x0_true, const int* finished,
+                                    const double* u_hist, double* x0_obs, double* x0_mpc, void* stream) {
+  if (int rc = ltv_check(desc, sp)) return rc;
+  if (!lat) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (lat->delay < 0 || lat->delay > FSAEMPC_CL_MAX_DELAY) return fail(FSAEMPC_ERR_ARG, "delay must be 0 .. FSAEMPC_CL_MAX_DELAY");
+  if (lat->compensate != 0 && lat->compensate != 1) return fail(FSAEMPC_ERR_ARG, "compensate must be 0 or 1");
+  if (int rc = cl_draw_check(lat->id0, step)) return rc;
+  if (lat->delay > 0 && !u_hist) return fail(FSAEMPC_ERR_ARG, "null argument (u_hist is required with delay > 0)");
+  if (!x0_true || !x0_obs || !x0_mpc) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (desc->batch == 0) return 0;
+  ClObserveParams P;
+  P.nx = fsaempc_ltv_nx(desc->model); P.N = desc->N; P.batch = desc->batch; P.integ = ltv_integ(desc);
+  P.delay = lat->delay; P.compensate = lat->compensate; P.sigma_per_instance = lat->sigma_per_instance ? 1 : 0; P.dt = desc->dt;
+  P.seed = lat->seed; P.id0 = (unsigned long long)lat->id0; P.step = (unsigned long long)step;
+  set_spline(&P, sp);
+  P.sigma = lat->sigma; P.x0_true = x0_true; P.finished = finished; P.u_hist = u_hist; P.x0_obs = x0_obs; P.x0_mpc = x0_mpc;
+  return launched(cl_observe_launch(P, (hipStream_t)stream, par_values(par), par_stride(par)), "cl_observe_launch");
+}
+
+// Host.
+int fsaempc_cl_history_slot(int delay, long long step, int lag) {
+  if (delay < 0 || delay > FSAEMPC_CL_MAX_DELAY || step < 0 || lag < 0 || lag > delay) return -1;
+  return cll_slot(delay, step, lag);
+}
+
+/* ---- closed loop: the state estimator ---- */
+namespace { struct ByteRange { const char* name; const void* p; size_t bytes; }; }
+static bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
+  if (!a.p || !b.p || a.bytes == 0 || b.bytes == 0) return false;
+  const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+  return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+
+int fsaempc_cl_estimate_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                     const fsaempc_cl_estimator* est, const double* z, const double* x_start, const double* u_prev,
+                                     long long u_stride, const int* finished, double* est_x, double* est_P, int* est_count, double* x0_est,
+                                     double* innov, double* nis, double* F_out, double* x_prior, void* stream) {
+  if (int rc = ltv_check(desc, sp)) return rc;
+  if (!est || !est->q || !est->r || !est->p0) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (!(est->L >= 0 && est->L < INFINITY)) return fail(FSAEMPC_ERR_ARG, "L must be finite and >= 0");
+  if (u_stride < 2) return fail(FSAEMPC_ERR_ARG, "u_stride must be >= 2");
+  if (!z || !x_start || !u_prev || !est_x || !est_P || !est_count || !x0_est || !innov || !nis) return fail(FSAEMPC_ERR_ARG, "null argument");
+  const size_t B = (size_t)desc->batch, nx = (size_t)fsaempc_ltv_nx(desc->model), d = sizeof(double);
+  const ByteRange out[] = {{"est_x", est_x, B * nx * d}, {"est_P", est_P, B * nx * nx * d}, {"est_count", est_count, B * 2 * sizeof(int)},
+                           {"x0_est", x0_est, B * nx * d}, {"innov", innov, B * nx * d}, {"nis", nis, B * d},
+                           {"F_out", F_out, B * nx * nx * d}, {"x_prior", x_prior, B * nx * d}};
+  const ByteRange in[] = {{"z", z, B * nx * d}, {"x_start", x_start, B * nx * d},
+                          {"u_prev", u_prev, B ? ((B - 1) * (size_t)u_stride + 2) * d : 0}, {"finished", finished, B * sizeof(int)},
+                          {"q", est->q, (est->q_per_instance ? B : 1) * nx * d}, {"r", est->r, (est->r_per_instance ? B : 1) * nx * d},
+                          {"p0", est->p0, nx * d}};
+  const int n_out = (int)(sizeof(out) / sizeof(out[0])), n_in = (int)(sizeof(in) / sizeof(in[0]));
+  for (int i = 0; i < n_out; ++i) {
+    for (int k = i + 1; k < n_out; ++k)
+      if (ranges_overlap(out[i], out[k])) return fail(FSAEMPC_ERR_ARG, "overlapping outputs");
+    for (int k = 0; k < n_in; ++k)
+      if (ranges_overlap(out[i], in[k])) return fail(FSAEMPC_ERR_ARG, "an output overlaps an input");
+  }
+  if (desc->batch == 0) return 0;
+  ClEstimateParams P;
+  P.nx = (int)nx; P.batch = desc->batch; P.integ = ltv_integ(desc); P.q_per_instance = est->q_per_instance ? 1 : 0;
+  P.r_per_instance = est->r_per_instance ? 1 : 0; P.dt = desc->dt; P.L = est->L;
+  set_spline(&P, sp);
+  P.q = est->q; P.r = est->r; P.p0 = est->p0; P.z = z; P.x_start = x_start; P.u_prev = u_prev; P.u_stride = u_stride; P.finished = finished;
+  P.est_x = est_x; P.est_P = est_P; P.est_count = est_count; P.x0_est = x0_est; P.innov = innov; P.nis = nis; P.F_out = F_out; P.x_prior = x_prior;
+  return launched(cl_estimate_launch(P, (hipStream_t)stream, par_values(par), par_stride(par)), "cl_estimate_launch");
+}
+
+}  // extern "C"

@@ -256,7 +256,7 @@ template <bool DYN> inline int ml_lapgrad_host(const MlCar& p, double A_lat, dou
 }
 
 #if defined(__HIPCC__)
-// ---- internal interface between capi.hip and minlap.hip ----
+// ---- internal interface between the C ABI (capi_plan.hip) and minlap.hip ----
 struct MinlapGradParams {
   int dynamic, n_waves, N_s, N_c;
   int cand;                 // waves per plan: wave w belongs to plan w / cand (its block, width check, base, lo, hi)

@@ -82,7 +82,7 @@ PLAN_HD void plan_walk(const double* plan, const double* t, int Ns, double ds, d
 }
 
 #if defined(__HIPCC__)
-// ---- internal interface between capi.hip and planner.hip ----
+// ---- internal interface between the C ABI (capi_plan.hip) and planner.hip ----
 struct PlanProfileParams {
   int dynamic, n_plans, N_s;
   double ds, v_cap, grip;

@@ -1,4 +1,4 @@
-// qp_sens.h -- internal interface between the C ABI (capi.hip) and the QP vector-Jacobian product kernel (qp_sens.hip)
+// qp_sens.h -- internal interface between the C ABI (capi_qp.hip) and the QP vector-Jacobian product kernel (qp_sens.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,4 +1,4 @@
-// qp_solver.h -- internal interface between the C ABI (capi.hip) and the QP kernels (qp_solver.hip, qp_wg.hip)
+// qp_solver.h -- internal interface between the C ABI (capi_qp.hip; capi_plan.hip reads the dimensions) and the QP kernels (qp_solver.hip, qp_wg.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -546,7 +546,7 @@ hipError_t qp_launch_solve_g4(const QpParams& P, int batch, hipStream_t st) { re
 static bool qp_use_wavefront_kernel(const QpDims& d) {
   return d.T <= QP_V1_MAX_T;
 }
-bool qp_runs_wavefront_kernel(const QpDims& d) {   // what qp_launch will pick (capi.hip checks the LDS budget of that kernel)
+bool qp_runs_wavefront_kernel(const QpDims& d) {   // what qp_launch will pick (the C ABI checks the LDS budget of that kernel)
   static const char* force = getenv("FSAEMPC_QP_KERNEL");   // A/B runs only: "wg" or "v1"
   return d.T <= QP_V1_MAX_T && ((force && force[0] == 'v') || (!(force && force[0] == 'w') && qp_use_wavefront_kernel(d)));
 }

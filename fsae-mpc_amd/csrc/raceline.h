@@ -205,7 +205,7 @@ RL_HD RlPoint rl_point(const double* c, int i, int Ns, int Nc, double h, double 
 }
 
 #if defined(__HIPCC__)
-// ---- internal interface between capi.hip and raceline.hip ----
+// ---- internal interface between the C ABI (capi_plan.hip) and raceline.hip ----
 struct RacelineQpParams {
   int N_s, N_c;
   double ds;

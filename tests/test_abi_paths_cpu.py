@@ -277,6 +277,39 @@ def test_workspace_sizes_are_what_they_were():
         assert L.fsaempc_ltv_workspace_bytes_b(C.byref(d), C.byref(blk)) == rc, bad
 
 
+QP_SHAPES = ((9, 0), (13, 36), (81, 240), (124, 1200), (196, 0))
+LINE_SHAPES = ((1, 8), (3, 8), (2, 40), (1, 196))             # (n_plans, N_c)
+CELLS_SHAPES = ((1, 16, 8), (3, 80, 40), (1, 392, 196), (1, 2048, 196))   # (n_plans, N_s, N_c)
+
+
+def other_workspace_sizes(L, _lib):
+    """Every size query outside the LTV step family, negative codes included: entry -> {shape: size, or sizes over the last argument}."""
+    got = {"sqp": {}, "qp_s": {}, "qp_vjp": {}, "raceline": {}, "minlap": {}, "cells": {}}
+    for model, N, B in itertools.product((0, 1), (6, 40), (1, 3)):
+        got["sqp"][(model, N, B)] = L.fsaempc_sqp_workspace_bytes(C.byref(_lib.LtvDesc(model, N, B, DT, -1)))
+    for (nV, nC), B, shared in itertools.product(QP_SHAPES, (1, 3), (0, 1)):
+        d = _lib.QpDesc(nV, nC, B, shared)
+        got["qp_s"][(nV, nC, B, shared)] = [L.fsaempc_qp_workspace_bytes_s(C.byref(d), s) for s in (-1, 0, 1, 4)]
+        got["qp_vjp"][(nV, nC, B, shared)] = L.fsaempc_qp_vjp_workspace_bytes(C.byref(d))
+    for k in LINE_SHAPES:
+        got["raceline"][k] = L.fsaempc_plan_raceline_workspace_bytes(*k)
+        got["minlap"][k] = [L.fsaempc_plan_minlap_workspace_bytes(*k, n_rho) for n_rho in (1, 8, 16)]
+    for k in CELLS_SHAPES:
+        got["cells"][k] = L.fsaempc_plan_raceline_cells_workspace_bytes(*k)
+    return got
+
+
+def test_the_other_workspace_sizes_are_what_they_were():
+    """The SQP, the plain QP solve (every slack hint), the QP VJP and the three racing-line workspaces: the sizes the library
+    reported before the C ABI glue was split into units and its layouts were written over one allocator."""
+    import fsae_mpc_amd as fm
+    from fsae_mpc_amd import _lib
+    got = other_workspace_sizes(fm.lib(), _lib)
+    for entry, want in OTHER_WORKSPACE_BYTES.items():
+        assert got[entry] == want, (entry, got[entry])
+    assert set(got) == set(OTHER_WORKSPACE_BYTES)
+
+
 def test_the_instances_of_the_gpu_comparison_solve_on_the_oracle(orc, otrack):
     """tests/test_abi_paths_gpu.py compares entries bit for bit and asserts exit flag 0 everywhere: these are cars the oracle solves,
     unblocked and blocked, so a batch of failures cannot pass there as "equal"."""
@@ -401,6 +434,27 @@ WORKSPACE_BYTES = {(0, 6, 1): [44800, 20480, 22016, 41472, 44800, 41472, 44800],
  (1, 6, 3): [251904, 131584, 144640, 226048, 251904, 226048, 251904],
  (1, 40, 1): [1590272, 1100288, 1128704, -1, -1, 934656, 1590272],
  (1, 40, 3): [4770048, 3299840, 3384832, -1, -1, 2803200, 4770048]}
+OTHER_WORKSPACE_BYTES = {
+ 'cells': {(1, 16, 8): 33024, (1, 392, 196): 2151360, (1, 2048, 196): 7646208, (3, 80, 40): 350720},
+ 'minlap': {(1, 8): [38336, 169600, 319872], (1, 196): [-2, -2, -2], (2, 40): [205312, 880256, 1651840], (3, 8): [113216, 507520, 958336]},
+ 'qp_s': {(9, 0, 1, 0): [18432, 18432, 19456, 19456], (9, 0, 1, 1): [18432, 18432, 19456, 19456],
+          (9, 0, 3, 0): [55296, 55296, 58368, 58368], (9, 0, 3, 1): [55296, 55296, 58368, 58368],
+          (13, 36, 1, 0): [34816, 34816, 35840, 35840], (13, 36, 1, 1): [34816, 34816, 35840, 35840],
+          (13, 36, 3, 0): [104448, 104448, 107520, 107520], (13, 36, 3, 1): [104448, 104448, 107520, 107520],
+          (81, 240, 1, 0): [313856, 379392, 313856, 313856], (81, 240, 1, 1): [313856, 379392, 313856, 313856],
+          (81, 240, 3, 0): [941568, 1138176, 941568, 941568], (81, 240, 3, 1): [941568, 1138176, 941568, 941568],
+          (124, 1200, 1, 0): [1721344, 1710080, 1721344, 1721344], (124, 1200, 1, 1): [1721344, 1710080, 1721344, 1721344],
+          (124, 1200, 3, 0): [5164032, 5130240, 5164032, 5164032], (124, 1200, 3, 1): [5164032, 5130240, 5164032, 5164032],
+          (196, 0, 1, 0): [510464, -2, -2, 510464], (196, 0, 1, 1): [510464, -2, -2, 510464],
+          (196, 0, 3, 0): [1531392, -2, -2, 1531392], (196, 0, 3, 1): [1531392, -2, -2, 1531392]},
+ 'qp_vjp': {(9, 0, 1, 0): 6400, (9, 0, 1, 1): 6400, (9, 0, 3, 0): 19200, (9, 0, 3, 1): 19200,
+            (13, 36, 1, 0): 6656, (13, 36, 1, 1): 6656, (13, 36, 3, 0): 19968, (13, 36, 3, 1): 19968,
+            (81, 240, 1, 0): 222976, (81, 240, 1, 1): 222976, (81, 240, 3, 0): 668928, (81, 240, 3, 1): 668928,
+            (124, 1200, 1, 0): 399104, (124, 1200, 1, 1): 399104, (124, 1200, 3, 0): 1197312, (124, 1200, 3, 1): 1197312,
+            (196, 0, 1, 0): 1388032, (196, 0, 1, 1): 1388032, (196, 0, 3, 0): 4164096, (196, 0, 3, 1): 4164096},
+ 'raceline': {(1, 8): 19264, (1, 196): -2, (2, 40): 108032, (3, 8): 56512},
+ 'sqp': {(0, 6, 1): 46336, (0, 6, 3): 136448, (0, 40, 1): 666112, (0, 40, 3): 1996032,
+         (1, 6, 1): 86528, (1, 6, 3): 257792, (1, 40, 1): 1601536, (1, 40, 3): 4802816}}
 EXPECTED = {'A NULL': [(-1, 'null argument (Bt is required as scratch)', '*')],
  'Bt NULL': [(-1, 'null argument (Bt is required as scratch)', '*')],
  'H NULL': [(-1, 'null argument (Bt is required as scratch)', '*')],
