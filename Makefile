@@ -35,9 +35,10 @@ $(LIBDIR)/cl_estimator.o $(LIBDIR)/capi_cl.o: $(CSRC)/cl_estimator.h
 # bytes per lane before): hoisted address arithmetic no longer lives across the whole iteration loop.
 WGFLAGS := -mllvm -disable-machine-licm -mllvm -sink-insts-to-avoid-spills=1
 
+# (qp_rules.h: the scalar rules of the algorithm, read by both solve kernels -- every solver unit and variant depends on it)
 # qp_solver.hip is compiled as five translation units (see the note in the file): main + the tile counts T = 1..4, 5, 6, 7
-QPHDRS := $(CSRC)/qp_solver.h $(CSRC)/qp_lane.h $(CSRC)/qp_solve_kernel.h $(CSRC)/qp_selftest.h $(CSRC)/qp_probe.h
-WGHDRS := $(CSRC)/qp_solver.h $(CSRC)/qp_lane.h
+QPHDRS := $(CSRC)/qp_solver.h $(CSRC)/qp_lane.h $(CSRC)/qp_rules.h $(CSRC)/qp_solve_kernel.h $(CSRC)/qp_selftest.h $(CSRC)/qp_probe.h
+WGHDRS := $(CSRC)/qp_solver.h $(CSRC)/qp_lane.h $(CSRC)/qp_rules.h
 QPOBJ := $(LIBDIR)/qp_solver_tu0.o $(LIBDIR)/qp_solver_tu1.o $(LIBDIR)/qp_solver_tu2.o $(LIBDIR)/qp_solver_tu3.o $(LIBDIR)/qp_solver_tu4.o
 $(LIBDIR)/qp_solver_tu%.o: $(CSRC)/qp_solver.hip $(QPHDRS) include/fsaempc.h $(CHECKDEPS)
 	@mkdir -p $(LIBDIR)

@@ -1,8 +1,11 @@
 // qp_solve_kernel.h -- the one-wavefront-per-QP solve kernel: what translation units 1..4 of qp_solver.hip compile (the main unit
-// reads it for the self tests and the probes).  Data layout: qp_solver.hip.
+// reads it for the self tests and the probes).  Data layout: qp_solver.hip.  The arithmetic of a row and the decisions of an
+// iteration and of the refinement (weights, directions, ratio tests, sigma, step length, merit, exits, acceptance) are qp_rules.h's,
+// shared with the workgroup kernel: this file moves the data and reduces across lanes.
 #pragma once
 #include "qp_solver.h"
 #include "qp_lane.h"
+#include "qp_rules.h"
 
 // 1: the two right-hand sides of an iteration's factor go through the triangular solves together (A/B builds; the shipped build
 // solves them one after the other: profiles/lane_reduce/README.md)
@@ -55,6 +58,10 @@ enum VecArr { V_X = 0, V_G, V_HX, V_R1, V_R2, V_P1, V_P2, V_P3, V_DX, V_E, V_NAR
 
 DEVINL double* rowp(const Ctx& k, int arr) { return k.rows + (size_t)arr * k.rowlen; }
 DEVINL double* vecp(const Ctx& k, int arr) { return k.vec + arr * k.np; }
+// An LDS n-vector element read as LDS, for the one place where a row array (global) or an n-vector feeds the same value: left as
+// two generic loads the compiler merges them into one flat load of a selected pointer, whose LDS aperture copy the register allocator
+// may place in vcc -- which this compiler expands into an illegal instruction (seen in the -O1 guard build).
+DEVINL double vec_read(const double* p) { return *(const __attribute__((address_space(3))) double*)p; }
 
 DEVINL bool row_valid(const Ctx& k, int js) {
   if (js < k.J) { const int s = 16 * js + k.c; return s < k.Kq && 4 * s + k.q < k.m; }
@@ -145,8 +152,6 @@ template <int T> DEVINL void hx_from_acc(const Ctx& k, const v4d* acc, const dou
     for (int p = 0; p < 4; ++p) if (k.c == 0) HX[16 * I + k.q + 4 * p] += sr[I][p];
   }
 }
-
-template <int C> struct IC { static constexpr int value = C; };
 
 // ---------------------------------------------------------------------------------------------
 // Operand stream of the passes over A~.  The stream is a plain sequence of 1 KB records (one column tile of one pair of
@@ -869,9 +874,6 @@ template <int T> DEVINL void vec_rows_load(const Ctx& k, const double* V, double
 #define STAMP_OUT do { } while (0)
 #endif
 
-#ifndef QP_REFINE_ATTEMPTS
-#define QP_REFINE_ATTEMPTS 3
-#endif
 // One QP as the kernel sees it: dimensions, this lane's coordinates, the arrays of the QP's workspace, the LDS base.  k.ring and k.cof
 // are the caller's to set: it carves the regions behind the n-vectors with qp_solve_lds.  Returns the QP's workspace.
 static_assert(V_NARR == QP_SOLVE_NVEC, "qp_solve_lds (qp_solver.h) counts the n-vectors");
@@ -1052,20 +1054,10 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
   // residuals and barrier weights of one row (owner lane): everything pass 1 / pass 2 need, in owner layout
   auto row1_body = [&](int ix, bool valid, double l, double u, double v, double tl, double tu, double zl, double zu,
                        double& s_gap, double& m_rp) {
-    const bool hl = valid && l > -INFINITY, hu = valid && u < INFINITY;
-    const double rpl = hl ? v - l - tl : 0.0, rpu = hu ? u - v - tu : 0.0;
-    const double dl_ = hl ? zl / tl : 0.0, du_ = hu ? zu / tu : 0.0;
-    aRPL[ix] = rpl; aRPU[ix] = rpu;
-    rowp(k, R_CB1)[ix] = dl_; rowp(k, R_CC1)[ix] = hl ? dl_ / tl : 0.0;
-    rowp(k, R_CB2)[ix] = du_; rowp(k, R_CC2)[ix] = hu ? du_ / tu : 0.0;
-    aD[ix] = dl_ + du_;
-    aW1[ix] = -dl_ * rpl + du_ * rpu;                              // affine rhs weight
-    aW2[ix] = (hl ? 1.0 / tl : 0.0) - (hu ? 1.0 / tu : 0.0);      // centering weight (times sigma*mu)
-    aW3[ix] = (hl ? zl : 0.0) - (hu ? zu : 0.0);                  // current multiplier (for the dual residual)
-    s_gap += (hl ? tl * zl : 0.0) + (hu ? tu * zu : 0.0);
-    const double sc = fmax(1.0, fabs(v));
-    if (hl) m_rp = fmax(m_rp, fabs(rpl) / fmax(sc, fabs(l)));
-    if (hu) m_rp = fmax(m_rp, fabs(rpu) / fmax(sc, fabs(u)));
+    const QprRow o = qpr_row_weights(valid, l, u, v, tl, tu, zl, zu, s_gap, m_rp);
+    aRPL[ix] = o.rpl; aRPU[ix] = o.rpu; rowp(k, R_CB1)[ix] = o.dl; rowp(k, R_CC1)[ix] = o.ccl;
+    rowp(k, R_CB2)[ix] = o.du; rowp(k, R_CC2)[ix] = o.ccu;
+    aD[ix] = o.D; aW1[ix] = o.W1; aW2[ix] = o.W2; aW3[ix] = o.W3;
   };
   struct Slot { int ix; bool valid; double l, u, v, tl, tu, zl, zu, va, vc, w2, rpl, rpu; };
   auto load_slot = [&](int js) {   // all loads of one owner-layout slot, issued together (one latency per trip)
@@ -1313,18 +1305,13 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     for (int h = 0; h < 2; ++h) {
       const int i = lane + 64 * h;
       if (i < n) {
-        const double gz = P3[i] + w3b[h];
-        fl += 0.5 * X[i] * HX[i] + G[i] * X[i];
-        const double sc = fmax(1.0, fmax(fabs(G[i]), fmax(fabs(HX[i]), fabs(gz))));
-        m_rd = fmax(m_rd, fabs(HX[i] + G[i] - gz) / sc);
+        fl += qpr_obj_term(X[i], HX[i], G[i]);
+        m_rd = fmax(m_rd, qpr_rd_term(HX[i], G[i], P3[i] + w3b[h]));
       }
     }
     const double fval = wave_sum(fl);
     const double rd_rel = wave_max(m_rd);
-    const double gap_rel = gap / fmax(1.0, fabs(fval));
-    // (fmax drops NaN operands: an iterate with NaN in it -- a step along a direction from a broken-down factorisation, 0 * NaN --
-    //  would read as merit 0.  Its objective is NaN, and so must the merit be: the best saved iterate is returned then.)
-    const double merit = (fabs(fval) < INFINITY && fabs(gap_rel) < INFINITY) ? fmax(rd_rel, fmax(rp_rel, gap_rel)) : INFINITY;
+    const QprMerit mer = qpr_merit(fval, gap, rd_rel, rp_rel); const double gap_rel = mer.gap_rel, merit = mer.merit;
     fval_s = fval; merit_s = merit;
     const bool res_ok = merit <= P.tol;
 #ifdef QP_DEBUG_DUMP
@@ -1334,40 +1321,30 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     }
 #endif
     if (!(merit < INFINITY)) { flag = have_saved ? 2 : -1; break; }
-    if (merit <= P.tol_loose && merit < saved_merit) {
+    const int keep = qpr_keep_rule(merit, rp_rel, gap_rel, P.tol_loose, saved_merit, have_saved);
+    if (keep == QPR_KEEP_SAVE) {
       for (int i = lane; i < k.np; i += 64) XS[i] = X[i];
       for (int js = 0; js < JT; ++js) LAMS[js * 64 + lane] = aW3[js * 64 + lane];
       have_saved = 1; saved_merit = merit;
-    } else if (merit > P.tol_loose && rp_rel <= P.tol_loose && gap_rel <= P.tol_loose) {
-      // Only the dual residual is in the way (the Newton steps lose accuracy once z/t passes ~1e19 and r_d creeps up):
-      // repair the certificate of a *copy* of the iterate by moving r_d into the bound multipliers, where a finite bound
-      // of the right sign exists; the copy qualifies as fall-back if its complementarity stays within tol_loose.
+    } else if (keep == QPR_KEEP_REPAIR) {   // only the dual residual is in the way: certificate repair of a copy
       double dgap = 0, m_rd2 = 0, lamfix[2] = {0.0, 0.0};
       for (int h = 0; h < 2; ++h) {
         const int i = lane + 64 * h;
         if (i < n) {
           const int ix = (J + (i >> 6)) * 64 + (i & 63);
-          const double lam = aW3[ix], gz = P3[i] + lam, r = HX[i] + G[i] - gz;
-          const double lam2 = lam + r, l = aL[ix], u = aU[ix], v = aV[ix];
-          const bool ok = lam2 >= 0 ? l > -INFINITY : u < INFINITY;
-          if (ok) { lamfix[h] = lam2; dgap += fabs(r) * fmax(0.0, lam2 >= 0 ? v - l : u - v); }
-          else {
-            lamfix[h] = lam;
-            const double sc = fmax(1.0, fmax(fabs(G[i]), fmax(fabs(HX[i]), fabs(gz))));
-            m_rd2 = fmax(m_rd2, fabs(r) / sc);
-          }
+          lamfix[h] = qpr_repair(aW3[ix], P3[i], HX[i], G[i], aL[ix], aU[ix], aV[ix], dgap, m_rd2);
         }
       }
-      const double merit2 = fmax(wave_max(m_rd2), fmax(rp_rel, (gap + wave_sum(dgap)) / fmax(1.0, fabs(fval))));
-      if (merit2 <= P.tol_loose && merit2 < saved_merit) {
+      const double merit2 = qpr_repaired_merit(wave_max(m_rd2), rp_rel, gap, wave_sum(dgap), fval);
+      if (qpr_beats_saved(merit2, P.tol_loose, saved_merit)) {
         for (int i = lane; i < k.np; i += 64) XS[i] = X[i];
         for (int js = 0; js < J; ++js) LAMS[js * 64 + lane] = aW3[js * 64 + lane];
         for (int h = 0; h < 2; ++h) { const int i = lane + 64 * h; if (i < k.np) LAMS[(J + (i >> 6)) * 64 + (i & 63)] = i < n ? lamfix[h] : 0.0; }
         have_saved = 1; saved_merit = merit2;
       }
       if (have_saved) { flag = 2; break; }
-    } else if (have_saved && merit > P.tol_loose) { flag = 2; break; }
-    if (merit < 0.9 * best_res) { best_res = merit; stall = 0; } else ++stall;
+    } else if (keep == QPR_KEEP_RETURN) { flag = 2; break; }
+    qpr_progress(merit, best_res, stall);
 
     // ================= factorise (registers, MFMA) and solve for the affine / centering right-hand sides =================
     for (int h = 0; h < 2; ++h) {
@@ -1417,39 +1394,16 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     double a_aff = 1.0, s1 = 0.0, s2 = 0.0;
     double wb[2] = {0.0, 0.0};   // second-order weight of this lane's variable-bound rows (slots J, J + 1): the corrector's right-hand side reads it
     auto row2_body = [&](const Slot& r, int js) {
-      const bool hl = r.valid && r.l > -INFINITY, hu = r.valid && r.u < INFINITY;
       double w = 0.0;
-      if (hl) {
-        const double dt = r.va + r.rpl, dz = -r.zl - (r.zl / r.tl) * dt;
-        if (dt < 0) a_aff = fmin(a_aff, -r.tl / dt);
-        if (dz < 0) a_aff = fmin(a_aff, -r.zl / dz);
-        s1 += r.tl * dz + r.zl * dt; s2 += dt * dz;
-        w -= dt * dz / r.tl;
-      }
-      if (hu) {
-        const double dt = -r.va + r.rpu, dz = -r.zu - (r.zu / r.tu) * dt;
-        if (dt < 0) a_aff = fmin(a_aff, -r.tu / dt);
-        if (dz < 0) a_aff = fmin(a_aff, -r.zu / dz);
-        s1 += r.tu * dz + r.zu * dt; s2 += dt * dz;
-        w += dt * dz / r.tu;
-      }
+      if (qpr_has_lower(r.valid, r.l)) w -= qpr_side_affine(r.tl, r.zl, r.rpl, r.va, a_aff, s1, s2);
+      if (qpr_has_upper(r.valid, r.u)) w += qpr_side_affine(r.tu, r.zu, r.rpu, -r.va, a_aff, s1, s2);
       if (js == J) wb[0] = w;       // (A rows: fused in pass 2; an invalid slot has w = 0)
       if (js == J + 1) wb[1] = w;
     };
     sweep(bv, row2_body);
     a_aff = wave_min(a_aff);
     s1 = wave_sum(s1); s2 = wave_sum(s2);
-    const double mu_aff = fmax(0.0, gap + a_aff * (s1 + a_aff * s2)) / cnt;
-    double sigma = mu > 0 ? (mu_aff / mu) * (mu_aff / mu) * (mu_aff / mu) : 0.0;
-    if (sigma > 1.0) sigma = 1.0;
-    {
-      const double mu_floor = 1e-5 * P.tol * fmax(1.0, fabs(fval)) / cnt;
-      if (mu > 0 && sigma < mu_floor / mu) sigma = fmin(1.0, mu_floor / mu);
-    }
-    const double smu = sigma * mu;
-    // the second-order term is dropped when the affine step is tiny (it then models nothing and makes the iteration
-    // cycle on low-speed instances); this also saves the corrector solve and pass 3 for that iteration
-    const double cw = a_aff >= 0.05 ? 1.0 : 0.0;
+    const QprCenter cen = qpr_centering(gap, cnt, mu, a_aff, s1, s2, P.tol, fval); const double smu = cen.smu, cw = cen.cw;   // (cw = 0: no second-order term, no corrector solve and no pass 3 this iteration)
     WAVE_SYNC();
     STAMP(8);
     if (cw != 0.0) {
@@ -1483,49 +1437,30 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
       if (i < n) DX[i] = R1[i] + smu * R2[i] + DX[i];
     }
     // ================= row phase 3: step length (Mehrotra heuristic on the blocking pair), update =================
-    double amax = 1e300, bp = 0, bdp = 0, bd = 0, bdd = 0, q1 = 0.0, q2 = 0.0;
+    QprBlock blk = qpr_block_none(); double q1 = 0.0, q2 = 0.0;
     double dvb[2] = {0.0, 0.0};
     auto row3a_body = [&](const Slot& r, int js) {
-      const bool hl = r.valid && r.l > -INFINITY, hu = r.valid && r.u < INFINITY;
       const double dv = r.va + smu * r.vc + r.w2;
       if (js < J) aVC[r.ix] = dv;  // keep the full G dx for the update (variable-bound slots: in dvb)
       if (js == J) dvb[0] = dv;
       if (js == J + 1) dvb[1] = dv;
-      if (hl) {
-        const double dta = r.va + r.rpl, dza = -r.zl - (r.zl / r.tl) * dta;
-        const double cl = smu - cw * dta * dza;
-        const double dt = dv + r.rpl, dz = -r.zl + cl / r.tl - (r.zl / r.tl) * dt;
-        if (dt < 0 && -r.tl / dt < amax) { amax = -r.tl / dt; bp = r.tl; bdp = dt; bd = r.zl; bdd = dz; }
-        if (dz < 0 && -r.zl / dz < amax) { amax = -r.zl / dz; bp = r.zl; bdp = dz; bd = r.tl; bdd = dt; }
-        q1 += r.tl * dz + r.zl * dt; q2 += dt * dz;
-      }
-      if (hu) {
-        const double dta = -r.va + r.rpu, dza = -r.zu - (r.zu / r.tu) * dta;
-        const double cu = smu - cw * dta * dza;
-        const double dt = -dv + r.rpu, dz = -r.zu + cu / r.tu - (r.zu / r.tu) * dt;
-        if (dt < 0 && -r.tu / dt < amax) { amax = -r.tu / dt; bp = r.tu; bdp = dt; bd = r.zu; bdd = dz; }
-        if (dz < 0 && -r.zu / dz < amax) { amax = -r.zu / dz; bp = r.zu; bdp = dz; bd = r.tu; bdd = dt; }
-        q1 += r.tu * dz + r.zu * dt; q2 += dt * dz;
-      }
+      if (qpr_has_lower(r.valid, r.l)) qpr_side_block(r.tl, r.zl, qpr_side_step(r.tl, r.zl, r.rpl, r.va, dv, smu, cw), blk, q1, q2);
+      if (qpr_has_upper(r.valid, r.u)) qpr_side_block(r.tu, r.zu, qpr_side_step(r.tu, r.zu, r.rpu, -r.va, -dv, smu, cw), blk, q1, q2);
     };
     sweep(bv, row3a_body);
-    const double amax_w = wave_min(amax);
+    const double amax_w = wave_min(blk.amax);
     double alpha = 1.0;
-    if (amax_w < 1e299) {
+    if (amax_w < QPR_AMAX_SET) {
       // blocking pair = the one on the lane that attains the minimum (first such lane)
-      const unsigned long long msk = __ballot(amax == amax_w);
+      const unsigned long long msk = __ballot(blk.amax == amax_w);
       const int src = __ffsll((long long)msk) - 1;
-      bp = rl(bp, src); bdp = rl(bdp, src); bd = rl(bd, src); bdd = rl(bdd, src);
       q1 = wave_sum(q1); q2 = wave_sum(q2);
-      const double gamma_f = 0.99, gamma_a = 1.0 / (1.0 - gamma_f);
-      const double mufull = fmax(0.0, gap + amax_w * (q1 + amax_w * q2)) / cnt / gamma_a;
-      const double a_h = (-bp + mufull / (bd + amax_w * bdd)) / bdp;
-      alpha = fmin(1.0, fmin(0.99999999 * amax_w, fmax(a_h, gamma_f * amax_w)));
+      alpha = qpr_step_length(gap, cnt, amax_w, q1, q2, rl(blk.bp, src), rl(blk.bdp, src), rl(blk.bd, src), rl(blk.bdd, src));
     }
 #ifdef QP_DEBUG_DUMP
     if (P.dump && P.dump_stage == 5 && b == P.dump_iter && lane == 0 && it < 120) {
       double* o_ = P.dump + 16 * it;
-      o_[8] = a_aff; o_[9] = sigma; o_[10] = alpha; o_[11] = cw; o_[12] = amax_w; o_[13] = (double)stall;
+      o_[8] = a_aff; o_[9] = cen.sigma; o_[10] = alpha; o_[11] = cw; o_[12] = amax_w; o_[13] = (double)stall;
     }
     if (P.dump && b == 0 && P.dump_stage == 4 && it == P.dump_iter) {   // debug: step-length pipeline of this iteration
       double c1 = 0, c2 = 0, c3 = 0, c4 = 0;
@@ -1533,7 +1468,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
       c1 = wave_sum(c1); c2 = wave_sum(c2); c3 = wave_sum(c3); c4 = wave_sum(c4);
       if (lane == 0) {
         double* o_ = P.dump;
-        o_[0] = a_aff; o_[1] = mu_aff; o_[2] = sigma; o_[3] = smu; o_[4] = cw; o_[5] = amax_w; o_[6] = alpha; o_[7] = gap; o_[8] = mu;
+        o_[0] = a_aff; o_[1] = cen.mu_aff; o_[2] = cen.sigma; o_[3] = smu; o_[4] = cw; o_[5] = amax_w; o_[6] = alpha; o_[7] = gap; o_[8] = mu;
         o_[9] = c1; o_[10] = c2; o_[11] = c3; o_[12] = c4; o_[13] = s1; o_[14] = s2; o_[15] = q1; o_[16] = q2;
       }
       for (int i = lane; i < n; i += 64) { P.dump[32 + i] = DX[i]; P.dump[32 + n + i] = R1[i]; P.dump[32 + 2 * n + i] = R2[i]; P.dump[32 + 3 * n + i] = P1[i]; }
@@ -1543,22 +1478,17 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     double xn = 0, zn = 0, s_gap = 0, m_rp = 0;
     auto row3b_body = [&](const Slot& r, int js) {
       if (js >= JT) return;
-      const bool hl = r.valid && r.l > -INFINITY, hu = r.valid && r.u < INFINITY;
       const double dv = r.vc;   // full G dx stored by the previous sweep
       double tl = r.tl, zl = r.zl, tu = r.tu, zu = r.zu;
-      if (hl) {
-        const double dta = r.va + r.rpl, dza = -zl - (zl / tl) * dta;
-        const double cl = smu - cw * dta * dza;
-        const double dt = dv + r.rpl, dz = -zl + cl / tl - (zl / tl) * dt;
-        tl += alpha * dt; zl += alpha * dz;
+      if (qpr_has_lower(r.valid, r.l)) {
+        const QprDir s_ = qpr_side_step(tl, zl, r.rpl, r.va, dv, smu, cw);
+        tl += alpha * s_.dt; zl += alpha * s_.dz;
         aTL[r.ix] = tl; aZL[r.ix] = zl;
         zn = fmax(zn, zl);
       }
-      if (hu) {
-        const double dta = -r.va + r.rpu, dza = -zu - (zu / tu) * dta;
-        const double cu = smu - cw * dta * dza;
-        const double dt = -dv + r.rpu, dz = -zu + cu / tu - (zu / tu) * dt;
-        tu += alpha * dt; zu += alpha * dz;
+      if (qpr_has_upper(r.valid, r.u)) {
+        const QprDir s_ = qpr_side_step(tu, zu, r.rpu, -r.va, -dv, smu, cw);
+        tu += alpha * s_.dt; zu += alpha * s_.dz;
         aTU[r.ix] = tu; aZU[r.ix] = zu;
         zn = fmax(zn, zu);
       }
@@ -1578,15 +1508,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     xn = wave_max(xn); zn = wave_max(zn);
     WAVE_SYNC();
     STAMP(12);
-    // divergence heuristics -> qpOASES exit codes (qpOASES.m:43-47)
-    // a diverging iterate is 'unbounded' (-3) only if it is primal feasible and the objective follows it to -infinity;
-    // with a primal residual it is the signature of an infeasible QP (-2); on a bounded feasible problem (every LTV-MPC QP:
-    // boxed inputs, slacks with positive linear cost) it is an internal failure (-1)
-    if (xn > 1e13) { flag = rp_prev > 1e-6 ? -2 : (fval < -1e13 ? -3 : -1); break; }
-    if (zn > 1e15 && rp_prev > 1e-6) { flag = -2; break; }
-    // once an iterate met tol_loose, a handful of non-improving iterations means the end game lost its numerical
-    // footing: return the saved iterate (this also bounds the iteration tail, i.e. the kernel's drain time)
-    if (stall > (have_saved ? 5 : 25)) { flag = have_saved ? 2 : (rp_prev > 1e-6 ? -2 : (P.polish ? 5 : 1)); break; }   // 5: stalled, the refinement may still certify (else 1)
+    if (qpr_exit_rule(xn, zn, rp_prev, fval, stall, have_saved, P.polish, flag)) break;   // divergence -> qpOASES exit codes; stall
   }
 
   // ---- outputs ----
@@ -1621,7 +1543,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
   if (P.dump && P.dump_stage == 5 && b == P.dump_iter && lane == 0) { double* o_ = P.dump + 16 * 120; o_[4] = (double)flag; for (int i_ = 5; i_ < 48; ++i_) o_[i_] = 0.0; }
 #endif
   if ((flag == 0 || flag == 4 || flag == 5) && P.polish) {
-    const double rho = 1e6, pin = 1e16, rinv = 1.0 / rho;
+    const double rho = QPR_RHO, pin = QPR_PIN, rinv = 1.0 / rho;
     double* PA = rowp(k, R_CB1); double* PB = rowp(k, R_RPL); double* PY = rowp(k, R_CC1); double* PS = rowp(k, R_CB2);
     double* PC = rowp(k, R_RPU); double* PP = rowp(k, R_CC2); double* PZ0 = aW2;   // constraint residual c, CG direction p, zeros
     double* ATR = R1; double* ATP = P3;                                               // A_W'r and A_W'p (n-vectors, by recurrence)
@@ -1632,11 +1554,8 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     }
     for (int js = 0; js < JT; ++js) {
       const int ix = js * 64 + lane;
-      const bool valid = row_valid(k, js);
-      const double l = aL[ix], u = aU[ix], v = aV[ix], lam = aW3[ix];
-      const bool lo = valid && l > -INFINITY && lam > 0 && lam > fabs(v - l);
-      const bool up = valid && u < INFINITY && lam < 0 && -lam > fabs(u - v);
-      PS[ix] = lo ? 1.0 : (up ? -1.0 : 0.0); PY[ix] = ((lo || up) && js < J) ? lam : 0.0;
+      const double lam = aW3[ix]; const QprSide sd = qpr_working_side(row_valid(k, js), aL[ix], aU[ix], aV[ix], lam);
+      PS[ix] = sd.side(); PY[ix] = (sd.active() && js < J) ? lam : 0.0;
     }
     for (int i = lane; i < k.np; i += 64) XS[i] = X[i];   // z of the refinement between attempts (the fall-back copy is no longer needed)
     WAVE_SYNC();
@@ -1646,7 +1565,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     for (int js = 0; js < JT; ++js) {
       const int ix = js * 64 + lane;
       const double sd = PS[ix];
-      PA[ix] = sd != 0.0 ? rho : 0.0; PB[ix] = sd > 0 ? aL[ix] : (sd < 0 ? aU[ix] : 0.0);
+      PA[ix] = sd != 0.0 ? rho : 0.0; PB[ix] = qpr_target(sd, aL[ix], aU[ix]);
       aD[ix] = js < J ? PA[ix] : (sd != 0.0 ? pin : 0.0); aW1[ix] = 0.0; aW2[ix] = 0.0; PC[ix] = 0.0; PP[ix] = 0.0;
     }
     WAVE_SYNC();
@@ -1769,33 +1688,16 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
         const int i = lane + 64 * h;
         if (i < n) {
           const int ix = (J + (i >> 6)) * 64 + (i & 63);
-          const double r = HX[i] + G[i] - P1[i];                    // free variable: must vanish; pinned variable: its bound multiplier
-          const double sc = fmax(1.0, fmax(fabs(G[i]), fmax(fabs(HX[i]), fabs(P1[i]))));
-          const double sd = PS[ix], zi = R2[i], l = aL[ix], u = aU[ix];
-          if (sd == 0.0) m_rd = fmax(m_rd, fabs(r) / sc);
-          else m_sg = fmax(m_sg, (sd > 0 ? -r : r) / sc);
-          aVC[ix] = sd != 0.0 ? r : 0.0;                            // multiplier of the variable-bound row
-          double viol = 0.0;
-          if (l > -INFINITY && zi < l) viol = l - zi;
-          if (u < INFINITY && zi > u) viol = fmax(viol, zi - u);
-          m_rp = fmax(m_rp, viol / fmax(1.0, fabs(zi)));
-          fl2 += 0.5 * zi * HX[i] + G[i] * zi + 0.0 * r;   // (0 * r: a non-finite residual must poison the sum -- fmax drops NaN operands)
+          const double zi = R2[i]; const QprVar o = qpr_kkt_var(HX[i], G[i], P1[i], PS[ix], zi, aL[ix], aU[ix], m_rd, m_sg, m_rp);
+          aVC[ix] = o.y;                                            // multiplier of the variable-bound row
+          fl2 += 0.5 * zi * HX[i] + G[i] * zi + 0.0 * o.r;   // (0 * r: a non-finite residual must poison the sum -- fmax drops NaN operands)
         }
       }
       for (int js = 0; js < J; ++js) {
         const int ix = js * 64 + lane;
         if (row_valid(k, js)) {
-          const double l = aL[ix], u = aU[ix], v = aVA[ix], y = aVC[ix], sd = PS[ix];
-          double sc = fmax(1.0, fabs(v));
-          if (l > -INFINITY) sc = fmax(sc, fabs(l));
-          if (u < INFINITY) sc = fmax(sc, fabs(u));
-          double viol = 0.0;
-          if (sd != 0.0) { viol = fabs(v - PB[ix]); m_cp = fmax(m_cp, fabs(y) * viol); }
-          if (l > -INFINITY && v < l) viol = fmax(viol, l - v);
-          if (u < INFINITY && v > u) viol = fmax(viol, v - u);
-          m_rp = fmax(m_rp, viol / sc);
-          m_sg = fmax(m_sg, (sd > 0 ? -y : (sd < 0 ? y : 0.0)) / fmax(1.0, fabs(y)));
-          fl2 += 0.0 * (v + y);
+          const double sd = PS[ix];
+          qpr_kkt_row(aL[ix], aU[ix], aVA[ix], aVC[ix], sd, sd != 0.0 ? PB[ix] : 0.0, m_rp, m_sg, m_cp, fl2);
         }
       }
       m_rd = wave_max(m_rd); m_rp = wave_max(m_rp); m_sg = wave_max(m_sg); m_cp = wave_max(m_cp);
@@ -1804,33 +1706,24 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
       if (P.dump && b < 32 && P.dump_stage == 3 && lane == 0) { double* o_ = P.dump + 64 * b; o_[0] = m_rd; o_[1] = m_rp; o_[2] = m_sg; o_[3] = m_cp; o_[5] = f2; }
       if (P.dump && P.dump_stage == 5 && b == P.dump_iter && lane == 0 && attempt < 8) { double* o_ = P.dump + 16 * 120 + 8 + 5 * attempt; o_[0] = 1.0; o_[1] = m_rd; o_[2] = m_rp; o_[3] = m_sg; o_[4] = m_cp; }
 #endif
-      // acceptance: relative stationarity 1e-8 (the 1e8 slack cost of ltvmpc_*.m:35 puts cancellations of 1e8 eps into A'y of
-      // the active soft rows: the floor of any fp64 evaluation of this residual; qpOASES' own terminationTolerance is
-      // 5e6 eps = 1.1e-9, qpOASES_options.m:190), feasibility and complementarity 1e-10, multipliers of the right sign
-      // (round-off level wrong signs are zeroed)
-      pok = m_rd <= 1e-8 && m_rp <= 1e-10 && m_cp <= 1e-10 * fmax(1.0, fabs(f2)) && m_sg <= 1e-8 && fabs(f2) < INFINITY;   // (f2 is NaN if anything in the candidate is not finite)
-      if (!pok) flag_polished = !(fabs(f2) < INFINITY) ? -5 : (!(m_rd <= 1e-8) ? -1 : (!(m_rp <= 1e-10) ? -2 : (!(m_sg <= 1e-8) ? -4 : -3)));
-      if (!pok && m_rd <= 1e-8 && attempt < QP_REFINE_ATTEMPTS - 1 && (m_rp > 1e-10 || m_sg > 1e-8)) {
+      const int rej = qpr_accept(m_rd, m_rp, m_sg, m_cp, f2);   // acceptance: stationarity, feasibility, complementarity, multiplier signs
+      pok = rej == 0; if (!pok) flag_polished = rej;
+      if (!pok && attempt < QP_REFINE_ATTEMPTS - 1 && qpr_correctable(m_rd, m_rp, m_sg)) {
         // single correction of the working set: add the most violated inactive row, else drop the worst wrong-sign row
         double my = 0.0; int myix = -1; double myside = 0.0;
-        const bool add = m_rp > 1e-10;
+        const bool add = qpr_correct_by_add(m_rp);
         for (int js = 0; js < JT; ++js) {
           const int ix = js * 64 + lane;
           if (!row_valid(k, js)) continue;
           const double l = aL[ix], u = aU[ix], sd = PS[ix];
-          const double v = js < J ? aVA[ix] : R2[(js - J) * 64 + lane];
+          const double v = js < J ? aVA[ix] : vec_read(R2 + (js - J) * 64 + lane);
           if (add) {
             if (sd != 0.0) continue;
-            double sc = fmax(1.0, fabs(v));
-            if (js < J) { if (l > -INFINITY) sc = fmax(sc, fabs(l)); if (u < INFINITY) sc = fmax(sc, fabs(u)); }
-            const double vl = l > -INFINITY ? (l - v) / sc : -1.0, vu = u < INFINITY ? (v - u) / sc : -1.0;
-            const double vv = fmax(vl, vu);
-            if (vv > my) { my = vv; myix = ix; myside = vl >= vu ? 1.0 : -1.0; }
+            const QprAdd a_ = qpr_add_score(l, u, v, js < J);
+            if (a_.score > my) { my = a_.score; myix = ix; myside = a_.side(); }
           } else {
             if (sd == 0.0) continue;
-            const double y = aVC[ix];
-            const double sc = js < J ? fmax(1.0, fabs(y)) : 1.0;
-            const double sg = (sd > 0 ? -y : y) / sc;
+            const double sg = qpr_drop_score(sd, aVC[ix], js < J);
             if (sg > my) { my = sg; myix = ix; myside = 0.0; }
           }
         }
@@ -1841,7 +1734,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
         WAVE_SYNC();
         continue;   // next attempt from the point reached (R2) with the corrected working set
       }
-      if (!pok && !(m_rd <= 1e-8) && attempt < QP_REFINE_ATTEMPTS - 1 && m_rd <= 1e-4) {   // stationarity above the floor: one more exact step from here
+      if (!pok && attempt < QP_REFINE_ATTEMPTS - 1 && qpr_one_more_step(m_rd)) {   // stationarity above the floor: one more exact step from here
         for (int i = lane; i < k.np; i += 64) XS[i] = R2[i];
         for (int js = 0; js < J; ++js) { const int ix = js * 64 + lane; PY[ix] = PS[ix] != 0.0 ? aVC[ix] : 0.0; }
         WAVE_SYNC();
@@ -1852,11 +1745,10 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
         for (int i = lane; i < k.np; i += 64) X[i] = R2[i];
         for (int js = 0; js < JT; ++js) {
           const int ix = js * 64 + lane;
-          const double y = aVC[ix], sd = PS[ix];
-          aW3[ix] = sd > 0 ? fmax(y, 0.0) : (sd < 0 ? fmin(y, 0.0) : 0.0);
+          aW3[ix] = qpr_clamp_multiplier(PS[ix], aVC[ix]);
         }
         flag_polished = 1 + attempt;
-        fval_s = f2; merit_s = fmax(m_rd, fmax(m_rp, m_cp / fmax(1.0, fabs(f2))));
+        fval_s = f2; merit_s = qpr_refined_merit(m_rd, m_rp, m_cp, f2);
         flag = 0;
       }
       WAVE_SYNC();
@@ -1884,7 +1776,7 @@ template <int T, int NB> __global__ __launch_bounds__(64, 1) void qp_solve_kerne
     hx_full(X);
     WAVE_SYNC();
     double fl = 0;
-    for (int h = 0; h < 2; ++h) { const int i = lane + 64 * h; if (i < n) fl += 0.5 * X[i] * HX[i] + G[i] * X[i]; }
+    for (int h = 0; h < 2; ++h) { const int i = lane + 64 * h; if (i < n) fl += qpr_obj_term(X[i], HX[i], G[i]); }
     fval_s = wave_sum(fl);
   }
   STAMP(13);

@@ -25,6 +25,9 @@
 //     triangular solves: one barrier per block step;
 //   * wave-uniform scalars are reduced through a small LDS scratch so that every wave takes the same branches.
 //
+// The arithmetic of a row and the decisions of an iteration and of the refinement are qp_rules.h's, shared with the one-wavefront
+// kernel: this file keeps where the data lives (row arrays, LDS vectors) and how it is reduced across waves (red_put / red_sum).
+//
 // Data layout of the workspace: see qp_solver.hip (qp_prep_kernel).  fp64 MFMA lane maps (cdna_hip_programming.md
 // section 3): A[i=l&15][k=l>>4], B[k=l>>4][j=l&15], C/D col = l&15, row = (l>>4) + 4*reg.
 #include <hip/hip_runtime.h>
@@ -32,6 +35,7 @@
 #include <stdint.h>
 #include "qp_solver.h"
 #include "qp_lane.h"
+#include "qp_rules.h"
 
 #define AINL __attribute__((always_inline))
 
@@ -141,13 +145,8 @@ DEVINL int diag_factor(int c, int q, v4d& Ud, v4d& Yk, double floor_abs) {
 #define STAMP_OUT do { } while (0)
 #endif
 
-#ifndef QP_REFINE_ATTEMPTS
-#define QP_REFINE_ATTEMPTS 3
-#endif
-
 // one owner-layout row as the sweeps see it
 struct Row { double l, u, tl, tu, zl, zu, v; };
-template <int C> struct IC { static constexpr int value = C; };
 struct TagKeep { static constexpr bool value = true; };
 struct TagInit { static constexpr bool value = false; };
 
@@ -526,19 +525,9 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
   // residuals and barrier weights of one row: what pass 1 needs goes to the row arrays D, W1, W2, W3 (A rows) or the
   // variable-row vectors; accumulates the complementarity sum and the relative primal residual
   auto row_weights = [&](int js, const Row& r, double& s_gap, double& m_rp) AINL {
-    const bool hl = r.l > -INFINITY, hu = r.u < INFINITY;
-    const double rpl = hl ? r.v - r.l - r.tl : 0.0, rpu = hu ? r.u - r.v - r.tu : 0.0;
-    const double dl = hl ? r.zl / r.tl : 0.0, du = hu ? r.zu / r.tu : 0.0;
-    const double D = dl + du;
-    const double W1 = -dl * rpl + du * rpu;                               // affine rhs weight
-    const double W2 = (hl ? 1.0 / r.tl : 0.0) - (hu ? 1.0 / r.tu : 0.0);  // centering weight (times sigma*mu)
-    const double W3 = (hl ? r.zl : 0.0) - (hu ? r.zu : 0.0);              // current multiplier (for the dual residual)
-    if (js < J) { const int ix = js * 64 + lane; aD[ix] = D; aW1[ix] = W1; aW2[ix] = W2; aW3[ix] = W3; }
-    else { const int i = (js - J) * 64 + lane; if (i < np) { DV_(i) = D; W1V_(i) = W1; W2V_(i) = W2; LV_(i) = W3; } }
-    s_gap += (hl ? r.tl * r.zl : 0.0) + (hu ? r.tu * r.zu : 0.0);
-    const double sc = fmax(1.0, fabs(r.v));
-    if (hl) m_rp = fmax(m_rp, fabs(rpl) / fmax(sc, fabs(r.l)));
-    if (hu) m_rp = fmax(m_rp, fabs(rpu) / fmax(sc, fabs(r.u)));
+    const QprRow o = qpr_row_weights(true, r.l, r.u, r.v, r.tl, r.tu, r.zl, r.zu, s_gap, m_rp);
+    if (js < J) { const int ix = js * 64 + lane; aD[ix] = o.D; aW1[ix] = o.W1; aW2[ix] = o.W2; aW3[ix] = o.W3; }
+    else { const int i = (js - J) * 64 + lane; if (i < np) { DV_(i) = o.D; W1V_(i) = o.W1; W2V_(i) = o.W2; LV_(i) = o.W3; } }
   };
   double gap = 0.0, rp_rel = 0.0;   // carried across iterations (produced by the update sweep)
 
@@ -1112,71 +1101,51 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
     // objective, dual residual (every wave computes the same numbers from LDS)
     double fl = 0, m_rd = 0;
     for (int i = lane; i < n; i += 64) {
-      const double gz = P3_(i) + LV_(i);
-      fl += 0.5 * X_(i) * HX_(i) + G_(i) * X_(i);
-      const double sc = fmax(1.0, fmax(fabs(G_(i)), fmax(fabs(HX_(i)), fabs(gz))));
-      m_rd = fmax(m_rd, fabs(HX_(i) + G_(i) - gz) / sc);
+      fl += qpr_obj_term(X_(i), HX_(i), G_(i));
+      m_rd = fmax(m_rd, qpr_rd_term(HX_(i), G_(i), P3_(i) + LV_(i)));
     }
     const double fval = wave_sum_rl(fl);
     const double rd_rel = wave_max_rl(m_rd);
-    const double gap_rel = gap / fmax(1.0, fabs(fval));
-    // (fmax drops NaN operands: an iterate with NaN in it -- a step along a direction from a broken-down factorisation, 0 * NaN --
-    //  would read as merit 0.  Its objective is NaN, and so must the merit be: the best saved iterate is returned then.)
-    const double merit = (fabs(fval) < INFINITY && fabs(gap_rel) < INFINITY) ? fmax(rd_rel, fmax(rp_rel, gap_rel)) : INFINITY;
+    const QprMerit mer = qpr_merit(fval, gap, rd_rel, rp_rel); const double gap_rel = mer.gap_rel, merit = mer.merit;
     fval_s = fval; merit_s = merit;
     const bool res_ok = merit <= P.tol;
     if (!(merit < INFINITY)) { flag = have_saved ? 2 : -1; break; }
-    if (merit <= P.tol_loose && merit < saved_merit) {
+    const int keep = qpr_keep_rule(merit, rp_rel, gap_rel, P.tol_loose, saved_merit, have_saved);
+    if (keep == QPR_KEEP_SAVE) {
       for (int i = tid; i < np; i += NTH) XS[i] = X_(i);
       for (int js = w; js < JT; js += W) {
         const int ix = js * 64 + lane;
         if (js < J) LAMS[ix] = aW3[ix]; else { const int i = (js - J) * 64 + lane; LAMS[ix] = i < np ? LV_(i) : 0.0; }
       }
       have_saved = 1; saved_merit = merit;
-    } else if (merit > P.tol_loose && rp_rel <= P.tol_loose && gap_rel <= P.tol_loose) {
-      // Only the dual residual is in the way: repair the certificate of a *copy* of the iterate by moving r_d into the
-      // bound multipliers, where a finite bound of the right sign exists.
+    } else if (keep == QPR_KEEP_REPAIR) {   // only the dual residual is in the way: certificate repair of a copy
       double dgap_l = 0, m_rd2_l = 0;
       for (int js = w; js < JT; js += W) {
         if (js < J) continue;
         const int i = (js - J) * 64 + lane, ix = js * 64 + lane;
-        if (i < n) {
-          const double l = aL[ix], u = aU[ix], v = aV[ix];
-          const double lam = LV_(i), gz = P3_(i) + lam, rr = HX_(i) + G_(i) - gz, lam2 = lam + rr;
-          const bool ok = lam2 >= 0 ? l > -INFINITY : u < INFINITY;
-          if (ok) dgap_l += fabs(rr) * fmax(0.0, lam2 >= 0 ? v - l : u - v);
-          else {
-            const double sc = fmax(1.0, fmax(fabs(G_(i)), fmax(fabs(HX_(i)), fabs(gz))));
-            m_rd2_l = fmax(m_rd2_l, fabs(rr) / sc);
-          }
-        }
+        if (i < n) qpr_repair(LV_(i), P3_(i), HX_(i), G_(i), aL[ix], aU[ix], aV[ix], dgap_l, m_rd2_l);
       }
       red_put(0, wave_sum_rl(dgap_l)); red_put(1, wave_max_rl(m_rd2_l));
       __syncthreads();
-      const double merit2 = fmax(red_max(1), fmax(rp_rel, (gap + red_sum(0)) / fmax(1.0, fabs(fval))));
+      const double rd2 = red_max(1), merit2 = qpr_repaired_merit(rd2, rp_rel, gap, red_sum(0), fval);
       red_next();
-      if (merit2 <= P.tol_loose && merit2 < saved_merit) {
+      if (qpr_beats_saved(merit2, P.tol_loose, saved_merit)) {
         for (int i = tid; i < np; i += NTH) XS[i] = X_(i);
         for (int js = w; js < JT; js += W) {
           const int ix = js * 64 + lane;
           if (js < J) LAMS[ix] = aW3[ix];
           else {
             const int i = (js - J) * 64 + lane;
-            double lf = 0.0;
-            if (i < n) {
-              const double l = aL[ix], u = aU[ix];
-              const double lam = LV_(i), rr = HX_(i) + G_(i) - (P3_(i) + lam), lam2 = lam + rr;
-              const bool ok = lam2 >= 0 ? l > -INFINITY : u < INFINITY;
-              lf = ok ? lam2 : lam;
-            }
+            double lf = 0.0, unused_gap = 0, unused_rd = 0;   // (the repaired multiplier once more: the sweep above kept only the sums)
+            if (i < n) lf = qpr_repair(LV_(i), P3_(i), HX_(i), G_(i), aL[ix], aU[ix], 0.0, unused_gap, unused_rd);
             LAMS[ix] = lf;
           }
         }
         have_saved = 1; saved_merit = merit2;
       }
       if (have_saved) { flag = 2; break; }
-    } else if (have_saved && merit > P.tol_loose) { flag = 2; break; }
-    if (merit < 0.9 * best_res) { best_res = merit; stall = 0; } else ++stall;
+    } else if (keep == QPR_KEEP_RETURN) { flag = 2; break; }
+    qpr_progress(merit, best_res, stall);
 
     // ================= factorise with the affine / centering right-hand sides riding along =================
     for (int i = tid; i < np; i += NTH) {
@@ -1290,39 +1259,16 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       const int ix = js * 64 + lane;
       const Row r = ld_row(ix);
       const double va = aVA[ix];
-      const bool hl = r.l > -INFINITY, hu = r.u < INFINITY;
       double wv = 0.0;
-      if (hl) {
-        const double dl = r.zl / r.tl;
-        const double dt = va + (r.v - r.l - r.tl), dz = -r.zl - dl * dt;
-        if (dt < 0) a_aff = fmin(a_aff, -r.tl / dt);
-        if (dz < 0) a_aff = fmin(a_aff, -r.zl / dz);
-        s1 += r.tl * dz + r.zl * dt; s2 += dt * dz;
-        wv -= dt * dz / r.tl;
-      }
-      if (hu) {
-        const double du = r.zu / r.tu;
-        const double dt = -va + (r.u - r.v - r.tu), dz = -r.zu - du * dt;
-        if (dt < 0) a_aff = fmin(a_aff, -r.tu / dt);
-        if (dz < 0) a_aff = fmin(a_aff, -r.zu / dz);
-        s1 += r.tu * dz + r.zu * dt; s2 += dt * dz;
-        wv += dt * dz / r.tu;
-      }
+      if (qpr_has_lower(true, r.l)) wv -= qpr_side_affine(r.tl, r.zl, r.v - r.l - r.tl, va, a_aff, s1, s2);
+      if (qpr_has_upper(true, r.u)) wv += qpr_side_affine(r.tu, r.zu, r.u - r.v - r.tu, -va, a_aff, s1, s2);
       if (js >= J) { const int i = (js - J) * 64 + lane; if (i < np) W1V_(i) = wv; }   // (A rows: fused in pass 2)
     }
     red_put(0, wave_min_rl(a_aff)); red_put(1, wave_sum_rl(s1)); red_put(2, wave_sum_rl(s2));
     __syncthreads();
     a_aff = red_min(0); s1 = red_sum(1); s2 = red_sum(2);
     red_next();
-    const double mu_aff = fmax(0.0, gap + a_aff * (s1 + a_aff * s2)) / cnt;
-    double sigma = mu > 0 ? (mu_aff / mu) * (mu_aff / mu) * (mu_aff / mu) : 0.0;
-    if (sigma > 1.0) sigma = 1.0;
-    {
-      const double mu_floor = 1e-5 * P.tol * fmax(1.0, fabs(fval)) / cnt;
-      if (mu > 0 && sigma < mu_floor / mu) sigma = fmin(1.0, mu_floor / mu);
-    }
-    const double smu = sigma * mu;
-    const double cw = a_aff >= 0.05 ? 1.0 : 0.0;   // second-order term dropped when the affine step is tiny
+    const QprCenter cen = qpr_centering(gap, cnt, mu, a_aff, s1, s2, P.tol, fval); const double smu = cen.smu, cw = cen.cw;   // (cw = 0: second-order term dropped, the affine step is tiny)
     STAMP(9);
     if (cw != 0.0) {
       // ================= corrector: A' w_cor came out of the fused pass 2 =================
@@ -1338,57 +1284,32 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
     }
     STAMP(11);
     // ================= row phase 3: step length (Mehrotra heuristic on the blocking pair) =================
-    double amax = 1e300, bp = 0, bdp = 0, bd = 0, bdd = 0, q1 = 0.0, q2 = 0.0;
+    QprBlock blk = qpr_block_none(); double q1 = 0.0, q2 = 0.0;
     for (int js = w; js < JT; js += W) {
       const int ix = js * 64 + lane;
       const Row r = ld_row(ix);
       const double va = aVA[ix];
-      const bool hl = r.l > -INFINITY, hu = r.u < INFINITY;
       const double dv = va + smu * aVC[ix] + aWC[ix];
       aVC[ix] = dv;  // keep the full G dx for the update
-      if (hl) {
-        const double dl = r.zl / r.tl;
-        const double rpl = r.v - r.l - r.tl;
-        const double dta = va + rpl, dza = -r.zl - dl * dta;
-        const double cl = smu - cw * dta * dza;
-        const double dt = dv + rpl, dz = -r.zl + cl / r.tl - dl * dt;
-        if (dt < 0 && -r.tl / dt < amax) { amax = -r.tl / dt; bp = r.tl; bdp = dt; bd = r.zl; bdd = dz; }
-        if (dz < 0 && -r.zl / dz < amax) { amax = -r.zl / dz; bp = r.zl; bdp = dz; bd = r.tl; bdd = dt; }
-        q1 += r.tl * dz + r.zl * dt; q2 += dt * dz;
-      }
-      if (hu) {
-        const double du = r.zu / r.tu;
-        const double rpu = r.u - r.v - r.tu;
-        const double dta = -va + rpu, dza = -r.zu - du * dta;
-        const double cu = smu - cw * dta * dza;
-        const double dt = -dv + rpu, dz = -r.zu + cu / r.tu - du * dt;
-        if (dt < 0 && -r.tu / dt < amax) { amax = -r.tu / dt; bp = r.tu; bdp = dt; bd = r.zu; bdd = dz; }
-        if (dz < 0 && -r.zu / dz < amax) { amax = -r.zu / dz; bp = r.zu; bdp = dz; bd = r.tu; bdd = dt; }
-        q1 += r.tu * dz + r.zu * dt; q2 += dt * dz;
-      }
+      if (qpr_has_lower(true, r.l)) qpr_side_block(r.tl, r.zl, qpr_side_step(r.tl, r.zl, r.v - r.l - r.tl, va, dv, smu, cw), blk, q1, q2);
+      if (qpr_has_upper(true, r.u)) qpr_side_block(r.tu, r.zu, qpr_side_step(r.tu, r.zu, r.u - r.v - r.tu, -va, -dv, smu, cw), blk, q1, q2);
     }
     {
-      const double amax_w = wave_min_rl(amax);
-      if (amax_w < 1e299) {
-        const unsigned long long msk = __ballot(amax == amax_w);
+      const double amax_w = wave_min_rl(blk.amax);
+      if (amax_w < QPR_AMAX_SET) {
+        const unsigned long long msk = __ballot(blk.amax == amax_w);
         const int src = __ffsll((long long)msk) - 1;
-        bp = rl(bp, src); bdp = rl(bdp, src); bd = rl(bd, src); bdd = rl(bdd, src);
+        blk.bp = rl(blk.bp, src); blk.bdp = rl(blk.bdp, src); blk.bd = rl(blk.bd, src); blk.bdd = rl(blk.bdd, src);
       }
-      red_put(0, amax_w); red_put(1, bp); red_put(2, bdp); red_put(3, bd); red_put(4, bdd); red_put(5, wave_sum_rl(q1)); red_put(6, wave_sum_rl(q2));
+      red_put(0, amax_w); red_put(1, blk.bp); red_put(2, blk.bdp); red_put(3, blk.bd); red_put(4, blk.bdd); red_put(5, wave_sum_rl(q1)); red_put(6, wave_sum_rl(q2));
     }
     __syncthreads();
     double alpha = 1.0;
     {
-      double amax_g = 1e300; int wsel = 0;
+      double amax_g = QPR_AMAX_UNSET; int wsel = 0;
       for (int i = 0; i < W; ++i) { const double a_ = red_get(0, i); if (a_ < amax_g) { amax_g = a_; wsel = i; } }
       q1 = red_sum(5); q2 = red_sum(6);
-      if (amax_g < 1e299) {
-        bp = red_get(1, wsel); bdp = red_get(2, wsel); bd = red_get(3, wsel); bdd = red_get(4, wsel);
-        const double gamma_f = 0.99, gamma_a = 1.0 / (1.0 - gamma_f);
-        const double mufull = fmax(0.0, gap + amax_g * (q1 + amax_g * q2)) / cnt / gamma_a;
-        const double a_h = (-bp + mufull / (bd + amax_g * bdd)) / bdp;
-        alpha = fmin(1.0, fmin(0.99999999 * amax_g, fmax(a_h, gamma_f * amax_g)));
-      }
+      if (amax_g < QPR_AMAX_SET) alpha = qpr_step_length(gap, cnt, amax_g, q1, q2, red_get(1, wsel), red_get(2, wsel), red_get(3, wsel), red_get(4, wsel));
     }
     red_next();
     STAMP(12);
@@ -1398,24 +1319,15 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       const int ix = js * 64 + lane;
       Row r = ld_row(ix);
       const double va = aVA[ix], dv = aVC[ix];
-      const bool hl = r.l > -INFINITY, hu = r.u < INFINITY;
-      if (hl) {
-        const double dl = r.zl / r.tl;
-        const double rpl = r.v - r.l - r.tl;
-        const double dta = va + rpl, dza = -r.zl - dl * dta;
-        const double cl = smu - cw * dta * dza;
-        const double dt = dv + rpl, dz = -r.zl + cl / r.tl - dl * dt;
-        r.tl += alpha * dt; r.zl += alpha * dz;
+      if (qpr_has_lower(true, r.l)) {
+        const QprDir s_ = qpr_side_step(r.tl, r.zl, r.v - r.l - r.tl, va, dv, smu, cw);
+        r.tl += alpha * s_.dt; r.zl += alpha * s_.dz;
         aTL[ix] = r.tl; aZL[ix] = r.zl;
         zn = fmax(zn, r.zl);
       }
-      if (hu) {
-        const double du = r.zu / r.tu;
-        const double rpu = r.u - r.v - r.tu;
-        const double dta = -va + rpu, dza = -r.zu - du * dta;
-        const double cu = smu - cw * dta * dza;
-        const double dt = -dv + rpu, dz = -r.zu + cu / r.tu - du * dt;
-        r.tu += alpha * dt; r.zu += alpha * dz;
+      if (qpr_has_upper(true, r.u)) {
+        const QprDir s_ = qpr_side_step(r.tu, r.zu, r.u - r.v - r.tu, -va, -dv, smu, cw);
+        r.tu += alpha * s_.dt; r.zu += alpha * s_.dz;
         aTU[ix] = r.tu; aZU[ix] = r.zu;
         zn = fmax(zn, r.zu);
       }
@@ -1431,12 +1343,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
     gap = red_sum(0); rp_rel = red_max(1); xn = red_max(2); zn = red_max(3);
     red_next();
     STAMP(13);
-    // divergence heuristics -> qpOASES exit codes (qpOASES.m:43-47)
-    // a diverging iterate is 'unbounded' (-3) only if it is primal feasible and the objective follows it to -infinity; with a
-    // primal residual it is the signature of an infeasible QP (-2); otherwise an internal failure (-1)
-    if (xn > 1e13) { flag = rp_prev > 1e-6 ? -2 : (fval < -1e13 ? -3 : -1); break; }
-    if (zn > 1e15 && rp_prev > 1e-6) { flag = -2; break; }
-    if (stall > (have_saved ? 5 : 25)) { flag = have_saved ? 2 : (rp_prev > 1e-6 ? -2 : (P.polish ? 5 : 1)); break; }   // 5: stalled, the refinement may still certify (else 1)
+    if (qpr_exit_rule(xn, zn, rp_prev, fval, stall, have_saved, P.polish, flag)) break;   // divergence -> qpOASES exit codes; stall
   }
   __syncthreads();
 
@@ -1465,7 +1372,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
   // n-vectors: Z = R2 (the point), ATR = R1, ATP = P3 (A_W'r, A_W'p by recurrence), DX work vector, P1 / P2 pass outputs;
   // variable rows as n-vectors: DV pin weight (read by factor_solve2), W1V side, W2V bound value.
   if ((flag == 0 || flag == 4 || flag == 5) && P.polish) {
-    const double rho = 1e6, pin = 1e16, rinv = 1.0 / rho;
+    const double rho = QPR_RHO, pin = QPR_PIN, rinv = 1.0 / rho;
     double* PS = rowarr(R_CB2); double* PA = rowarr(R_CB1); double* PB = rowarr(R_RPL);
     double* PY = rowarr(R_CC1); double* PC = rowarr(R_RPU); double* PP = rowarr(R_CC2);
     double* QV = aVA; double* YV = aVC;
@@ -1475,9 +1382,8 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       const double l = aL[ix], u = aU[ix], v = aV[ix];
       double lam;
       if (js < J) lam = aW3[ix]; else { const int i = (js - J) * 64 + lane; lam = i < np ? LV_(i) : 0.0; }
-      const bool lo = l > -INFINITY && lam > 0 && lam > fabs(v - l);
-      const bool up = u < INFINITY && lam < 0 && -lam > fabs(u - v);
-      PS[ix] = lo ? 1.0 : (up ? -1.0 : 0.0); PY[ix] = ((lo || up) && js < J) ? lam : 0.0;
+      const QprSide sd = qpr_working_side(true, l, u, v, lam);
+      PS[ix] = sd.side(); PY[ix] = (sd.active() && js < J) ? lam : 0.0;
     }
     for (int i = tid; i < np; i += NTH) XS[i] = X_(i);   // z of the refinement between attempts (the fall-back copy is no longer needed)
     __syncthreads();
@@ -1546,7 +1452,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
       for (int js = w; js < JT; js += W) {
         const int ix = js * 64 + lane;
         const double sd = PS[ix];
-        const double tgt = sd > 0 ? aL[ix] : (sd < 0 ? aU[ix] : 0.0);
+        const double tgt = qpr_target(sd, aL[ix], aU[ix]);
         PA[ix] = sd != 0.0 ? rho : 0.0; PB[ix] = tgt; PC[ix] = 0.0; PP[ix] = 0.0;
         if (js < J) { aD[ix] = sd != 0.0 ? rho : 0.0; aW1[ix] = 0.0; aW2[ix] = 0.0; }   // (W3 keeps the interior-point multipliers: they are returned if the refinement is rejected)
         else { const int i = (js - J) * 64 + lane; if (i < np) { DV_(i) = sd != 0.0 ? pin : 0.0; W1V_(i) = sd; W2V_(i) = tgt; } }
@@ -1650,47 +1556,26 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
         double m_rd = 0, m_rp = 0, m_sg = 0, m_cp = 0, fl2 = 0;
         for (int i = tid; i < n; i += NTH) {
           const int ix = vix(i);
-          const double r = HX_(i) + G_(i) - P1_(i);                   // free variable: must vanish; pinned variable: its bound multiplier
-          const double sc = fmax(1.0, fmax(fabs(G_(i)), fmax(fabs(HX_(i)), fabs(P1_(i)))));
-          const double sd = W1V_(i), zi = R2_(i), l = aL[ix], u = aU[ix];
-          if (sd == 0.0) m_rd = fmax(m_rd, fabs(r) / sc);
-          else m_sg = fmax(m_sg, (sd > 0 ? -r : r) / sc);
-          YV[ix] = sd != 0.0 ? r : 0.0;                               // multiplier of the variable-bound row
-          double viol = 0.0;
-          if (l > -INFINITY && zi < l) viol = l - zi;
-          if (u < INFINITY && zi > u) viol = fmax(viol, zi - u);
-          m_rp = fmax(m_rp, viol / fmax(1.0, fabs(zi)));
-          fl2 += 0.5 * zi * HX_(i) + G_(i) * zi + 0.0 * r;   // (0 * r: a non-finite residual must poison the sum -- fmax drops NaN operands)
+          const double zi = R2_(i); const QprVar o = qpr_kkt_var(HX_(i), G_(i), P1_(i), W1V_(i), zi, aL[ix], aU[ix], m_rd, m_sg, m_rp);
+          YV[ix] = o.y;                                               // multiplier of the variable-bound row
+          fl2 += 0.5 * zi * HX_(i) + G_(i) * zi + 0.0 * o.r;   // (0 * r: a non-finite residual must poison the sum -- fmax drops NaN operands)
         }
         for (int js = w; js < J; js += W) {
           const int ix = js * 64 + lane;
           const double l = aL[ix], u = aU[ix], v = QV[ix], y = YV[ix], sd = PS[ix];
-          if (l > -INFINITY || u < INFINITY) {   // (padding rows carry infinite bounds)
-            double sc = fmax(1.0, fabs(v));
-            if (l > -INFINITY) sc = fmax(sc, fabs(l));
-            if (u < INFINITY) sc = fmax(sc, fabs(u));
-            double viol = 0.0;
-            if (sd != 0.0) { viol = fabs(v - PB[ix]); m_cp = fmax(m_cp, fabs(y) * viol); }
-            if (l > -INFINITY && v < l) viol = fmax(viol, l - v);
-            if (u < INFINITY && v > u) viol = fmax(viol, v - u);
-            m_rp = fmax(m_rp, viol / sc);
-            m_sg = fmax(m_sg, (sd > 0 ? -y : (sd < 0 ? y : 0.0)) / fmax(1.0, fabs(y)));
-            fl2 += 0.0 * (v + y);
-          }
+          if (l > -INFINITY || u < INFINITY) qpr_kkt_row(l, u, v, y, sd, sd != 0.0 ? PB[ix] : 0.0, m_rp, m_sg, m_cp, fl2);   // (padding rows: infinite bounds)
         }
         red_put(0, wave_max_rl(m_rd)); red_put(1, wave_max_rl(m_rp)); red_put(2, wave_max_rl(m_sg)); red_put(3, wave_max_rl(m_cp)); red_put(4, wave_sum_rl(fl2));
         __syncthreads();
         m_rd = red_max(0); m_rp = red_max(1); m_sg = red_max(2); m_cp = red_max(3);
         const double f2 = red_sum(4);
         red_next();
-        // acceptance: relative stationarity 1e-8, feasibility and complementarity 1e-10, multipliers of the right sign (the same
-        // thresholds as the one-wavefront kernel)
-        pok = m_rd <= 1e-8 && m_rp <= 1e-10 && m_cp <= 1e-10 * fmax(1.0, fabs(f2)) && m_sg <= 1e-8 && fabs(f2) < INFINITY;   // (f2 is NaN if anything in the candidate is not finite)
-        if (!pok) flag_polished = !(fabs(f2) < INFINITY) ? -5 : (!(m_rd <= 1e-8) ? -1 : (!(m_rp <= 1e-10) ? -2 : (!(m_sg <= 1e-8) ? -4 : -3)));
-        if (!pok && m_rd <= 1e-8 && attempt < QP_REFINE_ATTEMPTS - 1 && (m_rp > 1e-10 || m_sg > 1e-8)) {
+        const int rej = qpr_accept(m_rd, m_rp, m_sg, m_cp, f2);   // acceptance: stationarity, feasibility, complementarity, multiplier signs
+        pok = rej == 0; if (!pok) flag_polished = rej;
+        if (!pok && attempt < QP_REFINE_ATTEMPTS - 1 && qpr_correctable(m_rd, m_rp, m_sg)) {
           // single correction of the working set: add the most violated inactive row, else drop the worst wrong-sign row
           double my = 0.0; int myix = -1; double myside = 0.0;
-          const bool add = m_rp > 1e-10;
+          const bool add = qpr_correct_by_add(m_rp);
           for (int js = w; js < JT; js += W) {
             const int ix = js * 64 + lane;
             const double l = aL[ix], u = aU[ix], sd = PS[ix];
@@ -1699,16 +1584,11 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
             if (js < J) v = QV[ix]; else { const int i = (js - J) * 64 + lane; v = i < np ? R2_(i) : 0.0; }
             if (add) {
               if (sd != 0.0) continue;
-              double sc = fmax(1.0, fabs(v));
-              if (js < J) { if (l > -INFINITY) sc = fmax(sc, fabs(l)); if (u < INFINITY) sc = fmax(sc, fabs(u)); }
-              const double vl = l > -INFINITY ? (l - v) / sc : -1.0, vu = u < INFINITY ? (v - u) / sc : -1.0;
-              const double vv = fmax(vl, vu);
-              if (vv > my) { my = vv; myix = ix; myside = vl >= vu ? 1.0 : -1.0; }
+              const QprAdd a_ = qpr_add_score(l, u, v, js < J);
+              if (a_.score > my) { my = a_.score; myix = ix; myside = a_.side(); }
             } else {
               if (sd == 0.0) continue;
-              const double y = YV[ix];
-              const double sc = js < J ? fmax(1.0, fabs(y)) : 1.0;
-              const double sg = (sd > 0 ? -y : y) / sc;
+              const double sg = qpr_drop_score(sd, YV[ix], js < J);
               if (sg > my) { my = sg; myix = ix; myside = 0.0; }
             }
           }
@@ -1723,7 +1603,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
           __syncthreads();
           continue;   // next attempt from the point reached (R2) with the corrected working set
         }
-        if (!pok && !(m_rd <= 1e-8) && attempt < QP_REFINE_ATTEMPTS - 1 && m_rd <= 1e-4) {   // stationarity above the floor: one more exact step from here
+        if (!pok && attempt < QP_REFINE_ATTEMPTS - 1 && qpr_one_more_step(m_rd)) {   // stationarity above the floor: one more exact step from here
           for (int i = tid; i < np; i += NTH) XS[i] = R2_(i);
           for (int js = w; js < J; js += W) { const int ix = js * 64 + lane; PY[ix] = PS[ix] != 0.0 ? YV[ix] : 0.0; }
           __syncthreads();
@@ -1733,12 +1613,11 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
         for (int i = tid; i < np; i += NTH) X_(i) = R2_(i);
         for (int js = w; js < JT; js += W) {
           const int ix = js * 64 + lane;
-          const double y = YV[ix], sd = PS[ix];
-          const double lam = sd > 0 ? fmax(y, 0.0) : (sd < 0 ? fmin(y, 0.0) : 0.0);
+          const double lam = qpr_clamp_multiplier(PS[ix], YV[ix]);
           if (js < J) aW3[ix] = lam; else { const int i = (js - J) * 64 + lane; if (i < np) LV_(i) = lam; }
         }
         flag_polished = 1 + attempt;
-        fval_s = f2; merit_s = fmax(m_rd, fmax(m_rp, m_cp / fmax(1.0, fabs(f2))));
+        fval_s = f2; merit_s = qpr_refined_merit(m_rd, m_rp, m_cp, f2);
         flag = 0;
         __syncthreads();
       } else if (!retry) break;
@@ -1768,7 +1647,7 @@ template <int T, int NB, int W> __global__ __launch_bounds__(64 * W, W >= 8 ? 2 
   if (!(v_current || flag_polished > 0)) {  // objective at the returned point (H~, g~ scaling is objective preserving)
     hx_keep(VEC(V_X));
     double fl = 0;
-    for (int i = lane; i < n; i += 64) fl += 0.5 * X_(i) * HX_(i) + G_(i) * X_(i);
+    for (int i = lane; i < n; i += 64) fl += qpr_obj_term(X_(i), HX_(i), G_(i));
     fval_s = wave_sum_rl(fl);
   }
   STAMP(14);
