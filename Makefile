@@ -30,6 +30,9 @@ $(LIBDIR)/cl_latency.o $(LIBDIR)/capi_cl.o: $(CSRC)/cl_latency.h
 # the state estimator of the closed loop: likewise
 $(LIBDIR)/cl_estimator.o $(LIBDIR)/capi_cl.o: $(CSRC)/cl_estimator.h
 
+# the SQP as the controller of the closed loop: likewise, and the SQP's host loop (its skip mask)
+$(LIBDIR)/cl_nmpc.o $(LIBDIR)/capi_cl.o $(LIBDIR)/capi_ltv.o: $(CSRC)/cl_nmpc.h
+
 # WGFLAGS (both solve kernels): without machine LICM and with sinking-to-avoid-spills the T = 8 workgroup kernel spills 20 VGPRs
 # instead of 166 (256 are its budget at two waves per SIMD) and the one-wavefront kernels need no scratch at all (T = 5: 140..504
 # bytes per lane before): hoisted address arithmetic no longer lives across the whole iteration loop.
@@ -55,7 +58,7 @@ $(LIBDIR)/track.o: $(CSRC)/track.cpp include/fsaempc.h
 	@mkdir -p $(LIBDIR)
 	g++ -O2 -std=c++17 -fPIC -Wall -Iinclude -c $< -o $@
 
-COMMON := $(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o $(LIBDIR)/sqp.o $(LIBDIR)/qp_sens.o $(LIBDIR)/reference.o $(LIBDIR)/plant.o $(LIBDIR)/cl_latency.o $(LIBDIR)/cl_estimator.o $(LIBDIR)/planner.o $(LIBDIR)/raceline.o $(LIBDIR)/minlap.o $(LIBDIR)/corridor.o $(LIBDIR)/cones.o $(CAPIOBJ) $(LIBDIR)/track.o
+COMMON := $(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o $(LIBDIR)/sqp.o $(LIBDIR)/qp_sens.o $(LIBDIR)/reference.o $(LIBDIR)/plant.o $(LIBDIR)/cl_latency.o $(LIBDIR)/cl_estimator.o $(LIBDIR)/cl_nmpc.o $(LIBDIR)/planner.o $(LIBDIR)/raceline.o $(LIBDIR)/minlap.o $(LIBDIR)/corridor.o $(LIBDIR)/cones.o $(CAPIOBJ) $(LIBDIR)/track.o
 $(LIBDIR)/libfsaempc.so: $(QPOBJ) $(WGOBJ) $(COMMON)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

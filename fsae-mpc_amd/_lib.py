@@ -36,6 +36,7 @@ EXPORTS = [
     "fsaempc_plan_line_lapgrad_batch_device", "fsaempc_plan_minlap_workspace_bytes", "fsaempc_plan_minlap_batch_device",
     "fsaempc_cl_noise_batch_device", "fsaempc_cl_observe_batch_device", "fsaempc_cl_history_slot",
     "fsaempc_cl_estimate_batch_device",
+    "fsaempc_sqp_batch_device_m", "fsaempc_cl_nmpc_shift_batch_device", "fsaempc_cl_nmpc_accept_batch_device",
 ]
 
 # fsaempc_ltv_params blocks (include/fsaempc.h FSAEMPC_P_*; tests check this table against the header's macros)
@@ -63,6 +64,7 @@ LAP_STATE_INDEX = {name: i for i, name in enumerate(["DONE", "STEPS", "S_PREV", 
 
 
 CL_MAX_DELAY = 4     # FSAEMPC_CL_MAX_DELAY
+SQP_SKIPPED = 4      # FSAEMPC_SQP_SKIPPED
 
 
 def check_laps(laps):
@@ -316,6 +318,10 @@ def lib():
         L.fsaempc_cl_history_slot.argtypes = [C.c_int, ll, C.c_int]
         L.fsaempc_cl_estimate_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(ClEstimator),
                                                        vp, vp, vp, ll] + [vp] * 10
+        L.fsaempc_sqp_batch_device_m.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams)] + [vp] * 4 + \
+            [C.POINTER(QpOpts), C.POINTER(SqpOpts)] + [vp] * 6 + [C.POINTER(SqpAux), vp, ll, vp]
+        L.fsaempc_cl_nmpc_shift_batch_device.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 5
+        L.fsaempc_cl_nmpc_accept_batch_device.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 10
         L.fsaempc_debug_set_dump.argtypes = [vp, C.c_int]
         L.fsaempc_track_last_error.restype = C.c_char_p
         L.fsaempc_track_from_csv.argtypes = [C.c_char_p, C.c_int, C.POINTER(TrackTable)]

@@ -179,6 +179,82 @@ def check_estimator(estimator, latency, nx, B, laps=1):
     return estimator.resolve(latency, nx, B, laps)
 
 
+class Nmpc:
+    """The batched SQP of the nonlinear MPC step as the controller of a closed loop (main.m:118-160, MODE =
+    "MS-NMPC"), validated here without a library call.  sweeps: the sweep cap of a period (max_sweeps; 1 is a real-time iteration).
+    skip_finished: cars that no longer drive are masked out of the SQP's sub-batch.  sqp_opts: the other fields of fsaempc_sqp_opts
+    (trials, tol_step, tol_feas, armijo, rho0, warm_start)."""
+
+    OPTIONS = ("trials", "tol_step", "tol_feas", "armijo", "rho0", "warm_start")
+
+    def __init__(self, sweeps=1, skip_finished=True, **sqp_opts):
+        def integer(v, name):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError("%s must be an integer" % name)
+            return int(v)
+        self.sweeps = integer(sweeps, "sweeps")
+        if self.sweeps < 1:
+            raise ValueError("sweeps must be >= 1")
+        if not isinstance(skip_finished, (bool, np.bool_)):
+            raise ValueError("skip_finished must be True or False")
+        self.skip_finished = bool(skip_finished)
+        self.sqp_opts = {}
+        for k, v in sqp_opts.items():
+            if k == "max_sweeps":
+                raise ValueError("the sweep cap is Nmpc(sweeps=...)")
+            if k not in self.OPTIONS:
+                raise ValueError("unknown SQP option %r (known: %s)" % (k, ", ".join(self.OPTIONS)))
+            if k == "trials":
+                v = integer(v, k)
+                if not 1 <= v <= 64:
+                    raise ValueError("trials must be 1 .. 64")
+            elif k == "warm_start":
+                if not isinstance(v, (bool, np.bool_)) and not (isinstance(v, (int, np.integer)) and v in (0, 1)):
+                    raise ValueError("warm_start must be 0 or 1")
+                v = int(v)
+            else:
+                if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < float("inf"):
+                    raise ValueError("%s must be a finite number >= 0" % k)
+                v = float(v)
+            self.sqp_opts[k] = v
+
+
+def check_controller(controller, corridor, blocking, N, warm_start):
+    """Validates ClosedLoop's controller argument against the arguments the SQP has no form for (no library call)."""
+    if controller is None:
+        return None
+    if not isinstance(controller, Nmpc):
+        raise ValueError("controller must be None (the LTV-MPC step) or an Nmpc")
+    if corridor is not None:
+        raise NotImplementedError("SqpBatch (the exact build of the NLP, nlp_build_qp) is not available with a corridor; "
+                                  "LtvBatch(..., corridor=...).sqp re-linearises a batch inside a corridor")
+    if blocking is not None and len(check_blocking(blocking, N)) != N:
+        raise NotImplementedError("SqpBatch (the exact build of the NLP, nlp_build_qp) is not available with move blocking; "
+                                  "LtvBatch(..., blocking=...).sqp re-linearises a blocked batch")
+    if warm_start:
+        raise ValueError("warm_start is the initial point of the LTV step's QP (fsaempc_qp_aux.x_init); the SQP has its own option, Nmpc(warm_start=...)")
+    return controller
+
+
+def nmpc_shift(u_keep, finished, shift, u_init, skip, stream=None):
+    """fsaempc_cl_nmpc_shift_batch_device on device tensors: u_init (B, N, 2) = u_keep shifted by one stage (shift = 1) or copied
+    (shift = 0), skip (B,) int32 = finished != 0 (finished may be None: all zero)."""
+    import torch
+    B, N = u_keep.shape[0], u_keep.shape[1]
+    P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(u_keep.device).cuda_stream)
+    check(lib().fsaempc_cl_nmpc_shift_batch_device(N, B, int(shift), P(u_keep), P(finished), P(u_init), P(skip), st), "fsaempc_cl_nmpc_shift_batch_device")
+
+
+def nmpc_accept(model, N, x_new, u_new, status, qp_iter, skip, x_keep, u_keep, exitflag, iter, stream=None):
+    """fsaempc_cl_nmpc_accept_batch_device on device tensors (qp_iter and skip may be None)."""
+    import torch
+    P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(x_keep.device).cuda_stream)
+    check(lib().fsaempc_cl_nmpc_accept_batch_device(int(model), int(N), status.shape[0], P(x_new), P(u_new), P(status), P(qp_iter), P(skip), P(x_keep),
+                                                    P(u_keep), P(exitflag), P(iter), st), "fsaempc_cl_nmpc_accept_batch_device")
+
+
 def cl_noise(nx, B, seed, id0, step, device="cuda:0"):
     """The (B, nx) standard normals the observation of period `step` draws for cars id0 .. id0 + B - 1
     (fsaempc_cl_noise_batch_device), a device tensor."""
@@ -198,7 +274,7 @@ class ClosedLoop:
 
     def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
                  params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6, corridor=None, laps=1,
-                 latency=None, estimator=None):
+                 latency=None, estimator=None, controller=None):
         """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
         None = the same as params (both None: the reference's constants compiled into the kernels).  blocking: block lengths of the
         controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2).  reference: None = the live
@@ -221,7 +297,19 @@ class ClosedLoop:
         self.est_x, self.est_P (B, nx, nx), self.est_count (B, 2); self.est_innov, self.est_nis and self.est_resets of the period), predicts
         x0_est over the delay if the latency compensates (self.x0_mpc; otherwise self.x0_mpc is self.x0_est), regenerates x_ref from the
         state the solve reads and solves from it.  The filter's input is the first input of the plan the plant followed in the period
-        just past."""
+        just past.
+        controller: None = the LTV-MPC step (main.m MODE = "LTV-MPC"): step() launches what it launches without the argument and
+        nothing more is allocated.  An Nmpc = the batched SQP of the nonlinear problem (MODE = "MS-NMPC").  step() then
+        runs pre, lap gate, observation / estimator as before, shifts the kept plan by one stage into self.u_init (unshifted in the
+        first period) and masks the cars that no longer drive (self.nmpc_skip), solves with self.sqp (a SqpBatch on the same track,
+        params, integrator and options) from the state the LTV step would have read, and takes the result over
+        (fsaempc_cl_nmpc_accept_batch_device: every finite result, whatever the status); history slots, plant and metrics follow
+        as before.  self.nmpc_status is the SQP's verbatim status of the last period; the returned exitflag is 0 for status 0 and 1
+        and the status otherwise.  self.mpc stays: its descriptor, spline and params serve the observer, the estimator and the
+        metrics.  The SQP call blocks the host once per sweep (it reads the number of instances still running), so in this mode step()
+        is no longer free of read-backs.  Not available with corridor=, a non-trivial blocking= (NotImplementedError) or
+        warm_start=True (ValueError: that flag is the QP's x_init; Nmpc(warm_start=...) is the SQP's own)."""
+        self.controller = check_controller(controller, corridor, blocking, N, warm_start)   # (before the library is touched)
         if not (float(slack_tol) >= 0):
             raise ValueError("slack_tol must be >= 0")
         self.laps = check_laps(laps)   # (before the library is touched)
@@ -319,6 +407,12 @@ class ClosedLoop:
         self._x_init = torch.zeros((self.B, self.mpc.nV), dtype=torch.float64, device=self.device) if self.warm_start else None
         if self.warm_start and self.mpc.blocking is not None:
             self._shift_idx = torch.tensor([min(s + 1, N - 1) for s in self.mpc.blocking.start], dtype=torch.long, device=self.device)
+        self.sqp = self.u_init = self.nmpc_skip = self.nmpc_status = None
+        if self.controller is not None:
+            from .sqp import SqpBatch
+            self.sqp = SqpBatch(model, N, dt, track, self.B, device=device, options=options, integrator=integrator, params=params)
+            self.u_init = torch.zeros((self.B, N, 2), dtype=torch.float64, device=self.device)
+            self.nmpc_skip = torch.zeros(self.B, dtype=torch.int32, device=self.device)
 
     def _stream(self, stream):
         return C.c_void_p(stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -425,6 +519,20 @@ class ClosedLoop:
         self._reference_from(self.x0_mpc, stream)
         return self.x0_mpc
 
+    def _nmpc_step(self, x0, stream):
+        """Shift, SQP and take-over of one period under an Nmpc controller; x0: the state the solve reads."""
+        torch, c = self.torch, self.controller
+        st = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        nmpc_shift(self.u_opt, self.finished if c.skip_finished else None, 0 if self.steps == 0 else 1, self.u_init, self.nmpc_skip, st)
+        # (the call blocks once per sweep: it reads the number of cars still in the sub-batch)
+        res = self.sqp.solve(x0, self.x_ref, self.u_init, stream=st, skip=self.nmpc_skip, max_sweeps=c.sweeps, **c.sqp_opts)
+        self.nmpc_status = res["status"]
+        exitflag = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        it = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        nmpc_accept(self.model, self.N, res["x_opt"], res["u_opt"], res["status"], res["qp_iter"], self.nmpc_skip, self.x_opt, self.u_opt, exitflag, it, st)
+        return dict(x_opt=res["x_opt"], u_opt=res["u_opt"], slack=res["slack"], fval=res["fval"], exitflag=exitflag, iter=it, status=res["status"],
+                    sweeps=res["sweeps"], qp_iter=res["qp_iter"], step_norm=res["step_norm"], hard_viol=res["hard_viol"])
+
     def step(self, stream=None):
         torch = self.torch
         self.pre(stream)
@@ -449,14 +557,17 @@ class ClosedLoop:
         elif self.latency is not None:
             self.observe(stream)
             x0 = self.x0_mpc
-        out = self.mpc.step(x0, self.x_ref, self.x_opt, self.u_opt, stream=stream, x_init=x_init,
-                            difficulty=self._last_iter if self.launch_hint else None)   # linearised about the previous plan (main.m:121-125)
-        if self.warm_start:
-            self._slack = out["slack"]
-        self._last_iter = out["iter"]
         P = lambda t: C.c_void_p(t.data_ptr())
-        check(lib().fsaempc_cl_accept_batch_device(self.model, self.N, self.B, P(out["x_opt"]), P(out["u_opt"]), P(out["exitflag"]), P(self.x_opt), P(self.u_opt),
-                                                   self._stream(stream)), "fsaempc_cl_accept_batch_device")
+        if self.controller is not None:
+            out = self._nmpc_step(x0, stream)
+        else:
+            out = self.mpc.step(x0, self.x_ref, self.x_opt, self.u_opt, stream=stream, x_init=x_init,
+                                difficulty=self._last_iter if self.launch_hint else None)   # linearised about the previous plan (main.m:121-125)
+            if self.warm_start:
+                self._slack = out["slack"]
+            self._last_iter = out["iter"]
+            check(lib().fsaempc_cl_accept_batch_device(self.model, self.N, self.B, P(out["x_opt"]), P(out["u_opt"]), P(out["exitflag"]), P(self.x_opt), P(self.u_opt),
+                                                       self._stream(stream)), "fsaempc_cl_accept_batch_device")
         if self.u_hist is not None:   # the newest plan into its slot, the plant on the one accepted `delay` periods ago
             d = self.latency.delay
             self.x_hist[self.steps % (d + 1)].copy_(self.x_opt)
@@ -506,17 +617,18 @@ def monte_carlo_carts(track, B, seed, lap=False):
 
 
 def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
-                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1, latency=None, estimator=None):
+                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1, latency=None, estimator=None, controller=None):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
     reference: None (the live ramp) or a Plan the cars track (ClosedLoop).  metrics: ClosedLoop(metrics=True); cl.report() afterwards.
     corridor: None or a Corridor (ClosedLoop).  laps: ClosedLoop(laps=...); cl.lap_times afterwards.  latency: None or a Latency (ClosedLoop).  estimator: None or an Estimator (ClosedLoop).
+    controller: None (the LTV-MPC step) or an Nmpc (ClosedLoop; the tallies are then the take-over's exit flags and the SQP's QP iterations).
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
     import torch
     cart0, s_init = monte_carlo_carts(track, B, seed)
     cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
                     params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics, corridor=corridor, laps=laps,
-                    latency=latency, estimator=estimator)
+                    latency=latency, estimator=estimator, controller=controller)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

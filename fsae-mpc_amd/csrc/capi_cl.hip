@@ -1,11 +1,12 @@
 // capi_cl.hip -- the C ABI of libfsaempc.so (include/fsaempc.h), closed-loop part: reference, pre, plant and accept, the metrics
-// and the lap gate with their two host-side reports, measurement noise, observation and the state estimator.  Host-side glue only:
+// and the lap gate with their two host-side reports, measurement noise, observation, the state estimator and the SQP as the controller.  Host-side glue only:
 // argument checks and kernel launches.
 #include "capi_common.h"
 #include "reference.h"
 #include "plant.h"
 #include "cl_latency.h"
 #include "cl_estimator.h"
+#include "cl_nmpc.h"
 using namespace capi;
 
 extern "C" {
@@ -241,6 +242,30 @@ int fsaempc_cl_estimate_batch_device(const fsaempc_ltv_desc* desc, const fsaempc
   P.q = est->q; P.r = est->r; P.p0 = est->p0; P.z = z; P.x_start = x_start; P.u_prev = u_prev; P.u_stride = u_stride; P.finished = finished;
   P.est_x = est_x; P.est_P = est_P; P.est_count = est_count; P.x0_est = x0_est; P.innov = innov; P.nis = nis; P.F_out = F_out; P.x_prior = x_prior;
   return launched(cl_estimate_launch(P, (hipStream_t)stream, par_values(par), par_stride(par)), "cl_estimate_launch");
+}
+
+/* ---- closed loop: the batched SQP as the controller ---- */
+int fsaempc_cl_nmpc_shift_batch_device(int N, int batch, int shift, const double* u_keep, const int* finished, double* u_init, int* skip,
+                                       void* stream) {
+  if (!u_keep || !u_init || !skip) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (N < 1 || batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (shift != 0 && shift != 1) return fail(FSAEMPC_ERR_ARG, "shift must be 0 or 1");
+  const size_t bytes = (size_t)batch * (size_t)N * 2 * sizeof(double);
+  if (ranges_overlap(ByteRange{"u_init", u_init, bytes}, ByteRange{"u_keep", u_keep, bytes}))
+    return fail(FSAEMPC_ERR_ARG, "u_init must not alias u_keep");
+  if (batch == 0) return 0;
+  return launched(cl_nmpc_shift_launch(N, batch, shift, u_keep, finished, u_init, skip, (hipStream_t)stream), "cl_nmpc_shift_launch");
+}
+
+int fsaempc_cl_nmpc_accept_batch_device(int model, int N, int batch, const double* x_new, const double* u_new, const int* status,
+                                        const int* qp_iter, const int* skip, double* x_keep, double* u_keep, int* exitflag, int* iter,
+                                        void* stream) {
+  if (!x_new || !u_new || !status || !x_keep || !u_keep || !exitflag || !iter) return fail(FSAEMPC_ERR_ARG, "null argument");
+  if (model != FSAEMPC_MODEL_KINEMATIC && model != FSAEMPC_MODEL_DYNAMIC) return fail(FSAEMPC_ERR_ARG, "unknown model");
+  if (N < 1 || batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions");
+  if (batch == 0) return 0;
+  return launched(cl_nmpc_accept_launch(fsaempc_ltv_nx(model) * N, 2 * N, batch, x_new, u_new, status, qp_iter, skip, x_keep, u_keep, exitflag, iter,
+                                        (hipStream_t)stream), "cl_nmpc_accept_launch");
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 // for what they do not take, plus the one check that is theirs.
 #include "capi_common.h"
 #include "sqp.h"
+#include "cl_nmpc.h"
 using namespace capi;
 
 extern "C" {
@@ -406,21 +407,14 @@ long long fsaempc_sqp_workspace_bytes(const fsaempc_ltv_desc* desc) {
   return (long long)sqp_ws(desc, nullptr).total;
 }
 
-int fsaempc_sqp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
-                             const double* x0, const double* x_ref, const double* u_init,
-                             const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
-                             double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
-                             const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
-  return fsaempc_sqp_batch_device_p(desc, sp, nullptr, x0, x_ref, u_init, qp_opts, sqp_opts, u_opt, x_opt, slack, fval, status, sweeps, aux,
-                                    workspace, workspace_bytes, stream);
-}
-
+// The one body behind the three entries below.
 // (build, initial rollout and line search all read the block: instance i of a compacted sub-batch finds its own through the index list)
-int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
-                               const double* x0, const double* x_ref, const double* u_init,
-                               const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
-                               double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
-                               const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
+// skip (optional): instances with skip[i] != 0 get status FSAEMPC_SQP_SKIPPED right after the initial rollout, so no compaction lists them
+static int sqp_impl(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                    const double* x0, const double* x_ref, const double* u_init, const int* skip,
+                    const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
+                    double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
+                    const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
   int rc = ltv_check(desc, sp); if (rc) return rc;
   if (!x0 || !x_ref || !u_init || !u_opt || !x_opt || !slack || !fval || !status || !sweeps || !workspace) return fail(FSAEMPC_ERR_ARG, "null argument");
   if (fsaempc_ltv_nV(desc->model, desc->N) > FSAEMPC_MAX_NV) return fail(FSAEMPC_ERR_DIM, "nV exceeds FSAEMPC_MAX_NV");
@@ -445,6 +439,7 @@ int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_splin
   auto stamp = [&](int i) { return timing ? launched(hipEventRecord(g_evs[i], st), "hipEventRecord") : 0; };
   for (double& v : g_sqp_ms) v = 0;
   if ((rc = launched(sqp_init_launch(P, u_init, st, par_values(par), par_stride(par)), "sqp_init_launch"))) return rc;
+  if (skip && (rc = launched(sqp_skip_launch(desc->batch, skip, status, st), "sqp_skip_launch"))) return rc;
   for (int sweep = 0; sweep < o.max_sweeps; ++sweep) {
     if ((rc = stamp(0))) return rc;
     int cnt = 0;
@@ -479,6 +474,31 @@ int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_splin
     }
   }
   return 0;
+}
+
+int fsaempc_sqp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
+                             const double* x0, const double* x_ref, const double* u_init,
+                             const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
+                             double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
+                             const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
+  return sqp_impl(desc, sp, nullptr, x0, x_ref, u_init, nullptr, qp_opts, sqp_opts, u_opt, x_opt, slack, fval, status, sweeps, aux,
+                  workspace, workspace_bytes, stream);
+}
+int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                               const double* x0, const double* x_ref, const double* u_init,
+                               const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
+                               double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
+                               const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
+  return sqp_impl(desc, sp, par, x0, x_ref, u_init, nullptr, qp_opts, sqp_opts, u_opt, x_opt, slack, fval, status, sweeps, aux,
+                  workspace, workspace_bytes, stream);
+}
+int fsaempc_sqp_batch_device_m(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                               const double* x0, const double* x_ref, const double* u_init, const int* skip,
+                               const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
+                               double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
+                               const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream) {
+  return sqp_impl(desc, sp, par, x0, x_ref, u_init, skip, qp_opts, sqp_opts, u_opt, x_opt, slack, fval, status, sweeps, aux,
+                  workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@ import ctypes as C
 from ._lib import LtvDesc, ParamBlock, QpOpts, SqpAux, Spline, check, check_blocking, default_opts, lib, sqp_default_opts
 from .ltvmpc import dims
 
-STATUS = {0: "converged", 1: "sweep limit", 2: "no step accepted", -1: "QP failed", -2: "QP infeasible"}
+STATUS = {0: "converged", 1: "sweep limit", 2: "no step accepted", -1: "QP failed", -2: "QP infeasible", 4: "skipped"}
 
 
 class SqpBatch:
@@ -66,9 +66,11 @@ class SqpBatch:
             return C.c_void_p(None)       # the library reports the missing device: there is no CPU path
         return C.c_void_p(stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream)
 
-    def solve(self, x0, x_ref, u_init, stream=None, **sqp_opts):
+    def solve(self, x0, x_ref, u_init, stream=None, skip=None, **sqp_opts):
         """Returns dict(u_opt (B,2N), x_opt (B,nx*N) = rollout of u_opt, slack (B,ns), fval (NLP objective), status, sweeps, lambda
         (B, nV+nC) of the last QP, qp_iter (total interior-point iterations), step_norm, hard_viol, merit (B, max_sweeps)).
+        skip: None, or an int32 (B,) device tensor: an instance with a non-zero entry is left out of every sub-batch
+        (fsaempc_sqp_batch_device_m): status 4 ("skipped"), sweeps 0, qp_iter 0, u_opt the clamped u_init and x_opt its rollout.
         sqp_opts: fields of fsaempc_sqp_opts (max_sweeps, trials, tol_step, tol_feas, armijo, rho0, warm_start)."""
         torch = self.torch
         B, N, nx = self.batch, self.N, self.nx
@@ -76,6 +78,8 @@ class SqpBatch:
         self._check("x0", x0, B * nx)
         self._check("x_ref", x_ref, B * nx * N)
         self._check("u_init", u_init, B * 2 * N)
+        if skip is not None and (skip.dtype != torch.int32 or not skip.is_contiguous() or skip.device != self.device or tuple(skip.shape) != (B,)):
+            raise ValueError("skip must be a contiguous int32 tensor of shape (%d,) on %s" % (B, self.device))
         need = lib().fsaempc_sqp_workspace_bytes(C.byref(self.desc))
         if need < 0:
             check(int(need), "fsaempc_sqp_workspace_bytes")
@@ -89,9 +93,9 @@ class SqpBatch:
         aux = SqpAux(P(out["lambda"]), P(out["qp_iter"]), P(out["step_norm"]), P(out["hard_viol"]), P(out["merit"]))
         tail = (C.byref(self.opts), C.byref(o), P(out["u_opt"]), P(out["x_opt"]), P(out["slack"]), P(out["fval"]), P(out["status"]),
                 P(out["sweeps"]), C.byref(aux), P(self._ws), C.c_longlong(self._ws.numel() * 8), self._stream(stream))
-        rc = lib().fsaempc_sqp_batch_device_p(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
-                                              P(x0), P(x_ref), P(u_init), *tail)
-        check(rc, "fsaempc_sqp_batch_device_p")
+        rc = lib().fsaempc_sqp_batch_device_m(C.byref(self.desc), C.byref(self.sp), self.params.ref() if self.params is not None else None,
+                                              P(x0), P(x_ref), P(u_init), P(skip) if skip is not None else None, *tail)
+        check(rc, "fsaempc_sqp_batch_device_m")
         return out
 
 

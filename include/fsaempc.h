@@ -357,6 +357,10 @@ int fsaempc_sqp_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline*
                              double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
                              const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream);
 
+/* Status of an instance the caller masked out of fsaempc_sqp_batch_device_m (distinct from the statuses above and from the internal
+ * "still running" = 3). */
+#define FSAEMPC_SQP_SKIPPED 4
+
 /* Phase times of the last fsaempc_sqp_batch_device call, summed over its sweeps, by HIP events (switch: fsaempc_qp_set_timing;
  * with it on, the call also synchronises after every sweep).  compact = compaction + gather. */
 int fsaempc_sqp_get_timing(double* build_ms, double* solve_ms, double* linesearch_ms, double* compact_ms);
@@ -493,6 +497,16 @@ int fsaempc_sqp_batch_device_p(const fsaempc_ltv_desc* desc, const fsaempc_splin
                                const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream);
 int fsaempc_cl_plant_batch_device_p(int model, int N, double dt, int batch, const fsaempc_ltv_params* par, double* cart, double* pid,
                                     const double* x_opt, const int* finished, const int* exitflag, double* u_last, void* stream);
+/* fsaempc_sqp_batch_device_p with a skip mask (device, batch ints; NULL: the entry above, launch for launch).  An instance with
+ * skip[i] != 0 never enters a sub-batch: no QP is built or solved for it, and its outputs are what the start of the call wrote --
+ * u_opt the clamped u_init, x_opt its rollout, the minimal slacks, fval of that point, sweeps 0, qp_iter 0 -- with status
+ * FSAEMPC_SQP_SKIPPED.  The other instances are bit for bit what they are without the mask.  With every instance masked the call
+ * returns after its first read. */
+int fsaempc_sqp_batch_device_m(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                               const double* x0, const double* x_ref, const double* u_init, const int* skip,
+                               const fsaempc_qp_opts* qp_opts, const fsaempc_sqp_opts* sqp_opts,
+                               double* u_opt, double* x_opt, double* slack, double* fval, int* status, int* sweeps,
+                               const fsaempc_sqp_aux* aux, void* workspace, long long workspace_bytes, void* stream);
 
 /* ---- lap report: what main.m:196-228 prints, accumulated per car on the device ----------
  * One record of FSAEMPC_NMETRIC doubles per car, instance-major, zeroed by the caller before the first step.  A step is "recorded"
@@ -1050,6 +1064,29 @@ int fsaempc_cl_estimate_batch_device(const fsaempc_ltv_desc* desc, const fsaempc
                                      double* est_x, double* est_P, int* est_count /* batch x 2, zeroed by the caller */,
                                      double* x0_est, double* innov, double* nis /* batch */,
                                      double* F_out /* optional, batch x nx x nx */, double* x_prior /* optional, batch x nx */, void* stream);
+
+/* ---- closed loop: the batched SQP (nonlinear MPC) as the controller (main.m:118-160, MODE = "MS-NMPC") ----------
+ * Between the pre-step (and lap gate, observation, estimator) and the plant, in place of the LTV step and
+ * fsaempc_cl_accept_batch_device: shift -> fsaempc_sqp_batch_device_m -> accept.  Both entries return FSAEMPC_ERR_ARG, with a text
+ * and before anything is launched or written, for a NULL required pointer, N < 1, batch < 0, an unknown model, a shift that is not
+ * 0 or 1 and a u_init that overlaps u_keep; batch == 0 succeeds without a launch. */
+
+/* The start of this period's solve from the plan the loop keeps (main.m:139-149: the previous solution goes back in):
+ * u_init[b, k] = u_keep[b, k + 1] for k < N - 1, u_init[b, N - 1] = u_keep[b, N - 1]; shift = 0 copies u_keep (the first period:
+ * the guess of main.m:47-55 is used as it is).  skip[b] = (finished[b] != 0), the mask of fsaempc_sqp_batch_device_m; finished may
+ * be NULL (skip is then all zero).  u_keep, u_init: batch x N x 2. */
+int fsaempc_cl_nmpc_shift_batch_device(int N, int batch, int shift, const double* u_keep, const int* finished, double* u_init, int* skip,
+                                       void* stream);
+
+/* Take-over of the SQP's result (x_new: nx*N, u_new: 2*N per car; status, qp_iter as the SQP returned them; qp_iter and skip may be
+ * NULL).  A car with skip[b] != 0: x_keep, u_keep untouched, exitflag 0, iter 0.  Every other car: exitflag 0 for status 0 and 1
+ * (under a sweep cap the sweep limit is the regular end of a period), the status itself (2, -1, -2) otherwise; iter = qp_iter (0
+ * without it); the plan is taken over iff every entry of x_new and u_new is finite, whatever the status: every point the SQP returns
+ * is the rollout of inputs inside their boxes from this period's state, after a failed QP that of the shifted previous plan
+ * (unlike fsaempc_cl_accept_batch_device, which keeps the stale plan after an abnormal exit). */
+int fsaempc_cl_nmpc_accept_batch_device(int model, int N, int batch, const double* x_new, const double* u_new, const int* status,
+                                        const int* qp_iter, const int* skip, double* x_keep, double* u_keep, int* exitflag, int* iter,
+                                        void* stream);
 
 /* ---- track pipeline (host side) --------------------------------------------------- */
 

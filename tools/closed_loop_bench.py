@@ -28,11 +28,16 @@ state-estimate noise with these standard deviations (the model's state layout: 5
 and the solve: process variances per period, measurement variances (default: the squares of --noise) and the indices of components that
 are not measured (their variance becomes +inf).  Echoed as "estimator", with the batch's re-initialisations and the mean NIS over the
 driving cars' periods.
+--nmpc K [--nmpc-trials T] [--nmpc-timing]: the batched SQP of the nonlinear problem as the controller (fsaempc.Nmpc), K sweeps
+per period, warm-started from the previous period's plan shifted by one stage.  "value" then counts the periods of driving cars that
+ended with status 0 or 1; "nmpc" joins the JSON line: the status shares over the driving cars' periods, mean sweeps and QP iterations per
+period and, with --nmpc-timing, the SQP's phase sums.  Excludes --corridor, --cones and --warm.
 usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--steps 200] [--horizon 40] [--track fss2019]
                                   [--plan | --raceline | --minlap K [--margin M] [--points N_c]] [--grip G] [--cells N_s] [--report [--slack-tol T]] [--lap] [--laps K]
                                   [--corridor FILE.npz | --cones FILE [--car-half-width W]] [--line-rows points|cells]
                                   [--delay D [--compensate]] [--noise s1,...,snx [--noise-seed S]]
-                                  [--estimator q1,...,qnx [--meas-var r1,...,rnx] [--unmeasured i,j]]"""
+                                  [--estimator q1,...,qnx [--meas-var r1,...,rnx] [--unmeasured i,j]]
+                                  [--nmpc K [--nmpc-trials T] [--nmpc-timing]]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -75,7 +80,20 @@ def main():
     ap.add_argument("--estimator", default=None, metavar="q1,...,qnx", help="run the EKF state estimator with these process variances per period (Estimator)")
     ap.add_argument("--meas-var", default=None, metavar="r1,...,rnx", help="with --estimator: measurement variances (default: the squares of --noise)")
     ap.add_argument("--unmeasured", default=None, metavar="i,j", help="with --estimator: state components that are not measured (variance +inf)")
+    ap.add_argument("--nmpc", type=int, default=None, metavar="K", help="the batched SQP as the controller, K sweeps per period (Nmpc); excludes --corridor, --cones and --warm")
+    ap.add_argument("--nmpc-trials", type=int, default=None, metavar="T", help="with --nmpc: step lengths the line search tries at once (default 8)")
+    ap.add_argument("--nmpc-timing", action="store_true", help="with --nmpc: the SQP's phase sums by device events (fsaempc_qp_set_timing: one more synchronisation per sweep)")
     a = ap.parse_args()
+    ctl = None
+    if (a.nmpc_trials is not None or a.nmpc_timing) and a.nmpc is None:
+        ap.error("--nmpc-trials and --nmpc-timing need --nmpc")
+    if a.nmpc is not None:
+        if a.corridor is not None or a.cones is not None or a.warm:
+            ap.error("--nmpc excludes --corridor, --cones and --warm")
+        try:
+            ctl = fm.Nmpc(sweeps=a.nmpc, **({"trials": a.nmpc_trials} if a.nmpc_trials is not None else {}))
+        except ValueError as e:
+            ap.error(str(e))
     sigma = None
     if a.noise is not None:
         try:
@@ -146,7 +164,7 @@ def main():
         plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip, corridor=cor, rows=a.line_rows)
     if a.minlap is not None:
         plan = fm.Plan.minlap(model, tr, N_s=a.cells, N_c=a.points, iters=a.minlap, margin=a.margin, grip=a.grip, corridor=cor)
-    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor, latency=lat, estimator=est)          # warm-up (allocations, code load)
+    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor, latency=lat, estimator=est, controller=ctl)          # warm-up (allocations, code load)
     n_max = float(fm.default_params(model)[fm.PARAM_INDEX["N_MAX"]])
     opts = fm.default_opts(max_iter=a.max_iter)
     t0 = time.perf_counter()
@@ -154,7 +172,7 @@ def main():
     # every car while it drives
     cart0, s_init = fm.monte_carlo_carts(tr, a.batch, a.seed, lap=a.lap)
     cl = fm.ClosedLoop(model, a.horizon, 0.05, tr, cart0, options=opts, warm_start=a.warm, launch_hint=not a.no_launch_hint, reference=plan,
-                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps, latency=lat, estimator=est)
+                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps, latency=lat, estimator=est, controller=ctl)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]
     fl_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
@@ -164,10 +182,21 @@ def main():
     nis_sum = torch.zeros((), dtype=torch.float64, device=cl.device)
     nis_cnt = torch.zeros((), dtype=torch.int64, device=cl.device)
     s_first = s_last = None
+    if ctl is not None:   # the SQP's verbatim status and sweep count per (period, car), and its phase sums by device events
+        st_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
+        sw_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
+        phase = dict(build=0.0, solve=0.0, linesearch=0.0, compact=0.0) if a.nmpc_timing else None
+        if phase is not None:
+            fm.lib().fsaempc_qp_set_timing(1)
     for t in range(a.steps):
         out = cl.step()
         drv = cl.finished == 0
         fl_d[t] = out["exitflag"]; it_d[t] = out["iter"]; ac_d[t] = drv
+        if ctl is not None:
+            st_d[t] = out["status"]; sw_d[t] = out["sweeps"]
+            if phase is not None:
+                for k_, v_ in fm.sqp_timing().items():
+                    phase[k_] += v_
         if s_first is None:
             s_first = cl.x0[:, 0].clone(); s_last = cl.x0[:, 0].clone()
         off += ((cl.x0[:, 1].abs() > n_max) & drv).sum()
@@ -194,6 +223,13 @@ def main():
         lap_summary = np.zeros((a.laps, 4))
         fm._lib.check(fm.lib().fsaempc_cl_lap_summary(lt.ctypes.data, a.batch, a.laps, lap_summary.ctypes.data), "fsaempc_cl_lap_summary")
     lost_qps = int((~ac[:, fin == 2]).sum())   # steps the lost cars sat out
+    nmpc = None
+    if ctl is not None:   # (mean sweeps = QPs solved per period and driving car; the accept entry's iter is the SQP's qp_iter)
+        st, sw = st_d.cpu().numpy(), sw_d.cpu().numpy()
+        nmpc = {"sweeps": a.nmpc, "trials": a.nmpc_trials if a.nmpc_trials is not None else 8,
+                "status_share_driving_cars": {fm.sqp.STATUS.get(int(k_), str(int(k_))): float(c_) / max(1, n_act) for k_, c_ in zip(*np.unique(st[ac], return_counts=True))},
+                "mean_sweeps_per_period": float(sw[ac].mean()) if n_act else 0.0, "mean_qp_iterations_per_period": float(it[ac].mean()) if n_act else 0.0,
+                **({"sqp_phase_ms_sum": phase, "sqp_phase_ms_per_step": {k_: v_ / a.steps for k_, v_ in phase.items()}} if phase is not None else {})}
     print(json.dumps({
         "metric": "QP solves/sec (closed loop, %s N=%d, fp64)" % (a.model, a.horizon), "value": solved / dt_wall, "unit": "QP solves/s",
         "n_gpus": 1, "steps": a.steps, "ms_per_step": 1e3 * dt_wall / a.steps, "dtype": "f64", "data": "synthetic",
@@ -206,6 +242,7 @@ def main():
                                      "cars_reset": int((cl.est_resets > 0).sum().item()),
                                      "nis_mean": float((nis_sum / nis_cnt.clamp(min=1)).item()), "nis_periods": int(nis_cnt.item()),
                                      "measured_components": nx_ - len(skip)}} if est is not None else {}),
+                   "controller": "LTV-MPC" if ctl is None else "MS-NMPC (batched SQP)", **({"nmpc": nmpc} if nmpc is not None else {}),
                    **({"cones": cone_info} if cone_info is not None else {}), "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
                    # (a mean over an empty set is NaN in the report: null in the JSON line)
                    **({"lap_report": {k: (None if v != v else v) for k, v in cl.report().summary().items()}, "slack_tol": a.slack_tol} if a.report else {}),
