@@ -21,6 +21,9 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/qp_solver.h $(CSRC)/qp_sens.h $(CSRC)/ltv_b
 CAPIOBJ := $(LIBDIR)/capi_qp.o $(LIBDIR)/capi_ltv.o $(LIBDIR)/capi_cl.o $(LIBDIR)/capi_plan.o
 $(CAPIOBJ): $(CSRC)/capi_common.h
 
+# the body of the LTV build kernel: read by the two units that instantiate it, without and with blocks
+$(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o: $(CSRC)/ltv_build_kernel.h
+
 # the minimum-time line: its own header, read by its unit and the C ABI's planning unit only
 $(LIBDIR)/minlap.o $(LIBDIR)/capi_plan.o: $(CSRC)/minlap.h
 

@@ -108,20 +108,17 @@ static int ltv_build_shaped(const fsaempc_ltv_desc* desc, const fsaempc_spline* 
   int rc = ltv_check(desc, sp); if (rc) return rc;
   const int nx = fsaempc_ltv_nx(desc->model), N = desc->N;
   const char* too_long = "horizon too long for the LDS staging";
+  const LtvBlockMap* bm = s.blocked ? &s.bm : nullptr;
+  // (the exact build's carve is refused ahead of a null argument, the order the ABI's tests pin; the check below covers the rest)
   if (exact && ltv_build_lds_bytes(nx, N, 256, true) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, too_long);
   if (!x0 || !x_ref || (!exact && !x_lin) || !u_lin || !q.H || !q.g || !q.A || !q.lb || !q.ub || !q.lbA || !q.ubA || !q.Bt)
     return fail(FSAEMPC_ERR_ARG, "null argument (Bt is required as scratch)");
-  if (s.blocked ? ltv_build_blocked_lds_bytes(nx, N, s.bm.M, 256) > 160 * 1024
-                : par_values(par) && ltv_build_lds_bytes(nx, N, 256, exact, true) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, too_long);
+  if (ltv_build_lds_bytes(nx, N, 256, exact, par_values(par) != nullptr, bm ? bm->M : 0) > 160 * 1024) return fail(FSAEMPC_ERR_DIM, too_long);
   if (desc->batch == 0) return 0;
   LtvParams P = ltv_params(desc, sp, x_lin, u_lin);
   P.x0 = x0; P.x_ref = x_ref;
   P.H = q.H; P.g = q.g; P.A = q.A; P.lb = q.lb; P.ub = q.ub; P.lbA = q.lbA; P.ubA = q.ubA; P.pred = q.pred; P.Bt = q.Bt; P.qconst = q.qconst;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = s.blocked        ? ltv_build_blocked_launch(P, s.bm, par_values(par), par_stride(par), desc->batch, st)
-               : par_values(par) ? ltv_build_par_launch(P, par_values(par), par_stride(par), par_idx, desc->batch, st, exact)
-                                 : ltv_build_launch(P, desc->batch, st, exact);
-  return launched(e, s.blocked ? "ltv_build_blocked_launch" : "ltv_build_launch");
+  return launched(ltv_build_launch(P, bm, par_values(par), par_stride(par), par_idx, desc->batch, (hipStream_t)stream, exact), "ltv_build_launch");
 }
 
 // the build entries: optional parameter block, blocking and corridor (whose rows overwrite the track rows of the built batch)
@@ -193,9 +190,8 @@ static int ltv_step_impl(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp,
                                        lambda, aux, c.qpws, (long long)c.qp_bytes, stream);
   if (rc) return rc;
   { Range r("fsaempc.ltv.post");
-    hipError_t e = s.blocked ? ltv_post_blocked_launch(nx, desc->N, ns, s.bm, desc->batch, c.z, q.pred, q.Bt, q.qconst, u_opt, x_opt, slack, fval, st)
-                             : ltv_post_launch(nx, desc->N, ns, desc->batch, c.z, q.pred, q.Bt, q.qconst, u_opt, x_opt, slack, fval, st);
-    if ((rc = launched(e, s.blocked ? "ltv_post_blocked_launch" : "ltv_post_launch"))) return rc; }
+    hipError_t e = ltv_post_launch(nx, desc->N, ns, s.blocked ? &s.bm : nullptr, desc->batch, c.z, q.pred, q.Bt, q.qconst, u_opt, x_opt, slack, fval, st);
+    if ((rc = launched(e, "ltv_post_launch"))) return rc; }
   if (timing) if ((rc = launched(hipEventRecord(g_evf[1], st), "hipEventRecord"))) return rc;
   return 0;
 }

@@ -12,26 +12,23 @@ struct LtvParams {
   double *pred, *Bt, *qconst;   // Bt is required (internal operand); pred/qconst optional
 };
 
-// exact = false: the LTV build of the reference; true: the exact build of the NLP at u_lin (x_lin is not read)
-hipError_t ltv_build_launch(const LtvParams& P, int batch, hipStream_t st, bool exact = false);
-hipError_t ltv_post_launch(int nx, int N, int ns, int batch, const double* z, const double* pred, const double* Bt,
-                           const double* qconst, double* u_opt, double* x_opt, double* slack, double* fval, hipStream_t st);
-size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact = false, bool par = false);
-// The same build with the constants read from parameter blocks (include/fsaempc.h, FSAEMPC_P_*): workgroup b reads
-// values + inst * stride (stride 0: one block for the batch), inst = idx ? idx[b] : b.
-hipError_t ltv_build_par_launch(const LtvParams& P, const double* values, int stride, const int* idx, int batch, hipStream_t st,
-                                bool exact = false);
-
-// Move blocking (ltv_build_blocked.hip): M blocks of consecutive steps share one input pair.  start[j] is the first
-// step of block j, start[M] = N; the map is a kernel argument (no device copy).  All QP tensors of P are in blocked sizes
-// (nV_b = 2 M + ns); values = nullptr selects the compiled-in constants, else workgroup b reads values + b * stride.
+// Move blocking: M blocks of consecutive steps share one input pair.  start[j] is the first step of block j,
+// start[M] = N; the map is a kernel argument (no device copy).  With a map all QP tensors of P are in blocked sizes (nV_b = 2 M + ns).
 struct LtvBlockMap { int M; unsigned char start[98]; };
-size_t ltv_build_blocked_lds_bytes(int nx, int N, int M, int threads);
-hipError_t ltv_build_blocked_launch(const LtvParams& P, const LtvBlockMap& bm, const double* values, int stride, int batch, hipStream_t st);
-// post-solve of a blocked step: x_opt = pred + Bt_b z, u_opt = the held inputs expanded to 2N, slack, fval += const
-hipError_t ltv_post_blocked_launch(int nx, int N, int ns, const LtvBlockMap& bm, int batch, const double* z, const double* pred,
-                                   const double* Bt, const double* qconst, double* u_opt, double* x_opt, double* slack, double* fval,
-                                   hipStream_t st);
+
+// The build (ltv_build_kernel.h).  bm = nullptr: unblocked.  exact = false: the LTV build of the reference; true: the exact build of
+// the NLP at u_lin (x_lin is not read; it knows no blocks).  values = nullptr: the constants compiled in, else they are read from
+// parameter blocks (include/fsaempc.h, FSAEMPC_P_*): workgroup b reads values + inst * stride (stride 0: one block for
+// the batch), inst = idx ? idx[b] : b.
+hipError_t ltv_build_launch(const LtvParams& P, const LtvBlockMap* bm, const double* values, int stride, const int* idx, int batch,
+                            hipStream_t st, bool exact);
+hipError_t ltv_build_launch_blocked_unit(const LtvParams& P, const LtvBlockMap& bm, const double* values, int stride, const int* idx,
+                                         int batch, hipStream_t st);   // ltv_build_blocked.hip's instantiations, for ltv_build_launch
+// dynamic LDS of the build, the kernel's carve term by term; par: with parameter blocks; M: blocks, 0 for unblocked
+size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact = false, bool par = false, int M = 0);
+// post-solve: x_opt = pred + Bt z, u_opt = z(1:2N) (bm = nullptr) or the held inputs expanded to 2N, slack, fval += const
+hipError_t ltv_post_launch(int nx, int N, int ns, const LtvBlockMap* bm, int batch, const double* z, const double* pred, const double* Bt,
+                           const double* qconst, double* u_opt, double* x_opt, double* slack, double* fval, hipStream_t st);
 
 // sensitivities: the affine maps of the build in x0 / x_ref (Abar R x nx, Crow nC x nx per instance, column-major),
 // the cotangent of the QP variables of a step (z = [u_opt; slack], zbar = [ubar; sbar] + Bt' xbar, kc columns) and the chain from the

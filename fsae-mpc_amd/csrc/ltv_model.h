@@ -1,4 +1,4 @@
-// ltv_model.h -- device functions shared by the LTV-MPC construction kernels (ltv_build.hip, ltv_build_blocked.hip): the model
+// ltv_model.h -- device functions shared by the LTV-MPC construction kernels (ltv_build_kernel.h; the sensitivity kernels of ltv_build.hip): the model
 // Jacobians, the linearisation of one step and the per-step coefficients of the linearised constraint rows.
 #pragma once
 #include <hip/hip_runtime.h>

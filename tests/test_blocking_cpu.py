@@ -21,6 +21,10 @@ SHAPES = [
     (1, 80, [1] * 16 + [2] * 16 + [4] * 8, "fsg2019", 64),
     (1, 60, [1] * 12 + [2] * 12 + [4] * 6, "fss2019", 64),
     (0, 20, [1] * 4 + [2] * 4 + [4] * 2, "fsg2019", 128),
+    # M = 13: two column tiles of the build's SYRK, the second beginning at step 11 -- weighted row 33, no multiple of 4 (its first
+    # k-step is the floor of 33 / 4, the only batch here in which that floor rounds), with a ragged tail (3 N = 63)
+    (0, 21, [1] * 5 + [2] * 8, "fsg2019", 3),
+    (1, 21, [1] * 5 + [2] * 8, "fsg2019", 3),
 ]
 QP = ("H", "g", "A", "lb", "ub", "lbA", "ubA")
 NEW = ["fsaempc_ltv_blocked_nV", "fsaempc_ltv_build_qp_batch_device_b", "fsaempc_ltv_workspace_bytes_b", "fsaempc_ltv_step_batch_device_b",
