@@ -183,9 +183,29 @@ size_t ltv_build_lds_bytes(int nx, int N, int threads, bool exact, bool par, int
          (M ? (size_t)(M + 1 + N) : 0) * sizeof(int);   // bst, bos: the block map
 }
 
+// The kinematic default block (fsaempc_ltv_default_params) on the device, for the one build that is routed through its RtPar kernel.
+// No device code names it: external linkage and `used` keep it in the code object, where hipGetSymbolAddress looks it up (a static
+// or const one is dropped from the device side and the lookup aborts).  Nothing writes it.
+__device__ __attribute__((used)) double fsaempc_kin_default_block[FSAEMPC_NPAR] = {
+    FixedPar::M, FixedPar::IZ, FixedPar::LF, FixedPar::LR, FixedPar::GRAV, FixedPar::PB, FixedPar::PC, FixedPar::PD, FixedPar::PE,
+    FixedPar::QW[0], FixedPar::QW[1], FixedPar::QW[2], FixedPar::Q_TERMINAL, FixedPar::R_ACC, FixedPar::R_STEER,
+    FixedPar::R_SOFT0, 0, 0, 0, FixedPar::U_ACC_MAX, FixedPar::U_STEER_MAX, FixedPar::DELTA_MAX, FixedPar::N_MAX, FixedPar::V_MIN,
+    FixedPar::ALAT_MAX, FixedPar::SLIP_MAX, FixedPar::ELL_LONG, FixedPar::ELL_LAT,
+    FixedPar::PID_KP_V, FixedPar::PID_MAX_F, FixedPar::PID_KP_D, FixedPar::PID_MAX_DRATE};
+
 hipError_t ltv_build_launch(const LtvParams& P, const LtvBlockMap* bm, const double* values, int stride, const int* idx, int batch,
                             hipStream_t st, bool exact) {
   if (bm) return exact ? hipErrorNotSupported : ltv_build_launch_blocked_unit(P, *bm, values, stride, idx, batch, st);
+  // The exact kinematic build under RK4 with the constants compiled in, ltv_build_kernel<5, true, false, FixedPar>, returned wrong
+  // linearisations (NaN or wrong Ad_k, Bd_k of whole steps, other steps in other runs) on the MI355X while its rollout stayed right;
+  // the cause is not established.  Its RtPar sibling with the default block is the same arithmetic and does not, so
+  // that one combination runs there: one block shared by the batch (stride 0).  Euler and RK2, the kinematic default, are not moved.
+  if (exact && !values && P.nx == 5 && P.integ != 0 && P.integ != 1) {
+    const double* block = nullptr;
+    hipError_t e = hipGetSymbolAddress((void**)&block, HIP_SYMBOL(fsaempc_kin_default_block));
+    if (e != hipSuccess) return e;
+    return select_build<false>(P, nullptr, block, 0, nullptr, batch, st, true);
+  }
   return select_build<false>(P, nullptr, values, stride, idx, batch, st, exact);
 }
 
