@@ -27,6 +27,11 @@ $(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o: $(CSRC)/ltv_build_kernel.h
 # the minimum-time line: its own header, read by its unit and the C ABI's planning unit only
 $(LIBDIR)/minlap.o $(LIBDIR)/capi_plan.o: $(CSRC)/minlap.h
 
+# the speed profile of the plans: its rules and kernel phases, read by the three plan units (and through minlap.h by
+# the C ABI's planning unit); the body of the plan kernel, read by the two units that instantiate it, on the centre line and on a line
+$(LIBDIR)/planner.o $(LIBDIR)/raceline.o $(LIBDIR)/minlap.o $(LIBDIR)/capi_plan.o: $(CSRC)/plan_profile.h
+$(LIBDIR)/planner.o $(LIBDIR)/raceline.o: $(CSRC)/plan_profile_kernel.h
+
 # measurement noise, plan latency and delay compensation of the closed loop: likewise, the C ABI's closed-loop unit
 $(LIBDIR)/cl_latency.o $(LIBDIR)/capi_cl.o: $(CSRC)/cl_latency.h
 

@@ -2,13 +2,13 @@
 // gradient in the control points c by the adjoint of that profile, written once for the host and the device, and the internal
 // interface between the C ABI and the kernels of minlap.hip.
 //
-// Forward (the arithmetic of plan_line_profile_kernel, raceline.hip): per cell n, n', a = 1 - n kappa, r, mu (rl_point), dl = ds r,
+// Forward (the profile on a line, plan_profile.h; what plan_profile_kernel<.., LINE = true> runs): per cell n, n', a = 1 - n kappa, r, mu (rl_point), dl = ds r,
 // m = kappa + (mu_next - mu_prev) / (2 ds), k = m / r, K = max(|k|, 1e-12), vlat = min(v_cap, sqrt(A_lat / K)); from the first minimum
 // i0 of vlat one forward pass (acceleration out of the predecessor over the predecessor's cell) and one backward pass (braking into
 // the successor over the cell's own length); T = sum dl / v.
 //
-//   ml_ax             the longitudinal limit of line_ax (raceline.hip: the same text) and its partials in v and K
-//   ml_forward        the two passes; keeps the speeds after the forward pass and, per cell and pass, whether the recurrence won the min
+//   (plan_profile.h)  pp_ax<DYN, true>: the longitudinal limit with its partials in v and K; pp_passes with PpRecord: the two passes,
+//                     keeping the speeds after the forward pass and, per cell and pass, whether the recurrence won the min
 //   ml_cell_seed      the adjoints T puts on a cell's speed and length
 //   ml_reverse        the two passes undone in reverse order: adjoints of vlat, K and dl
 //   ml_cell_kbar      vlat and K = max(|k|, 1e-12) undone: the adjoint of k
@@ -23,69 +23,9 @@
 #include <math.h>
 #include <stddef.h>
 #include "raceline.h"
+#include "plan_profile.h"
 
 #define ML_HD RL_HD
-
-struct MlCar { double U_ACC_MAX, ELL_LONG; };   // the two limits of the block that the longitudinal limit reads
-
-// a_x(v, K) of line_ax and d a_x / d v, d a_x / d K.  The partials are zero where U_ACC_MAX or y = 1 is the active branch.
-template <bool DYN> ML_HD double ml_ax(const MlCar& p, double v, double K, double A_lat, double grip, double& dv, double& dK) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  dv = 0.0; dK = 0.0;
-  if (!DYN) return grip * p.U_ACC_MAX;
-  const double y0 = v * v * K / A_lat;
-  const double y = fmin(y0, 1.0);
-  double c0 = 1.0, c1 = 0.8660254037844386, s0 = 0.0, s1 = 0.5;                        // edge 0
-  if (!(y <= 0.5)) { c0 = 0.8660254037844386; c1 = 0.5; s0 = 0.5; s1 = 0.8660254037844386; }   // edge 1
-  if (!(y <= 0.8660254037844386)) { c0 = 0.5; c1 = 0.0; s0 = 0.8660254037844386; s1 = 1.0; }   // edge 2
-  const double X = c0 + (c1 - c0) * (y - s0) / (s1 - s0);
-  const double val = grip * p.ELL_LONG * X;
-  if (val < p.U_ACC_MAX && y0 < 1.0) {
-    const double slope = grip * p.ELL_LONG * ((c1 - c0) / (s1 - s0));
-    dv = slope * (2.0 * v * K / A_lat);
-    dK = slope * (v * v / A_lat);
-  }
-  return fmin(p.U_ACC_MAX, val);
-}
-
-#define ML_WON_FWD 1   // the forward recurrence was strictly below the cell's corner speed
-#define ML_WON_BWD 2   // the backward recurrence was strictly below the cell's speed after the forward pass
-
-// The two recurrences of plan_line_profile_kernel from cell i0.  v: in the corner speeds vlat, out the final speeds; vf: the speeds
-// after the forward pass (the backward pass may lower a cell the forward pass read as its source); won: ML_WON_* per cell.
-template <bool DYN> ML_HD void ml_forward(const MlCar& p, int Ns, int i0, double A_lat, double grip, const double* k, const double* dl,
-                                          double* v, double* vf, int* won) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  double dv, dK;
-  double vp = v[i0]; int i = i0;
-  for (int j = 1; j <= Ns; ++j) {
-    const int pr = i;
-    i = i + 1; if (i >= Ns) i = 0;
-    const double Kp = fmax(fabs(k[pr]), 1e-12);
-    const double a = ml_ax<DYN>(p, vp, Kp, A_lat, grip, dv, dK);
-    const double cand = sqrt(vp * vp + 2.0 * a * dl[pr]);
-    const double own = v[i];
-    const double vi = fmin(own, cand);
-    won[i] = cand < own ? ML_WON_FWD : 0;
-    v[i] = vi; vf[i] = vi; vp = vi;
-  }
-  vp = v[i0]; i = i0;
-  for (int j = 1; j <= Ns; ++j) {
-    const int nx = i;
-    i = i - 1; if (i < 0) i = Ns - 1;
-    const double Kn = fmax(fabs(k[nx]), 1e-12);
-    const double a = ml_ax<DYN>(p, vp, Kn, A_lat, grip, dv, dK);
-    const double cand = sqrt(vp * vp + 2.0 * a * dl[i]);
-    const double own = v[i];
-    const double vi = fmin(own, cand);
-    if (cand < own) won[i] |= ML_WON_BWD;
-    v[i] = vi; vp = vi;
-  }
-}
 
 // T = sum dl_i / v_i: what it puts on v_i and dl_i
 ML_HD void ml_cell_seed(double dl, double v, double& vbar, double& dlbar) {
@@ -97,7 +37,7 @@ ML_HD void ml_cell_seed(double dl, double v, double& vbar, double& dlbar) {
 }
 
 // The backward pass undone from its last step to its first, then the forward pass the same way.  In: vbar, dlbar of ml_cell_seed,
-// Kbar = 0; v, vf, won of ml_forward; v0 = vlat[i0] (the source of the first forward step).  Out: vbar the adjoint of vlat, Kbar of
+// Kbar = 0; v, vf, won of pp_passes (PpRecord); v0 = vlat[i0] (the source of the first forward step).  Out: vbar the adjoint of vlat, Kbar of
 // K, dlbar of dl.  A step's source is the cell's final speed (backward) or its speed after the forward pass (forward), except the
 // first step of each pass, which read cell i0 before that pass set it.
 template <bool DYN> ML_HD void ml_reverse(const MlCar& p, int Ns, int i0, double A_lat, double grip, double v0, const double* k,
@@ -113,7 +53,7 @@ template <bool DYN> ML_HD void ml_reverse(const MlCar& p, int Ns, int i0, double
     if (won[i] & ML_WON_BWD) {
       const double vn = j == 1 ? vf[nx] : v[nx];
       const double Kn = fmax(fabs(k[nx]), 1e-12);
-      const double a = ml_ax<DYN>(p, vn, Kn, A_lat, grip, dv, dK);
+      const double a = pp_ax<DYN, true>(p, vn, Kn, A_lat, grip, &dv, &dK);
       const double qbar = vbar[i] / (2.0 * v[i]);
       vbar[i] = 0.0;
       vbar[nx] += qbar * (2.0 * vn + 2.0 * dl[i] * dv);
@@ -128,7 +68,7 @@ template <bool DYN> ML_HD void ml_reverse(const MlCar& p, int Ns, int i0, double
     if (won[i] & ML_WON_FWD) {
       const double vp = j == 1 ? v0 : vf[pr];
       const double Kp = fmax(fabs(k[pr]), 1e-12);
-      const double a = ml_ax<DYN>(p, vp, Kp, A_lat, grip, dv, dK);
+      const double a = pp_ax<DYN, true>(p, vp, Kp, A_lat, grip, &dv, &dK);
       const double qbar = vbar[i] / (2.0 * vf[i]);
       vbar[i] = 0.0;
       vbar[pr] += qbar * (2.0 * vp + 2.0 * dl[pr] * dv);
@@ -225,13 +165,10 @@ template <bool DYN> inline int ml_lapgrad_host(const MlCar& p, double A_lat, dou
     k[i] = (kap[i] + (mu[nx] - mu[pr]) / (2.0 * ds)) / rv[i];
     dl[i] = ds * rv[i];
   }
-  int i0 = 0;
-  for (int i = 0; i < Ns; ++i) {
-    v[i] = fmin(v_cap, sqrt(A_lat / fmax(fabs(k[i]), 1e-12)));
-    if (v[i] < v[i0]) i0 = i;
-  }
+  for (int i = 0; i < Ns; ++i) v[i] = pp_corner_speed(k[i], A_lat, v_cap);
+  const int i0 = pp_first_min(v, Ns);
   const double v0 = v[i0];
-  ml_forward<DYN>(p, Ns, i0, A_lat, grip, k, dl, v, vf, won);
+  pp_passes<DYN>(p, Ns, i0, A_lat, grip, k, (const double*)dl, v, PpRecord{vf, won});
   double sum = 0.0;
   for (int i = 0; i < Ns; ++i) {
     sum += dl[i] / v[i];

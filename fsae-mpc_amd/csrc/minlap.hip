@@ -1,7 +1,9 @@
 // minlap.hip -- the minimum-time racing line of the s-domain plans, batched on the device.
 //
-//   plan_line_lapgrad_kernel   lap time T(c) of the profile of plan_line_profile_kernel (raceline.hip) on a line and dT/dc by the
-//                              adjoint of that profile.  One wavefront per line, cells dealt to the lanes for the parallel phases,
+//   plan_line_lapgrad_kernel   lap time T(c) of the profile on a line and dT/dc by the adjoint of that profile: up to and including
+//                              the two passes the phases of plan_profile.h that plan_profile_kernel<.., LINE = true> (raceline.hip)
+//                              runs, with the passes recorded (PpRecord), then the adjoint half of minlap.h.  One wavefront per
+//                              line, cells dealt to the lanes for the parallel phases,
 //                              the four serial chains (two passes, two passes undone) run by lane 0 out of LDS between barriers, the
 //                              gradient gathered per control point over its cells in ascending order (no atomics: the same bits on
 //                              every call).  A wave may run on clamp(base + step, lo, hi) (the candidates of one iteration).
@@ -20,12 +22,10 @@
 
 namespace {
 
-DEVINL double ml_clamp(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }   // (a NaN x stays NaN)
-
 template <bool DYN, class PAR> __global__ void __launch_bounds__(64) plan_line_lapgrad_kernel(MinlapGradParams P, typename PAR::Args pa) {
   extern __shared__ double lds[];
   const int wave = blockIdx.x, plan = wave / P.cand, lane = threadIdx.x, Ns = P.N_s, Nc = P.N_c;
-  const int per = (Ns + 63) / 64;   // cells per lane: every loop below runs `per` times on every lane
+  const int per = (Ns + 63) / 64;   // cells per lane: the loops over cells below run `per` times on every lane
   double* kq = lds;                 // Ns: curvature of the centre line, then of the line; after the chains a
   double* mq = lds + Ns;            // Ns: heading offset
   double* dq = lds + 2 * Ns;        // Ns: |dp/ds|, then the cell's length on the line; after the chains kappa
@@ -44,24 +44,10 @@ template <bool DYN, class PAR> __global__ void __launch_bounds__(64) plan_line_l
   const double ds = P.ds, grip = P.grip;
 
   if (!nan_plan) {
-    const double* c = P.line + (size_t)wave * P.line_stride;
-    for (int j = lane; j < Nc; j += 64) {
-      double cj = c[j];
-      if (P.base) cj = ml_clamp(P.base[(size_t)plan * Nc + j] + cj, P.lo[(size_t)plan * Nc + j], P.hi[(size_t)plan * Nc + j]);
-      cq[j] = cj;
-    }
+    const size_t o = (size_t)plan * Nc;
+    pp_load_points(cq, P.line + (size_t)wave * P.line_stride, Nc, lane, false, P.base ? P.base + o : nullptr, P.lo + o, P.hi + o);
     __syncthreads();
-    bool a_ok = true;
-    for (int it = 0; it < per; ++it) {
-      const int i = lane + 64 * it;
-      if (i < Ns) {
-        const double k = kappa(sp, (double)i * ds);
-        const RlPoint q = rl_point(cq, i, Ns, Nc, P.h, k);
-        a_ok = a_ok && (q.a >= 0.1);
-        kq[i] = k; mq[i] = q.mu; dq[i] = q.r;
-      }
-    }
-    nan_plan = __any(!a_ok) != 0;   // (all 64 lanes are here)
+    nan_plan = pp_line_geometry(sp, cq, Ns, Nc, ds, P.h, lane, per, kq, mq, dq);
   }
   if (nan_plan) {   // (uniform over the wave) this line is NaN, the others are unaffected
     for (int j = lane; j < Nc; j += 64) {
@@ -73,42 +59,17 @@ template <bool DYN, class PAR> __global__ void __launch_bounds__(64) plan_line_l
   }
   if (lout) for (int j = lane; j < Nc; j += 64) lout[j] = cq[j];
   __syncthreads();
-
-  // curvature and length of the line per cell (own cell written, neighbours' heading offsets read)
-  for (int it = 0; it < per; ++it) {
-    const int i = lane + 64 * it;
-    if (i < Ns) {
-      const int pr = i > 0 ? i - 1 : Ns - 1, nx = i + 1 < Ns ? i + 1 : 0;
-      const double r = dq[i];
-      kq[i] = (kq[i] + (mq[nx] - mq[pr]) / (2.0 * ds)) / r;
-      dq[i] = ds * r;
-    }
-  }
+  pp_line_curvature(kq, mq, dq, Ns, ds, lane, per);
   __syncthreads();
 
   const double A_lat = grip * (DYN ? p.ELL_LAT : p.ALAT_MAX);
   const MlCar car{p.U_ACC_MAX, p.ELL_LONG};
-  double best = INFINITY; int ibest = 0x7fffffff;
-  for (int it = 0; it < per; ++it) {
-    const int i = lane + 64 * it;
-    if (i < Ns) {
-      const double K = fmax(fabs(kq[i]), 1e-12);
-      const double vl = fmin(P.v_cap, sqrt(A_lat / K));
-      vq[i] = vl;
-      if (vl < best) { best = vl; ibest = i; }
-    }
-  }
-  // first index of the minimum over the wave (every lane takes part; a tie goes to the lower index)
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const double ob = __shfl_xor(best, m, 64);
-    const int oi = __shfl_xor(ibest, m, 64);
-    if (ob < best || (ob == best && oi < ibest)) { best = ob; ibest = oi; }
-  }
-  const int i0 = ibest < Ns ? ibest : 0;
+  double best; int ibest;
+  pp_corner_phase<false>(sp, ds, kq, vq, Ns, lane, A_lat, P.v_cap, best, ibest);
+  const int i0 = pp_wave_first_min(best, ibest, Ns);   // (best: vlat[i0], the source of the first forward step)
   __syncthreads();
 
-  if (lane == 0) ml_forward<DYN>(car, Ns, i0, A_lat, grip, kq, dq, vq, vf, won);
+  if (lane == 0) pp_passes<DYN>(car, Ns, i0, A_lat, grip, kq, (const double*)dq, vq, PpRecord{vf, won});
   __syncthreads();
 
   // T = sum dl / v: each lane sums its cells in ascending order, then the wave; the seeds of the reverse sweep

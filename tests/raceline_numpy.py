@@ -121,7 +121,7 @@ def offsets(c, N_s):
 
 
 def line_profile(model, k, L, c, v_cap=20.0, grip=1.0, par=None, margin=None):
-    """plan_line_profile_kernel: k (N_s,) curvature of the centre line at the cells, c (N_c,) control points.  Returns the dict of
+    """plan_profile_kernel<.., LINE = true>: k (N_s,) curvature of the centre line at the cells, c (N_c,) control points.  Returns the dict of
     plan_numpy.profile plus n, mu, kl (the line's curvature), dl (the cells' lengths on the line).  margin: None (no width check) or
     the margin of Plan.raceline."""
     k = np.asarray(k, dtype=np.float64)

@@ -5,7 +5,8 @@ models, with the iteration records; --restated FILE.json (lap histories of tests
 adds the largest relative difference to them.
 --time: whole-call wall time of Plan.raceline and of Plan.minlap (K iterations) on the same inputs for --plans 1 256: median, min and
 max of --reps synchronised calls after one warm-up call.
---once P: one Plan.raceline and one Plan.minlap call with P plans after a warm-up of each (for a kernel trace).
+--once P: one Plan.profile, one Plan.raceline and one Plan.minlap call with P plans after a warm-up of each (for a kernel trace: all
+three plan kernels in one).
 usage: tools/minlap_bench.py (--laps [--restated FILE.json] | --time [--plans 1 256] [--reps 10] | --once P) [--iters 12] [--cells 500] [--points 100]"""
 import argparse, json, os, sys, time
 import numpy as np
@@ -71,9 +72,10 @@ def main():
         P = a.once
         blocks = fm.param_draws(fm.DYNAMIC, range(P), 77, 0.1) if P > 1 else None
         for rep in range(2):
+            fm.Plan.profile(fm.DYNAMIC, tr, N_s=a.cells, params=blocks); sync()
             fm.Plan.raceline(fm.DYNAMIC, tr, params=blocks, **kw); sync()
             fm.Plan.minlap(fm.DYNAMIC, tr, iters=a.iters, params=blocks, **kw); sync()
-        print(json.dumps({"what": "two Plan.raceline and two Plan.minlap calls", "n_plans": P, "iters": a.iters}))
+        print(json.dumps({"what": "two Plan.profile, two Plan.raceline and two Plan.minlap calls", "n_plans": P, "iters": a.iters}))
 
 
 if __name__ == "__main__":
