@@ -1,4 +1,4 @@
-"""The diagonal tiles of the register Cholesky (csrc/qp_solver.hip, `diag_factor`): the MFMA operand of a 4-row panel is built with
+"""The diagonal tiles of the register Cholesky (csrc/qp_solve_kernel.h, `diag_factor`): the MFMA operand of a 4-row panel is built with
 selects on constant lane masks and the diagonal tile is updated ahead of its companions; the former form stays in the source as
 the reference of fsaempc_selftest_diag_factor().  The arithmetic is the same, so nothing may move: a wrong lane mask or a panel
 that reads its tile too early shows up as wrong numbers (against the CPU oracle), a scheduling slip as run-to-run differences or

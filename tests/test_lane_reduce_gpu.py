@@ -1,4 +1,4 @@
-"""The cross-lane reductions of the one-wavefront solve kernel (csrc/qp_solver.hip: grp16_* over a DPP row, single and batched,
+"""The cross-lane reductions of the one-wavefront solve kernel (csrc/qp_lane.h: grp16_* over a DPP row, single and batched,
 q_* over the four rows, wave_*): lane moves that leave the destination's old value undefined, and independent reductions done step
 by step as one batch.  What can go wrong is a call site that is not convergent (a disabled lane then contributes garbage instead of
 a zero), a tree that pairs other lanes than before, or a batch that mixes up its members.  The device self test compares the
