@@ -36,6 +36,7 @@ EXPORTS = [
     "fsaempc_plan_line_lapgrad_batch_device", "fsaempc_plan_minlap_workspace_bytes", "fsaempc_plan_minlap_batch_device",
     "fsaempc_cl_noise_batch_device", "fsaempc_cl_observe_batch_device", "fsaempc_cl_history_slot",
     "fsaempc_cl_estimate_batch_device",
+    "fsaempc_cl_sense_batch_device", "fsaempc_cl_estimate_cart_batch_device",
     "fsaempc_sqp_batch_device_m", "fsaempc_cl_nmpc_shift_batch_device", "fsaempc_cl_nmpc_accept_batch_device",
 ]
 
@@ -118,6 +119,10 @@ class ClLatency(C.Structure):   # fsaempc_cl_latency
 
 class ClEstimator(C.Structure):   # fsaempc_cl_estimator
     _fields_ = [("q", C.c_void_p), ("q_per_instance", C.c_int), ("r", C.c_void_p), ("r_per_instance", C.c_int), ("p0", C.c_void_p), ("L", C.c_double)]
+
+
+class ClSensors(C.Structure):   # fsaempc_cl_sensors
+    _fields_ = [("sigma", C.c_void_p), ("sigma_per_instance", C.c_int), ("seed", C.c_ulonglong), ("id0", C.c_longlong)]
 
 
 class LtvBlocking(C.Structure):
@@ -318,6 +323,9 @@ def lib():
         L.fsaempc_cl_history_slot.argtypes = [C.c_int, ll, C.c_int]
         L.fsaempc_cl_estimate_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(ClEstimator),
                                                        vp, vp, vp, ll] + [vp] * 10
+        L.fsaempc_cl_sense_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(ClSensors), ll] + [vp] * 7
+        L.fsaempc_cl_estimate_cart_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(ClEstimator),
+                                                            vp, vp, vp, ll] + [vp] * 11
         L.fsaempc_sqp_batch_device_m.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams)] + [vp] * 4 + \
             [C.POINTER(QpOpts), C.POINTER(SqpOpts)] + [vp] * 6 + [C.POINTER(SqpAux), vp, ll, vp]
         L.fsaempc_cl_nmpc_shift_batch_device.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 5

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CL_MAX_DELAY, LAP_STATE_INDEX, METRIC_INDEX, NLAPSTATE, NMETRIC, NREPORT, REPORT_INDEX, ClEstimator, ClLatency, ParamBlock, Spline, check,
+from ._lib import (CL_MAX_DELAY, LAP_STATE_INDEX, METRIC_INDEX, NLAPSTATE, NMETRIC, NREPORT, REPORT_INDEX, ClEstimator, ClLatency, ClSensors, ParamBlock, Spline, check,
                    check_blocking, check_laps, lib)
 from .ltvmpc import LtvBatch, dims
 from .corridor import check_corridor
@@ -119,7 +119,9 @@ class Estimator:
     step, validated here without a library call.  All variances are in the model's state layout.  q: process variances per MPC
     period, (nx,) for the batch or (B, nx) per car, finite and >= 0.  r: measurement variances, (nx,) or (B, nx), each finite and
     >= 0 or +inf ("this component is not measured"); None = the squares of the loop's Latency.sigma.  p0: initial variances, (nx,),
-    finite and > 0; None = r where r is finite and > 0, else 1.0 (needs an r for the batch)."""
+    finite and > 0; None = r where r is finite and > 0, else 1.0 (needs an r for the batch).  In a loop with CartesianSensors
+     r is read in the sensor layout, [X, Y, psi, ...], and None = the squares of the sensors' sigma; q and p0 stay in
+    the state layout (so a default p0 takes the sensor variances of (X, Y, psi) for (s, n, mu): the same units)."""
 
     def __init__(self, q, r=None, p0=None):
         def array(v, name):
@@ -149,11 +151,13 @@ class Estimator:
             raise ValueError("p0 must be given with a per-car r")
         self.q, self.r, self.p0 = q, r, p0
 
-    def resolve(self, latency, nx, B, laps=1):
+    def resolve(self, latency, nx, B, laps=1, sensors=None):
         """(q, r, p0) for a loop of B cars with nx states: shapes checked, r and p0 filled in from their defaults."""
         if self.q.shape not in ((nx,), (B, nx)):
             raise ValueError("q must be (nx = %d,) or (B = %d, %d), got %s" % (nx, B, nx, self.q.shape))
         r = self.r
+        if r is None and sensors is not None:
+            r = sensors.sigma ** 2
         if r is None:
             if latency is None or latency.sigma is None:
                 raise ValueError("Estimator(r=None) takes the variances of a Latency with sigma")
@@ -165,18 +169,65 @@ class Estimator:
             if r.ndim != 1:
                 raise ValueError("p0 must be given with a per-car r")
             p0 = np.where(np.isfinite(r) & (r > 0), r, 1.0)
-        if laps > 1 and np.isinf(r[..., 0]).any():
+        if sensors is None and laps > 1 and np.isinf(r[..., 0]).any():   # (with sensors the re-basing reads the projection)
             raise ValueError("laps > 1 needs a measured arc length (r[0] finite): the estimate is re-based on it at the line")
         return self.q, r, p0
 
 
-def check_estimator(estimator, latency, nx, B, laps=1):
+def check_estimator(estimator, latency, nx, B, laps=1, sensors=None):
     """Validates ClosedLoop's estimator argument (no library call): None, or an Estimator resolved to (q, r, p0)."""
     if estimator is None:
         return None
     if not isinstance(estimator, Estimator):
         raise ValueError("estimator must be None or an Estimator")
-    return estimator.resolve(latency, nx, B, laps)
+    return estimator.resolve(latency, nx, B, laps, sensors)
+
+
+class CartesianSensors:
+    """The Cartesian sensor models of a closed loop, validated here without a library call.  sigma: the standard
+    deviations of the measurement noise in the sensor layout -- the model's state layout with (s, n, mu) replaced by (X, Y, psi):
+    kinematic [X, Y, psi, v, delta], dynamic [X, Y, psi, x_d, y_d, theta_d, delta] -- (nx,) for the batch or (B, nx) per car, finite
+    and >= 0 (a zero leaves the component exact).  seed, id0: the noise of car b depends on (seed, id0 + b, period, component) only,
+    as Latency's."""
+
+    def __init__(self, sigma, seed=0, id0=0):
+        def integer(v, name):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError("%s must be an integer" % name)
+            return int(v)
+        self.seed = integer(seed, "seed")
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2^64)")
+        self.id0 = integer(id0, "id0")
+        if not 0 <= self.id0 < 2 ** 63:
+            raise ValueError("id0 must be >= 0 (and below 2^63)")
+        try:
+            sigma = np.array(sigma, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("sigma must be an array of numbers")
+        if sigma.ndim not in (1, 2) or sigma.shape[-1] not in (5, 7):
+            raise ValueError("sigma must be (nx,) or (B, nx), got %s" % (sigma.shape,))
+        if not np.isfinite(sigma).all() or (sigma < 0).any():
+            raise ValueError("sigma must be finite and >= 0")
+        self.sigma = sigma
+
+    def check_batch(self, nx, B):
+        """The shape of sigma against the model and the batch of the loop that takes it."""
+        if self.sigma.shape not in ((nx,), (B, nx)):
+            raise ValueError("sigma must be (nx = %d,) or (B = %d, %d), got %s" % (nx, B, nx, self.sigma.shape))
+
+
+def check_sensors(sensors, latency, nx, B):
+    """Validates ClosedLoop's sensors argument (no library call): None, or a CartesianSensors whose sigma fits (nx,) or (B, nx), next
+    to a latency that adds no noise of its own."""
+    if sensors is None:
+        return None
+    if not isinstance(sensors, CartesianSensors):
+        raise ValueError("sensors must be None or a CartesianSensors")
+    sensors.check_batch(nx, B)
+    if latency is not None and latency.sigma is not None:
+        raise ValueError("sensors and Latency(sigma=...) are two noise sources: with sensors the latency carries the delay only")
+    return sensors
 
 
 class Nmpc:
@@ -274,7 +325,7 @@ class ClosedLoop:
 
     def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
                  params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6, corridor=None, laps=1,
-                 latency=None, estimator=None, controller=None):
+                 latency=None, estimator=None, controller=None, sensors=None):
         """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
         None = the same as params (both None: the reference's constants compiled into the kernels).  blocking: block lengths of the
         controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2).  reference: None = the live
@@ -308,7 +359,15 @@ class ClosedLoop:
         and the status otherwise.  self.mpc stays: its descriptor, spline and params serve the observer, the estimator and the
         metrics.  The SQP call blocks the host once per sweep (it reads the number of instances still running), so in this mode step()
         is no longer free of read-backs.  Not available with corridor=, a non-trivial blocking= (NotImplementedError) or
-        warm_start=True (ValueError: that flag is the QP's x_init; Nmpc(warm_start=...) is the SQP's own)."""
+        warm_start=True (ValueError: that flag is the QP's x_init; Nmpc(warm_start=...) is the SQP's own).
+        sensors: None or a CartesianSensors.  None launches what the loop launches without the argument.  Otherwise
+        step() measures the car in the Cartesian frame after pre() and the lap gate (self.y_meas, sensor layout) and projects the
+        measurement onto the track (self.x_proj; self.proj_lost counts the projections that lost the track and fell back to x0).
+        With an estimator the filter reads y_meas through h(x) (fsaempc_cl_estimate_cart_batch_device; Estimator.r in the sensor
+        layout, None = sigma^2; first prior, re-initialisation and re-basing from x_proj, so laps > 1 needs no measured arc length);
+        without one the loop drives on x_proj.  The latency's prediction then runs on that state if it compensates, x_ref is
+        regenerated and the controller solves from it.  self.x0 stays the true state (the gate and the metrics read it).  Not
+        together with a Latency that has a sigma (ValueError: two noise sources)."""
         self.controller = check_controller(controller, corridor, blocking, N, warm_start)   # (before the library is touched)
         if not (float(slack_tol) >= 0):
             raise ValueError("slack_tol must be >= 0")
@@ -323,7 +382,8 @@ class ClosedLoop:
         self.reference = reference
         check_corridor(corridor, np.asarray(cart0).size // 7, device)   # (before the library is touched)
         self.latency = check_latency(latency, 5 if model == 0 else 7, np.asarray(cart0).size // 7)   # (likewise)
-        self._est_arrays = check_estimator(estimator, latency, 5 if model == 0 else 7, np.asarray(cart0).size // 7, self.laps)   # (likewise)
+        self.sensors = check_sensors(sensors, self.latency, 5 if model == 0 else 7, np.asarray(cart0).size // 7)   # (likewise)
+        self._est_arrays = check_estimator(estimator, latency, 5 if model == 0 else 7, np.asarray(cart0).size // 7, self.laps, self.sensors)   # (likewise)
         self.estimator = estimator
         if self.latency is not None and not self.latency.engaged:
             self.latency = None
@@ -391,6 +451,16 @@ class ClosedLoop:
                 self._lat_pred = ClLatency(lat.delay, int(lat.compensate), None, 0, lat.seed, lat.id0)
                 if not lat.compensate:
                     self.x0_mpc = self.x0_est
+        self.y_meas = self.x_proj = self.proj_lost = None
+        if self.sensors is not None:
+            self._sens_sigma = torch.from_numpy(np.ascontiguousarray(self.sensors.sigma)).to(self.device)
+            self._sens = ClSensors(C.c_void_p(self._sens_sigma.data_ptr()), 1 if self._sens_sigma.dim() == 2 else 0, self.sensors.seed, self.sensors.id0)
+            self.y_meas = torch.zeros_like(self.x0)
+            self.x_proj = torch.zeros_like(self.x0)
+            self.proj_lost = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+            if self.estimator is None and self.latency is None:
+                self._s0_mpc = torch.empty(self.B, dtype=torch.float64, device=self.device)
+                self.x0_mpc = self.x_proj
         self.metrics = torch.zeros((self.B, NMETRIC), dtype=torch.float64, device=self.device) if metrics else None
         self.lap_state = self.lap_times = self.lap_records = None   # laps == 1: nothing is allocated unless lap_gate() is called
         if self.laps > 1:
@@ -519,6 +589,37 @@ class ClosedLoop:
         self._reference_from(self.x0_mpc, stream)
         return self.x0_mpc
 
+    def sense(self, stream=None):
+        """Measurement and naive projection of this period on what pre() and the lap gate left (fsaempc_cl_sense_batch_device)."""
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(lib().fsaempc_cl_sense_batch_device(C.byref(self.mpc.desc), C.byref(self.mpc.sp), C.byref(self._sens), self.steps, P(self.cart), P(self.x0),
+                                                  P(self.finished), P(self.y_meas), P(self.x_proj), P(self.proj_lost), self._stream(stream)),
+              "fsaempc_cl_sense_batch_device")
+
+    def sensed_state(self, stream=None):
+        """Measurement, projection, filter (with an estimator) and prediction (with a compensating latency) of this period
+        (DESIGN.md 6s), then x_ref regenerated from the state the solve reads, which is returned."""
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._fill_history()
+        self.sense(stream)
+        state = self.x_proj
+        if self.estimator is not None:
+            check(lib().fsaempc_cl_estimate_cart_batch_device(C.byref(self.mpc.desc), C.byref(self.mpc.sp),
+                                                              self.mpc.params.ref() if self.mpc.params is not None else None, C.byref(self._est),
+                                                              P(self.y_meas), P(self.x_proj), P(self.prev_input()), 2 * self.N, P(self.finished),
+                                                              P(self.est_x), P(self.est_P), P(self.est_count), P(self.x0_est), P(self.est_innov),
+                                                              P(self.est_nis), None, None, None, self._stream(stream)),
+                  "fsaempc_cl_estimate_cart_batch_device")
+            state = self.x0_est
+            if self.latency is not None and self.latency.compensate:
+                self._observe_call(self._lat_pred, self.x0_est, self._obs_scratch, self.x0_mpc, stream)
+                state = self.x0_mpc
+        elif self.latency is not None:   # (no sigma next to sensors: x0_obs is a copy of x_proj, x0_mpc its prediction)
+            self._observe_call(self._lat, self.x_proj, self.x0_obs, self.x0_mpc, stream)
+            state = self.x0_mpc
+        self._reference_from(state, stream)
+        return state
+
     def _nmpc_step(self, x0, stream):
         """Shift, SQP and take-over of one period under an Nmpc controller; x0: the state the solve reads."""
         torch, c = self.torch, self.controller
@@ -552,7 +653,9 @@ class ClosedLoop:
             if self._slack is not None:
                 x_init[:, nu:].copy_(self._slack)
         x0 = self.x0
-        if self.estimator is not None:
+        if self.sensors is not None:
+            x0 = self.sensed_state(stream)
+        elif self.estimator is not None:
             x0 = self.estimate(stream)
         elif self.latency is not None:
             self.observe(stream)
@@ -617,10 +720,11 @@ def monte_carlo_carts(track, B, seed, lap=False):
 
 
 def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
-                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1, latency=None, estimator=None, controller=None):
+                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1, latency=None, estimator=None, controller=None, sensors=None):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
     reference: None (the live ramp) or a Plan the cars track (ClosedLoop).  metrics: ClosedLoop(metrics=True); cl.report() afterwards.
     corridor: None or a Corridor (ClosedLoop).  laps: ClosedLoop(laps=...); cl.lap_times afterwards.  latency: None or a Latency (ClosedLoop).  estimator: None or an Estimator (ClosedLoop).
+    sensors: None or a CartesianSensors (ClosedLoop).
     controller: None (the LTV-MPC step) or an Nmpc (ClosedLoop; the tallies are then the take-over's exit flags and the SQP's QP iterations).
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
@@ -628,7 +732,7 @@ def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cud
     cart0, s_init = monte_carlo_carts(track, B, seed)
     cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
                     params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics, corridor=corridor, laps=laps,
-                    latency=latency, estimator=estimator, controller=controller)
+                    latency=latency, estimator=estimator, controller=controller, sensors=sensors)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

@@ -1,11 +1,12 @@
 // capi_cl.hip -- the C ABI of libfsaempc.so (include/fsaempc.h), closed-loop part: reference, pre, plant and accept, the metrics
-// and the lap gate with their two host-side reports, measurement noise, observation, the state estimator and the SQP as the controller.  Host-side glue only:
+// and the lap gate with their two host-side reports, measurement noise, observation, the state estimator, the Cartesian sensor models and the SQP as the controller.  Host-side glue only:
 // argument checks and kernel launches.
 #include "capi_common.h"
 #include "reference.h"
 #include "plant.h"
 #include "cl_latency.h"
 #include "cl_estimator.h"
+#include "cl_sensors.h"
 #include "cl_nmpc.h"
 using namespace capi;
 
@@ -210,6 +211,17 @@ static bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
   return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
 }
 
+// no output may overlap another output or an input
+static int ranges_check(const ByteRange* out, int n_out, const ByteRange* in, int n_in) {
+  for (int i = 0; i < n_out; ++i) {
+    for (int k = i + 1; k < n_out; ++k)
+      if (ranges_overlap(out[i], out[k])) return fail(FSAEMPC_ERR_ARG, "overlapping outputs");
+    for (int k = 0; k < n_in; ++k)
+      if (ranges_overlap(out[i], in[k])) return fail(FSAEMPC_ERR_ARG, "an output overlaps an input");
+  }
+  return 0;
+}
+
 int fsaempc_cl_estimate_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
                                      const fsaempc_cl_estimator* est, const double* z, const double* x_start, const double* u_prev,
                                      long long u_stride, const int* finished, double* est_x, double* est_P, int* est_count, double* x0_est,
@@ -227,13 +239,7 @@ int fsaempc_cl_estimate_batch_device(const fsaempc_ltv_desc* desc, const fsaempc
                           {"u_prev", u_prev, B ? ((B - 1) * (size_t)u_stride + 2) * d : 0}, {"finished", finished, B * sizeof(int)},
                           {"q", est->q, (est->q_per_instance ? B : 1) * nx * d}, {"r", est->r, (est->r_per_instance ? B : 1) * nx * d},
                           {"p0", est->p0, nx * d}};
-  const int n_out = (int)(sizeof(out) / sizeof(out[0])), n_in = (int)(sizeof(in) / sizeof(in[0]));
-  for (int i = 0; i < n_out; ++i) {
-    for (int k = i + 1; k < n_out; ++k)
-      if (ranges_overlap(out[i], out[k])) return fail(FSAEMPC_ERR_ARG, "overlapping outputs");
-    for (int k = 0; k < n_in; ++k)
-      if (ranges_overlap(out[i], in[k])) return fail(FSAEMPC_ERR_ARG, "an output overlaps an input");
-  }
+  if (int rc = ranges_check(out, (int)(sizeof(out) / sizeof(out[0])), in, (int)(sizeof(in) / sizeof(in[0])))) return rc;
   if (desc->batch == 0) return 0;
   ClEstimateParams P;
   P.nx = (int)nx; P.batch = desc->batch; P.integ = ltv_integ(desc); P.q_per_instance = est->q_per_instance ? 1 : 0;
@@ -242,6 +248,68 @@ int fsaempc_cl_estimate_batch_device(const fsaempc_ltv_desc* desc, const fsaempc
   P.q = est->q; P.r = est->r; P.p0 = est->p0; P.z = z; P.x_start = x_start; P.u_prev = u_prev; P.u_stride = u_stride; P.finished = finished;
   P.est_x = est_x; P.est_P = est_P; P.est_count = est_count; P.x0_est = x0_est; P.innov = innov; P.nis = nis; P.F_out = F_out; P.x_prior = x_prior;
   return launched(cl_estimate_launch(P, (hipStream_t)stream, par_values(par), par_stride(par)), "cl_estimate_launch");
+}
+
+/* ---- closed loop: Cartesian sensor models ---- */
+int fsaempc_cl_sense_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_cl_sensors* sens, long long step,
+                                  const double* cart, const double* x0_true, const int* finished, double* y, double* x_proj, int* proj_lost,
+                                  void* stream) {
+  if (int rc = ltv_check(desc, sp)) return rc;
+  if (!sens) return fail(FSAEMPC_ERR_ARG, "null argument (sens)");
+  if (!sens->sigma) return fail(FSAEMPC_ERR_ARG, "null argument (sens->sigma)");
+  if (int rc = cl_draw_check(sens->id0, step)) return rc;
+  if (!cart) return fail(FSAEMPC_ERR_ARG, "null argument (cart)");
+  if (!x0_true) return fail(FSAEMPC_ERR_ARG, "null argument (x0_true)");
+  if (!y) return fail(FSAEMPC_ERR_ARG, "null argument (y)");
+  if (!x_proj) return fail(FSAEMPC_ERR_ARG, "null argument (x_proj)");
+  if (!proj_lost) return fail(FSAEMPC_ERR_ARG, "null argument (proj_lost)");
+  const size_t B = (size_t)desc->batch, nx = (size_t)fsaempc_ltv_nx(desc->model), d = sizeof(double);
+  const ByteRange out[] = {{"y", y, B * nx * d}, {"x_proj", x_proj, B * nx * d}, {"proj_lost", proj_lost, B * sizeof(int)}};
+  const ByteRange in[] = {{"cart", cart, B * 7 * d}, {"x0_true", x0_true, B * nx * d}, {"finished", finished, B * sizeof(int)},
+                          {"sigma", sens->sigma, (sens->sigma_per_instance ? B : 1) * nx * d}};
+  if (int rc = ranges_check(out, (int)(sizeof(out) / sizeof(out[0])), in, (int)(sizeof(in) / sizeof(in[0])))) return rc;
+  if (desc->batch == 0) return 0;
+  ClSenseParams P;
+  P.nx = (int)nx; P.batch = desc->batch; P.sigma_per_instance = sens->sigma_per_instance ? 1 : 0;
+  P.seed = sens->seed; P.id0 = (unsigned long long)sens->id0; P.step = (unsigned long long)step;
+  set_spline(&P, sp);
+  P.sigma = sens->sigma; P.cart = cart; P.x0_true = x0_true; P.finished = finished; P.y = y; P.x_proj = x_proj; P.proj_lost = proj_lost;
+  return launched(cl_sense_launch(P, (hipStream_t)stream), "cl_sense_launch");
+}
+
+int fsaempc_cl_estimate_cart_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                          const fsaempc_cl_estimator* est, const double* y, const double* x_proj, const double* u_prev,
+                                          long long u_stride, const int* finished, double* est_x, double* est_P, int* est_count, double* x0_est,
+                                          double* innov, double* nis, double* F_out, double* x_prior, double* H_out, void* stream) {
+  if (int rc = ltv_check(desc, sp)) return rc;
+  if (!est) return fail(FSAEMPC_ERR_ARG, "null argument (est)");
+  if (!est->q) return fail(FSAEMPC_ERR_ARG, "null argument (est->q)");
+  if (!est->r) return fail(FSAEMPC_ERR_ARG, "null argument (est->r)");
+  if (!est->p0) return fail(FSAEMPC_ERR_ARG, "null argument (est->p0)");
+  if (!(est->L >= 0 && est->L < INFINITY)) return fail(FSAEMPC_ERR_ARG, "L must be finite and >= 0");
+  if (u_stride < 2) return fail(FSAEMPC_ERR_ARG, "u_stride must be >= 2");
+  const struct { const char* name; const void* p; } need[] = {{"y", y}, {"x_proj", x_proj}, {"u_prev", u_prev}, {"est_x", est_x}, {"est_P", est_P},
+                                                               {"est_count", est_count}, {"x0_est", x0_est}, {"innov", innov}, {"nis", nis}};
+  for (const auto& n : need)
+    if (!n.p) return fail(FSAEMPC_ERR_ARG, "null argument (%s)", n.name);
+  const size_t B = (size_t)desc->batch, nx = (size_t)fsaempc_ltv_nx(desc->model), d = sizeof(double);
+  const ByteRange out[] = {{"est_x", est_x, B * nx * d}, {"est_P", est_P, B * nx * nx * d}, {"est_count", est_count, B * 2 * sizeof(int)},
+                           {"x0_est", x0_est, B * nx * d}, {"innov", innov, B * nx * d}, {"nis", nis, B * d},
+                           {"F_out", F_out, B * nx * nx * d}, {"x_prior", x_prior, B * nx * d}, {"H_out", H_out, B * nx * nx * d}};
+  const ByteRange in[] = {{"y", y, B * nx * d}, {"x_proj", x_proj, B * nx * d},
+                          {"u_prev", u_prev, B ? ((B - 1) * (size_t)u_stride + 2) * d : 0}, {"finished", finished, B * sizeof(int)},
+                          {"q", est->q, (est->q_per_instance ? B : 1) * nx * d}, {"r", est->r, (est->r_per_instance ? B : 1) * nx * d},
+                          {"p0", est->p0, nx * d}};
+  if (int rc = ranges_check(out, (int)(sizeof(out) / sizeof(out[0])), in, (int)(sizeof(in) / sizeof(in[0])))) return rc;
+  if (desc->batch == 0) return 0;
+  ClEstimateCartParams P;
+  P.nx = (int)nx; P.batch = desc->batch; P.integ = ltv_integ(desc); P.q_per_instance = est->q_per_instance ? 1 : 0;
+  P.r_per_instance = est->r_per_instance ? 1 : 0; P.dt = desc->dt; P.L = est->L;
+  set_spline(&P, sp);
+  P.q = est->q; P.r = est->r; P.p0 = est->p0; P.y = y; P.x_proj = x_proj; P.u_prev = u_prev; P.u_stride = u_stride; P.finished = finished;
+  P.est_x = est_x; P.est_P = est_P; P.est_count = est_count; P.x0_est = x0_est; P.innov = innov; P.nis = nis; P.F_out = F_out; P.x_prior = x_prior;
+  P.H_out = H_out;
+  return launched(cl_estimate_cart_launch(P, (hipStream_t)stream, par_values(par), par_stride(par)), "cl_estimate_cart_launch");
 }
 
 /* ---- closed loop: the batched SQP as the controller ---- */

@@ -1065,6 +1065,61 @@ int fsaempc_cl_estimate_batch_device(const fsaempc_ltv_desc* desc, const fsaempc
                                      double* x0_est, double* innov, double* nis /* batch */,
                                      double* F_out /* optional, batch x nx x nx */, double* x_prior /* optional, batch x nx */, void* stream);
 
+/* ---- closed loop: Cartesian sensor models ----------------------------------------------
+ * What the car measures is not the curvilinear state the MPC uses but its pose and motion in the Cartesian frame.  The sensor layout
+ * is the model's state layout with (s, n, mu) replaced by (X, Y, psi): kinematic [X, Y, psi, v, delta], dynamic
+ * [X, Y, psi, x_d, y_d, theta_d, delta].  Out of the plant's 7 Cartesian states c the exact measurement is, as the pre-step assembles
+ * x0: kinematic y_true = [c0, c1, c2, sqrt(c3^2 + c4^2), c6], dynamic y_true = c.  Opt-in like the entries above.
+ *
+ * fsaempc_cl_sense_batch_device: one call per MPC period after the pre-step (and the lap gate), on the same stream.
+ *   measurement   y[i] = y_true[i] + sigma[i] z_i(seed, id0 + b, step): the draws, their counter layout and the observation rule of
+ *                 fsaempc_cl_observe_batch_device, component i of the sensor layout taking draw i (sigma[i] == 0 copies).
+ *   projection    x_proj = the pre-step's frame transform (Newton closest point, n, mu, x0 assembly) of the Cartesian vector y stands
+ *                 for -- kinematic (y0, y1, y2, y3, 0, 0, y4), dynamic y -- with the Newton search started at x0_true[b][0]: the
+ *                 true arc length selects the lap and the branch, it is not a measurement.  The lap check of the transform is not
+ *                 used.  If the transform loses the track (its out-of-race rule): x_proj[b] = x0_true[b] bit for bit and
+ *                 proj_lost[b] += 1 (proj_lost: batch ints, zeroed by the caller).
+ *   finished      finished[b] != 0: y = y_true and x_proj = x0_true, bit for bit.
+ * x_proj is what a loop without a filter drives on, and the filter's first prior and re-initialisation state.
+ * FSAEMPC_ERR_ARG before any launch: what the LTV entries refuse in desc and sp; sens or sens->sigma NULL; id0 < 0; step < 0 or
+ * >= 2^32; cart, x0_true, y, x_proj or proj_lost NULL; an output that overlaps another output or an input.  desc->batch == 0
+ * succeeds without a launch. */
+typedef struct {
+  const double* sigma;       /* device; nx values (sensor layout), or batch * nx (sigma_per_instance) */
+  int sigma_per_instance;
+  unsigned long long seed;
+  long long id0;             /* id of instance 0 (a shard's first global id) */
+} fsaempc_cl_sensors;
+
+int fsaempc_cl_sense_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_cl_sensors* sens, long long step,
+                                  const double* cart /* batch x 7 */, const double* x0_true /* batch x nx */, const int* finished /* optional */,
+                                  double* y /* batch x nx */, double* x_proj /* batch x nx */, int* proj_lost /* batch */, void* stream);
+
+/* fsaempc_cl_estimate_cart_batch_device: the filter of fsaempc_cl_estimate_batch_device reading the Cartesian measurement.  What the
+ * caller keeps, the model, Q and P0 are those of that entry, in the state layout; est->r is in the sensor layout.  The measurement
+ * function is h(x) (vehicle_models/curvilinear_to_cartesian.m:16-28): with the two Bezier tables at s, t = (-Y', X') / |(X', Y')|,
+ * h0 = X + n t_x, h1 = Y + n t_y, h2 = atan2(Y', X') + mu, h_i = x_i for i >= 3; H = dh/dx is exact (forward mode through the same
+ * code) and differs from the identity in rows and columns 0 .. 2 only.  Steps 1 .. 8 of that entry hold with x_proj in the place of
+ * z in steps 1, 4 and 7 and of x_start in step 2, and with
+ *   5 re-basing   if L > 0: x-[0] += L rint((x_proj[0] - x-[0]) / L) (the projection always carries an arc length).
+ *   6 update      the EKF update linearised once at the prior and processed row by row: nu0 = y - h(x-), the heading entry wrapped
+ *                 to [-pi, pi] (MATLAB's angdiff(h2, y2)), H = dh/dx(x-).  For i = 0 .. nx - 1, measured components only:
+ *                 nu_i = nu0_i - H_i (x - x-), c = P H_i', s_i = H_i c + r_i; unless s_i > 0 the component is skipped;
+ *                 x_a += c_a nu_i / s_i, P_ab -= (c_a c_b) / s_i (exactly symmetric).  innov_i = nu_i (0 for an unmeasured
+ *                 component), nis = sum of nu_i^2 / s_i over the components applied.  For diagonal R this is the joint update
+ *                 K = P H' (H P H' + R)^-1 with that H.
+ *   7 check       as there; step 6 then runs again from x- = x_proj, linearised at x_proj.
+ * H_out is the H the applied update was linearised with (the identity for a finished car).
+ * FSAEMPC_ERR_ARG before any launch: what fsaempc_cl_estimate_batch_device refuses, with y and x_proj in the places of z and
+ * x_start.  desc->batch == 0 succeeds without a launch. */
+int fsaempc_cl_estimate_cart_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                          const fsaempc_cl_estimator* est, const double* y /* batch x nx */, const double* x_proj /* batch x nx */,
+                                          const double* u_prev, long long u_stride /* doubles between cars */, const int* finished /* optional */,
+                                          double* est_x, double* est_P, int* est_count /* batch x 2, zeroed by the caller */,
+                                          double* x0_est, double* innov, double* nis /* batch */,
+                                          double* F_out /* optional, batch x nx x nx */, double* x_prior /* optional, batch x nx */,
+                                          double* H_out /* optional, batch x nx x nx */, void* stream);
+
 /* ---- closed loop: the batched SQP (nonlinear MPC) as the controller (main.m:118-160, MODE = "MS-NMPC") ----------
  * Between the pre-step (and lap gate, observation, estimator) and the plant, in place of the LTV step and
  * fsaempc_cl_accept_batch_device: shift -> fsaempc_sqp_batch_device_m -> accept.  Both entries return FSAEMPC_ERR_ARG, with a text

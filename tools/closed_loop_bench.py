@@ -28,6 +28,10 @@ state-estimate noise with these standard deviations (the model's state layout: 5
 and the solve: process variances per period, measurement variances (default: the squares of --noise) and the indices of components that
 are not measured (their variance becomes +inf).  Echoed as "estimator", with the batch's re-initialisations and the mean NIS over the
 driving cars' periods.
+--sensors s1,...,snx [--sensor-seed S]: Cartesian sensor models (fsaempc.CartesianSensors): the car measures
+[X, Y, psi, v, delta] (kinematic) or [X, Y, psi, x_d, y_d, theta_d, delta] (dynamic) with these standard deviations; without --estimator the
+loop drives on the projection of the measurement, with it the filter reads the measurement through h(x) (--meas-var is then in the
+sensor layout and defaults to the squares of --sensors).  Excludes --noise.  Echoed as "sensors", with the projections that lost the track.
 --nmpc K [--nmpc-trials T] [--nmpc-timing]: the batched SQP of the nonlinear problem as the controller (fsaempc.Nmpc), K sweeps
 per period, warm-started from the previous period's plan shifted by one stage.  "value" then counts the periods of driving cars that
 ended with status 0 or 1; "nmpc" joins the JSON line: the status shares over the driving cars' periods, mean sweeps and QP iterations per
@@ -37,6 +41,7 @@ usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--
                                   [--corridor FILE.npz | --cones FILE [--car-half-width W]] [--line-rows points|cells]
                                   [--delay D [--compensate]] [--noise s1,...,snx [--noise-seed S]]
                                   [--estimator q1,...,qnx [--meas-var r1,...,rnx] [--unmeasured i,j]]
+                                  [--sensors s1,...,snx [--sensor-seed S]]
                                   [--nmpc K [--nmpc-trials T] [--nmpc-timing]]"""
 import argparse, json, os, sys, time
 import numpy as np
@@ -80,6 +85,8 @@ def main():
     ap.add_argument("--estimator", default=None, metavar="q1,...,qnx", help="run the EKF state estimator with these process variances per period (Estimator)")
     ap.add_argument("--meas-var", default=None, metavar="r1,...,rnx", help="with --estimator: measurement variances (default: the squares of --noise)")
     ap.add_argument("--unmeasured", default=None, metavar="i,j", help="with --estimator: state components that are not measured (variance +inf)")
+    ap.add_argument("--sensors", default=None, metavar="s1,...,snx", help="Cartesian sensor models: standard deviations in the sensor layout (CartesianSensors); excludes --noise")
+    ap.add_argument("--sensor-seed", type=int, default=0, metavar="S", help="with --sensors: seed of the counter-based generator")
     ap.add_argument("--nmpc", type=int, default=None, metavar="K", help="the batched SQP as the controller, K sweeps per period (Nmpc); excludes --corridor, --cones and --warm")
     ap.add_argument("--nmpc-trials", type=int, default=None, metavar="T", help="with --nmpc: step lengths the line search tries at once (default 8)")
     ap.add_argument("--nmpc-timing", action="store_true", help="with --nmpc: the SQP's phase sums by device events (fsaempc_qp_set_timing: one more synchronisation per sweep)")
@@ -107,24 +114,37 @@ def main():
         ap.error(str(e))
     est = None
     nx_ = 5 if a.model == "kinematic" else 7
+    sens = sens_sigma = None
+    if a.sensors is not None:
+        if a.noise is not None:
+            ap.error("--sensors excludes --noise (two noise sources)")
+        try:
+            sens_sigma = [float(v) for v in a.sensors.split(",")]
+        except ValueError:
+            ap.error("--sensors takes comma-separated numbers")
+        try:
+            sens = fm.CartesianSensors(sens_sigma, seed=a.sensor_seed)
+            sens.check_batch(nx_, a.batch)
+        except ValueError as e:
+            ap.error(str(e))
     if a.estimator is None and (a.meas_var is not None or a.unmeasured is not None):
         ap.error("--meas-var and --unmeasured need --estimator")
     if a.estimator is not None:
         try:
             q = [float(v) for v in a.estimator.split(",")]
-            r = [float(v) for v in a.meas_var.split(",")] if a.meas_var is not None else ([v * v for v in sigma] if sigma is not None else None)
+            r = [float(v) for v in a.meas_var.split(",")] if a.meas_var is not None else ([v * v for v in (sigma if sigma is not None else sens_sigma)] if sigma is not None or sens_sigma is not None else None)
             skip = [int(v) for v in a.unmeasured.split(",")] if a.unmeasured is not None else []
         except ValueError:
             ap.error("--estimator and --meas-var take comma-separated numbers, --unmeasured comma-separated indices")
         if r is None:
-            ap.error("--estimator needs --meas-var or --noise")
+            ap.error("--estimator needs --meas-var, --noise or --sensors")
         if len(r) != nx_ or any(not 0 <= i < nx_ for i in skip):
             ap.error("--meas-var takes %d values, --unmeasured indices 0 .. %d" % (nx_, nx_ - 1))
         for i in skip:
             r[i] = float("inf")
         try:
             est = fm.Estimator(q, r)
-            est.resolve(lat, nx_, a.batch, a.laps)
+            est.resolve(lat, nx_, a.batch, a.laps, sens)
         except ValueError as e:
             ap.error(str(e))
     if a.corridor is not None and a.cones is not None:
@@ -164,7 +184,7 @@ def main():
         plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip, corridor=cor, rows=a.line_rows)
     if a.minlap is not None:
         plan = fm.Plan.minlap(model, tr, N_s=a.cells, N_c=a.points, iters=a.minlap, margin=a.margin, grip=a.grip, corridor=cor)
-    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor, latency=lat, estimator=est, controller=ctl)          # warm-up (allocations, code load)
+    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor, latency=lat, estimator=est, controller=ctl, sensors=sens)          # warm-up (allocations, code load)
     n_max = float(fm.default_params(model)[fm.PARAM_INDEX["N_MAX"]])
     opts = fm.default_opts(max_iter=a.max_iter)
     t0 = time.perf_counter()
@@ -172,7 +192,7 @@ def main():
     # every car while it drives
     cart0, s_init = fm.monte_carlo_carts(tr, a.batch, a.seed, lap=a.lap)
     cl = fm.ClosedLoop(model, a.horizon, 0.05, tr, cart0, options=opts, warm_start=a.warm, launch_hint=not a.no_launch_hint, reference=plan,
-                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps, latency=lat, estimator=est, controller=ctl)
+                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps, latency=lat, estimator=est, controller=ctl, sensors=sens)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]
     fl_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
@@ -242,6 +262,8 @@ def main():
                                      "cars_reset": int((cl.est_resets > 0).sum().item()),
                                      "nis_mean": float((nis_sum / nis_cnt.clamp(min=1)).item()), "nis_periods": int(nis_cnt.item()),
                                      "measured_components": nx_ - len(skip)}} if est is not None else {}),
+                   **({"sensors": {"sigma": sens_sigma, "seed": a.sensor_seed, "filter": est is not None, "projections_lost": int(cl.proj_lost.sum().item()),
+                                   "cars_with_a_lost_projection": int((cl.proj_lost > 0).sum().item())}} if sens is not None else {}),
                    "controller": "LTV-MPC" if ctl is None else "MS-NMPC (batched SQP)", **({"nmpc": nmpc} if nmpc is not None else {}),
                    **({"cones": cone_info} if cone_info is not None else {}), "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
                    # (a mean over an empty set is NaN in the report: null in the JSON line)
