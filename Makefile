@@ -42,6 +42,10 @@ $(LIBDIR)/cl_estimator.o $(LIBDIR)/capi_cl.o: $(CSRC)/cl_estimator.h
 $(LIBDIR)/cl_sensors.o $(LIBDIR)/capi_cl.o: $(CSRC)/cl_sensors.h
 $(LIBDIR)/cl_sensors.o: $(CSRC)/cl_latency.h $(CSRC)/cl_estimator.h
 
+# cone-based localisation: the cone sensor's unit; the filter with the cone rows lives in the unit of the Cartesian filter
+$(LIBDIR)/cl_cone_loc.o $(LIBDIR)/cl_sensors.o $(LIBDIR)/capi_cl.o: $(CSRC)/cl_cone_loc.h
+$(LIBDIR)/cl_cone_loc.o: $(CSRC)/cl_latency.h $(CSRC)/cl_sensors.h $(CSRC)/qp_lane.h
+
 # the SQP as the controller of the closed loop: likewise, and the SQP's host loop (its skip mask)
 $(LIBDIR)/cl_nmpc.o $(LIBDIR)/capi_cl.o $(LIBDIR)/capi_ltv.o: $(CSRC)/cl_nmpc.h
 
@@ -70,7 +74,7 @@ $(LIBDIR)/track.o: $(CSRC)/track.cpp include/fsaempc.h
 	@mkdir -p $(LIBDIR)
 	g++ -O2 -std=c++17 -fPIC -Wall -Iinclude -c $< -o $@
 
-COMMON := $(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o $(LIBDIR)/sqp.o $(LIBDIR)/qp_sens.o $(LIBDIR)/reference.o $(LIBDIR)/plant.o $(LIBDIR)/cl_latency.o $(LIBDIR)/cl_estimator.o $(LIBDIR)/cl_sensors.o $(LIBDIR)/cl_nmpc.o $(LIBDIR)/planner.o $(LIBDIR)/raceline.o $(LIBDIR)/minlap.o $(LIBDIR)/corridor.o $(LIBDIR)/cones.o $(CAPIOBJ) $(LIBDIR)/track.o
+COMMON := $(LIBDIR)/ltv_build.o $(LIBDIR)/ltv_build_blocked.o $(LIBDIR)/sqp.o $(LIBDIR)/qp_sens.o $(LIBDIR)/reference.o $(LIBDIR)/plant.o $(LIBDIR)/cl_latency.o $(LIBDIR)/cl_estimator.o $(LIBDIR)/cl_sensors.o $(LIBDIR)/cl_cone_loc.o $(LIBDIR)/cl_nmpc.o $(LIBDIR)/planner.o $(LIBDIR)/raceline.o $(LIBDIR)/minlap.o $(LIBDIR)/corridor.o $(LIBDIR)/cones.o $(CAPIOBJ) $(LIBDIR)/track.o
 $(LIBDIR)/libfsaempc.so: $(QPOBJ) $(WGOBJ) $(COMMON)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

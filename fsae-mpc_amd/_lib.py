@@ -37,6 +37,7 @@ EXPORTS = [
     "fsaempc_cl_noise_batch_device", "fsaempc_cl_observe_batch_device", "fsaempc_cl_history_slot",
     "fsaempc_cl_estimate_batch_device",
     "fsaempc_cl_sense_batch_device", "fsaempc_cl_estimate_cart_batch_device",
+    "fsaempc_cl_cone_sense_batch_device", "fsaempc_cl_estimate_cones_batch_device",
     "fsaempc_sqp_batch_device_m", "fsaempc_cl_nmpc_shift_batch_device", "fsaempc_cl_nmpc_accept_batch_device",
 ]
 
@@ -125,6 +126,9 @@ class ClSensors(C.Structure):   # fsaempc_cl_sensors
     _fields_ = [("sigma", C.c_void_p), ("sigma_per_instance", C.c_int), ("seed", C.c_ulonglong), ("id0", C.c_longlong)]
 
 
+CONE_OBS_MAX = 16    # FSAEMPC_CONE_OBS_MAX
+
+
 class LtvBlocking(C.Structure):
     _fields_ = [("n_blocks", C.c_int), ("len", C.POINTER(C.c_int))]
 
@@ -155,6 +159,11 @@ CONE_INFO_INDEX = {name: i for i, name in enumerate(
 
 class ConeMaps(C.Structure):   # fsaempc_cones
     _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("n_left", C.c_int), ("n_right", C.c_int), ("per_corridor", C.c_int)]
+
+
+class ClConeSensor(C.Structure):   # fsaempc_cl_cone_sensor
+    _fields_ = [("truth", C.POINTER(ConeMaps)), ("r_min", C.c_double), ("r_max", C.c_double), ("fov", C.c_double), ("sigma_range", C.c_double),
+                ("sigma_bearing", C.c_double), ("p_detect", C.c_double), ("k_max", C.c_int), ("seed", C.c_ulonglong), ("id0", C.c_longlong)]
 
 
 def check_blocking(blocking, N):
@@ -326,6 +335,9 @@ def lib():
         L.fsaempc_cl_sense_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(ClSensors), ll] + [vp] * 7
         L.fsaempc_cl_estimate_cart_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(ClEstimator),
                                                             vp, vp, vp, ll] + [vp] * 11
+        L.fsaempc_cl_cone_sense_batch_device.argtypes = [C.c_int, C.POINTER(ClConeSensor), ll] + [vp] * 7
+        L.fsaempc_cl_estimate_cones_batch_device.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams), C.POINTER(ClEstimator),
+                                                             vp, vp, vp, ll] + [vp] * 10 + [C.POINTER(ConeMaps), C.c_int, C.POINTER(C.c_double)] + [vp] * 7
         L.fsaempc_sqp_batch_device_m.argtypes = [C.POINTER(LtvDesc), C.POINTER(Spline), C.POINTER(LtvParams)] + [vp] * 4 + \
             [C.POINTER(QpOpts), C.POINTER(SqpOpts)] + [vp] * 6 + [C.POINTER(SqpAux), vp, ll, vp]
         L.fsaempc_cl_nmpc_shift_batch_device.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 5

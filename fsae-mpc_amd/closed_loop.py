@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CL_MAX_DELAY, LAP_STATE_INDEX, METRIC_INDEX, NLAPSTATE, NMETRIC, NREPORT, REPORT_INDEX, ClEstimator, ClLatency, ClSensors, ParamBlock, Spline, check,
+from ._lib import (CL_MAX_DELAY, CONE_OBS_MAX, CONES_MAX, LAP_STATE_INDEX, METRIC_INDEX, NLAPSTATE, NMETRIC, NREPORT, REPORT_INDEX, ClConeSensor, ClEstimator, ClLatency, ClSensors, ConeMaps, ParamBlock, Spline, check,
                    check_blocking, check_laps, lib)
 from .ltvmpc import LtvBatch, dims
 from .corridor import check_corridor
@@ -230,6 +230,108 @@ def check_sensors(sensors, latency, nx, B):
     return sensors
 
 
+class ConeSensor:
+    """The cone sensor of a closed loop and the cone rows of its filter, validated here without a library call.  left,
+    right: (K_l, 2) / (K_r, 2) positions of the cones that stand on the track (the truth the sensor reads), at most CONES_MAX per side.
+    r_min, r_max (m), fov (rad, the whole opening angle, centred on the heading): the view.  sigma = (range m, bearing rad): the noise,
+    finite and >= 0.  p_detect: the probability that a cone in view is detected.  k_max: observations per car and period, the nearest
+    ones, 1 .. CONE_OBS_MAX.  seed, id0: the draws of car b and cone g depend on (seed, id0 + b, period, g) only.  map_left, map_right:
+    the map the filter reads, None = the truth; (K, 2) for the batch or (B, K, 2) one per car (cone_draws: a Monte-Carlo over the
+    mapping error), with the truth's counts.  r = (range, bearing) variances of the filter's cone rows, each >= 0 or +inf ("this channel is
+    off": r = (inf, v) is a bearing-only camera); None = sigma^2."""
+
+    def __init__(self, left, right, r_max=15.0, r_min=0.5, fov=2 * np.pi / 3, sigma=(0.05, 0.01), p_detect=1.0, k_max=16, seed=0, id0=0,
+                 map_left=None, map_right=None, r=None):
+        def integer(v, name):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError("%s must be an integer" % name)
+            return int(v)
+
+        def number(v, name):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("%s must be a number" % name)
+            return float(v)
+
+        def side(v, name, ndims):
+            try:
+                a = np.array(v, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("%s must be an array of numbers" % name)
+            if a.ndim == ndims[0] and a.size == 0:
+                a = a.reshape((0, 2))
+            if a.ndim not in ndims or a.shape[-1] != 2:
+                raise ValueError("%s must be (K, 2)%s, got %s" % (name, " or (B, K, 2)" if len(ndims) > 1 else "", a.shape))
+            if a.shape[-2] > CONES_MAX:
+                raise ValueError("%s: at most %d cones per side" % (name, CONES_MAX))
+            return np.ascontiguousarray(a)
+        self.left, self.right = side(left, "left", (2,)), side(right, "right", (2,))
+        if self.left.shape[0] + self.right.shape[0] == 0:
+            raise ValueError("a cone map with no cones")
+        self.r_min, self.r_max, self.fov = number(r_min, "r_min"), number(r_max, "r_max"), number(fov, "fov")
+        if not (self.r_max < float("inf")) or not (self.r_min > 0) or not (self.r_min < self.r_max):
+            raise ValueError("r_min must be > 0 and below a finite r_max")
+        if not (0 < self.fov <= 2 * np.pi):
+            raise ValueError("fov must be in (0, 2 pi]")
+        try:
+            sg = np.array(sigma, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("sigma must be two numbers")
+        if sg.shape != (2,) or not np.isfinite(sg).all() or (sg < 0).any():
+            raise ValueError("sigma must be (range, bearing), finite and >= 0")
+        self.sigma = sg
+        self.p_detect = number(p_detect, "p_detect")
+        if not (0 <= self.p_detect <= 1):
+            raise ValueError("p_detect must be in [0, 1]")
+        self.k_max = integer(k_max, "k_max")
+        if not 1 <= self.k_max <= CONE_OBS_MAX:
+            raise ValueError("k_max must be 1 .. %d" % CONE_OBS_MAX)
+        self.seed = integer(seed, "seed")
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2^64)")
+        self.id0 = integer(id0, "id0")
+        if not 0 <= self.id0 < 2 ** 63:
+            raise ValueError("id0 must be >= 0 (and below 2^63)")
+        if (map_left is None) != (map_right is None):
+            raise ValueError("map_left and map_right are given together")
+        if map_left is None:
+            self.map_left, self.map_right = self.left, self.right
+        else:
+            self.map_left, self.map_right = side(map_left, "map_left", (2, 3)), side(map_right, "map_right", (2, 3))
+            if self.map_left.ndim != self.map_right.ndim or (self.map_left.ndim == 3 and self.map_left.shape[0] != self.map_right.shape[0]):
+                raise ValueError("map_left and map_right are both shared or both per car")
+            if self.map_left.shape[-2] != self.left.shape[0] or self.map_right.shape[-2] != self.right.shape[0]:
+                raise ValueError("the map must have the truth's counts (%d left, %d right), got %d and %d"
+                                 % (self.left.shape[0], self.right.shape[0], self.map_left.shape[-2], self.map_right.shape[-2]))
+        if r is None:
+            self.r = sg ** 2
+        else:
+            try:
+                self.r = np.array(r, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("r must be two numbers")
+            if self.r.shape != (2,) or np.isnan(self.r).any() or (self.r < 0).any():
+                raise ValueError("r must be (range, bearing), each >= 0 (+inf: the channel is off)")
+
+    def check_batch(self, B):
+        """A per-car map against the batch of the loop that takes it."""
+        if self.map_left.ndim == 3 and self.map_left.shape[0] != B:
+            raise ValueError("a per-car map must be (B = %d, K, 2), got %s" % (B, self.map_left.shape))
+
+
+def check_cones(cones, sensors, estimator, B):
+    """Validates ClosedLoop's cones argument (no library call): None, or a ConeSensor next to sensors and an estimator."""
+    if cones is None:
+        return None
+    if not isinstance(cones, ConeSensor):
+        raise ValueError("cones must be None or a ConeSensor")
+    if sensors is None:
+        raise ValueError("cones needs sensors=CartesianSensors(...): the filter with the cone rows reads the Cartesian measurement")
+    if estimator is None:
+        raise ValueError("cones needs estimator=Estimator(...): the cone observations are rows of the filter")
+    cones.check_batch(B)
+    return cones
+
+
 class Nmpc:
     """The batched SQP of the nonlinear MPC step as the controller of a closed loop (main.m:118-160, MODE =
     "MS-NMPC"), validated here without a library call.  sweeps: the sweep cap of a period (max_sweeps; 1 is a real-time iteration).
@@ -325,7 +427,7 @@ class ClosedLoop:
 
     def __init__(self, model, N, dt, track, cart0, target_vel=20.0, device="cuda:0", options=None, integrator=-1, warm_start=False, launch_hint=True,
                  params=None, plant_params=None, blocking=None, reference=None, metrics=False, slack_tol=1e-6, corridor=None, laps=1,
-                 latency=None, estimator=None, controller=None, sensors=None):
+                 latency=None, estimator=None, controller=None, sensors=None, cones=None):
         """params: parameter block(s) of the controller ((32,) or (B, 32), as for LtvBatch); plant_params: the cars' own block(s),
         None = the same as params (both None: the reference's constants compiled into the kernels).  blocking: block lengths of the
         controller's held inputs (LtvBatch); the plan the loop carries stays the expanded one, (B, N, 2).  reference: None = the live
@@ -367,7 +469,15 @@ class ClosedLoop:
         layout, None = sigma^2; first prior, re-initialisation and re-basing from x_proj, so laps > 1 needs no measured arc length);
         without one the loop drives on x_proj.  The latency's prediction then runs on that state if it compensates, x_ref is
         regenerated and the controller solves from it.  self.x0 stays the true state (the gate and the metrics read it).  Not
-        together with a Latency that has a sigma (ValueError: two noise sources)."""
+        together with a Latency that has a sigma (ValueError: two noise sources).
+        cones: None or a ConeSensor, next to sensors and an estimator (ValueError without either).  None launches what
+        the loop launches without the argument.  Otherwise step() runs pre, lap gate, sense, the cone sensor
+        (fsaempc_cl_cone_sense_batch_device on the true pose: self.cone_n, self.cone_seen (B,), self.cone_id (B, k_max), self.cone_z
+        (B, k_max, 2)) and the filter with the cone rows in the place of the Cartesian filter
+        (fsaempc_cl_estimate_cones_batch_device: self.cone_innov (B, k_max, 2), self.est_rows (B,) the rows applied, next to the
+        estimator's attributes), then whatever followed before.  A GPS outage is Estimator(r=[inf, inf, inf, ...]): the pose rows
+        are off and the cones carry the pose; the first prior, the re-initialisation state and the re-basing still read x_proj, the
+        projection of the (noisy) pose measurement."""
         self.controller = check_controller(controller, corridor, blocking, N, warm_start)   # (before the library is touched)
         if not (float(slack_tol) >= 0):
             raise ValueError("slack_tol must be >= 0")
@@ -384,6 +494,7 @@ class ClosedLoop:
         self.latency = check_latency(latency, 5 if model == 0 else 7, np.asarray(cart0).size // 7)   # (likewise)
         self.sensors = check_sensors(sensors, self.latency, 5 if model == 0 else 7, np.asarray(cart0).size // 7)   # (likewise)
         self._est_arrays = check_estimator(estimator, latency, 5 if model == 0 else 7, np.asarray(cart0).size // 7, self.laps, self.sensors)   # (likewise)
+        self.cones = check_cones(cones, self.sensors, estimator, np.asarray(cart0).size // 7)   # (likewise)
         self.estimator = estimator
         if self.latency is not None and not self.latency.engaged:
             self.latency = None
@@ -461,6 +572,25 @@ class ClosedLoop:
             if self.estimator is None and self.latency is None:
                 self._s0_mpc = torch.empty(self.B, dtype=torch.float64, device=self.device)
                 self.x0_mpc = self.x_proj
+        self.cone_n = self.cone_seen = self.cone_id = self.cone_z = self.cone_innov = self.est_rows = None
+        if self.cones is not None:
+            cs = self.cones
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+            self._cone_arrays = [dev(a) for a in (cs.left, cs.right)]
+            self._cone_arrays += self._cone_arrays if cs.map_left is cs.left else [dev(a) for a in (cs.map_left, cs.map_right)]
+            tl, tr_, ml, mr = self._cone_arrays
+            self._cone_truth = ConeMaps(ptr(tl), ptr(tr_), cs.left.shape[0], cs.right.shape[0], 0)
+            self._cone_map = ConeMaps(ptr(ml), ptr(mr), cs.left.shape[0], cs.right.shape[0], 1 if cs.map_left.ndim == 3 else 0)
+            self._cone_sensor = ClConeSensor(C.pointer(self._cone_truth), cs.r_min, cs.r_max, cs.fov, float(cs.sigma[0]), float(cs.sigma[1]), cs.p_detect,
+                                             cs.k_max, cs.seed, cs.id0)
+            self._cone_r = (C.c_double * 2)(float(cs.r[0]), float(cs.r[1]))
+            self.cone_n = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+            self.cone_seen = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+            self.cone_id = torch.full((self.B, cs.k_max), -1, dtype=torch.int32, device=self.device)
+            self.cone_z = torch.zeros((self.B, cs.k_max, 2), dtype=torch.float64, device=self.device)
+            self.cone_innov = torch.zeros((self.B, cs.k_max, 2), dtype=torch.float64, device=self.device)
+            self.est_rows = torch.zeros(self.B, dtype=torch.int32, device=self.device)
         self.metrics = torch.zeros((self.B, NMETRIC), dtype=torch.float64, device=self.device) if metrics else None
         self.lap_state = self.lap_times = self.lap_records = None   # laps == 1: nothing is allocated unless lap_gate() is called
         if self.laps > 1:
@@ -596,6 +726,13 @@ class ClosedLoop:
                                                   P(self.finished), P(self.y_meas), P(self.x_proj), P(self.proj_lost), self._stream(stream)),
               "fsaempc_cl_sense_batch_device")
 
+    def cone_sense(self, stream=None):
+        """The cone observations of this period from the true pose (fsaempc_cl_cone_sense_batch_device)."""
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(lib().fsaempc_cl_cone_sense_batch_device(self.B, C.byref(self._cone_sensor), self.steps, P(self.cart), P(self.finished), P(self.cone_n),
+                                                       P(self.cone_seen), P(self.cone_id), P(self.cone_z), self._stream(stream)),
+              "fsaempc_cl_cone_sense_batch_device")
+
     def sensed_state(self, stream=None):
         """Measurement, projection, filter (with an estimator) and prediction (with a compensating latency) of this period
         (DESIGN.md 6s), then x_ref regenerated from the state the solve reads, which is returned."""
@@ -603,13 +740,24 @@ class ClosedLoop:
         self._fill_history()
         self.sense(stream)
         state = self.x_proj
-        if self.estimator is not None:
+        if self.cones is not None:
+            self.cone_sense(stream)
+            check(lib().fsaempc_cl_estimate_cones_batch_device(C.byref(self.mpc.desc), C.byref(self.mpc.sp),
+                                                               self.mpc.params.ref() if self.mpc.params is not None else None, C.byref(self._est),
+                                                               P(self.y_meas), P(self.x_proj), P(self.prev_input()), 2 * self.N, P(self.finished),
+                                                               P(self.est_x), P(self.est_P), P(self.est_count), P(self.x0_est), P(self.est_innov),
+                                                               P(self.est_nis), None, None, None, C.byref(self._cone_map), self.cones.k_max, self._cone_r,
+                                                               P(self.cone_n), P(self.cone_id), P(self.cone_z), P(self.cone_innov), P(self.est_rows), None,
+                                                               self._stream(stream)),
+                  "fsaempc_cl_estimate_cones_batch_device")
+        elif self.estimator is not None:
             check(lib().fsaempc_cl_estimate_cart_batch_device(C.byref(self.mpc.desc), C.byref(self.mpc.sp),
                                                               self.mpc.params.ref() if self.mpc.params is not None else None, C.byref(self._est),
                                                               P(self.y_meas), P(self.x_proj), P(self.prev_input()), 2 * self.N, P(self.finished),
                                                               P(self.est_x), P(self.est_P), P(self.est_count), P(self.x0_est), P(self.est_innov),
                                                               P(self.est_nis), None, None, None, self._stream(stream)),
                   "fsaempc_cl_estimate_cart_batch_device")
+        if self.estimator is not None:
             state = self.x0_est
             if self.latency is not None and self.latency.compensate:
                 self._observe_call(self._lat_pred, self.x0_est, self._obs_scratch, self.x0_mpc, stream)
@@ -720,11 +868,12 @@ def monte_carlo_carts(track, B, seed, lap=False):
 
 
 def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cuda:0", warm_start=False, launch_hint=True, params=None,
-                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1, latency=None, estimator=None, controller=None, sensors=None):
+                plant_params=None, blocking=None, reference=None, metrics=False, corridor=None, laps=1, latency=None, estimator=None, controller=None, sensors=None,
+                cones=None):
     """Closed-loop Monte-Carlo: B cars from random initial states, `steps` receding-horizon steps, device-resident loop.
     reference: None (the live ramp) or a Plan the cars track (ClosedLoop).  metrics: ClosedLoop(metrics=True); cl.report() afterwards.
     corridor: None or a Corridor (ClosedLoop).  laps: ClosedLoop(laps=...); cl.lap_times afterwards.  latency: None or a Latency (ClosedLoop).  estimator: None or an Estimator (ClosedLoop).
-    sensors: None or a CartesianSensors (ClosedLoop).
+    sensors: None or a CartesianSensors (ClosedLoop).  cones: None or a ConeSensor (ClosedLoop).
     controller: None (the LTV-MPC step) or an Nmpc (ClosedLoop; the tallies are then the take-over's exit flags and the SQP's QP iterations).
     Returns the ClosedLoop and the per-step tallies (exit flags, iteration counts, driving mask), read back once at the end --
     the reference reports exactly this tally as "abnormal exits %" (main.m:209,222)."""
@@ -732,7 +881,7 @@ def monte_carlo(model, N, track, B, steps, seed=20190, options=None, device="cud
     cart0, s_init = monte_carlo_carts(track, B, seed)
     cl = ClosedLoop(model, N, 0.05, track, cart0, options=options, device=device, warm_start=warm_start, launch_hint=launch_hint,
                     params=params, plant_params=plant_params, blocking=blocking, reference=reference, metrics=metrics, corridor=corridor, laps=laps,
-                    latency=latency, estimator=estimator, controller=controller, sensors=sensors)
+                    latency=latency, estimator=estimator, controller=controller, sensors=sensors, cones=cones)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]        # start the closest-point search near the car
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]   # and the first linearisation at its speed
     flags = torch.zeros((steps, B), dtype=torch.int32, device=cl.device)

@@ -7,6 +7,7 @@
 #include "cl_latency.h"
 #include "cl_estimator.h"
 #include "cl_sensors.h"
+#include "cl_cone_loc.h"
 #include "cl_nmpc.h"
 using namespace capi;
 
@@ -277,39 +278,140 @@ int fsaempc_cl_sense_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_sp
   return launched(cl_sense_launch(P, (hipStream_t)stream), "cl_sense_launch");
 }
 
-int fsaempc_cl_estimate_cart_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
-                                          const fsaempc_cl_estimator* est, const double* y, const double* x_proj, const double* u_prev,
-                                          long long u_stride, const int* finished, double* est_x, double* est_P, int* est_count, double* x0_est,
-                                          double* innov, double* nis, double* F_out, double* x_prior, double* H_out, void* stream) {
+// What the two filters on the Cartesian measurement share: the checks of their common arguments, the kernel's parameters and the byte
+// ranges of what they write and read (the cone filter adds its own to both lists before the overlap check).
+namespace {
+struct CartArgs {
+  const double* y; const double* x_proj; const double* u_prev; long long u_stride; const int* finished;
+  double* est_x; double* est_P; int* est_count; double* x0_est; double* innov; double* nis; double* F_out; double* x_prior; double* H_out;
+};
+constexpr int CL_CART_OUT = 9, CL_CART_IN = 7;
+}
+static int cl_cart_check(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_cl_estimator* est, const CartArgs& a,
+                         ClEstimateCartParams* P, ByteRange* out, ByteRange* in) {
   if (int rc = ltv_check(desc, sp)) return rc;
   if (!est) return fail(FSAEMPC_ERR_ARG, "null argument (est)");
   if (!est->q) return fail(FSAEMPC_ERR_ARG, "null argument (est->q)");
   if (!est->r) return fail(FSAEMPC_ERR_ARG, "null argument (est->r)");
   if (!est->p0) return fail(FSAEMPC_ERR_ARG, "null argument (est->p0)");
   if (!(est->L >= 0 && est->L < INFINITY)) return fail(FSAEMPC_ERR_ARG, "L must be finite and >= 0");
-  if (u_stride < 2) return fail(FSAEMPC_ERR_ARG, "u_stride must be >= 2");
-  const struct { const char* name; const void* p; } need[] = {{"y", y}, {"x_proj", x_proj}, {"u_prev", u_prev}, {"est_x", est_x}, {"est_P", est_P},
-                                                               {"est_count", est_count}, {"x0_est", x0_est}, {"innov", innov}, {"nis", nis}};
+  if (a.u_stride < 2) return fail(FSAEMPC_ERR_ARG, "u_stride must be >= 2");
+  const struct { const char* name; const void* p; } need[] = {{"y", a.y}, {"x_proj", a.x_proj}, {"u_prev", a.u_prev}, {"est_x", a.est_x},
+                                                               {"est_P", a.est_P}, {"est_count", a.est_count}, {"x0_est", a.x0_est},
+                                                               {"innov", a.innov}, {"nis", a.nis}};
   for (const auto& n : need)
     if (!n.p) return fail(FSAEMPC_ERR_ARG, "null argument (%s)", n.name);
   const size_t B = (size_t)desc->batch, nx = (size_t)fsaempc_ltv_nx(desc->model), d = sizeof(double);
-  const ByteRange out[] = {{"est_x", est_x, B * nx * d}, {"est_P", est_P, B * nx * nx * d}, {"est_count", est_count, B * 2 * sizeof(int)},
-                           {"x0_est", x0_est, B * nx * d}, {"innov", innov, B * nx * d}, {"nis", nis, B * d},
-                           {"F_out", F_out, B * nx * nx * d}, {"x_prior", x_prior, B * nx * d}, {"H_out", H_out, B * nx * nx * d}};
-  const ByteRange in[] = {{"y", y, B * nx * d}, {"x_proj", x_proj, B * nx * d},
-                          {"u_prev", u_prev, B ? ((B - 1) * (size_t)u_stride + 2) * d : 0}, {"finished", finished, B * sizeof(int)},
-                          {"q", est->q, (est->q_per_instance ? B : 1) * nx * d}, {"r", est->r, (est->r_per_instance ? B : 1) * nx * d},
-                          {"p0", est->p0, nx * d}};
-  if (int rc = ranges_check(out, (int)(sizeof(out) / sizeof(out[0])), in, (int)(sizeof(in) / sizeof(in[0])))) return rc;
-  if (desc->batch == 0) return 0;
+  const ByteRange o[CL_CART_OUT] = {{"est_x", a.est_x, B * nx * d}, {"est_P", a.est_P, B * nx * nx * d}, {"est_count", a.est_count, B * 2 * sizeof(int)},
+                                    {"x0_est", a.x0_est, B * nx * d}, {"innov", a.innov, B * nx * d}, {"nis", a.nis, B * d},
+                                    {"F_out", a.F_out, B * nx * nx * d}, {"x_prior", a.x_prior, B * nx * d}, {"H_out", a.H_out, B * nx * nx * d}};
+  const ByteRange i[CL_CART_IN] = {{"y", a.y, B * nx * d}, {"x_proj", a.x_proj, B * nx * d},
+                                   {"u_prev", a.u_prev, B ? ((B - 1) * (size_t)a.u_stride + 2) * d : 0}, {"finished", a.finished, B * sizeof(int)},
+                                   {"q", est->q, (est->q_per_instance ? B : 1) * nx * d}, {"r", est->r, (est->r_per_instance ? B : 1) * nx * d},
+                                   {"p0", est->p0, nx * d}};
+  for (int k = 0; k < CL_CART_OUT; ++k) out[k] = o[k];
+  for (int k = 0; k < CL_CART_IN; ++k) in[k] = i[k];
+  P->nx = (int)nx; P->batch = desc->batch; P->integ = ltv_integ(desc); P->q_per_instance = est->q_per_instance ? 1 : 0;
+  P->r_per_instance = est->r_per_instance ? 1 : 0; P->dt = desc->dt; P->L = est->L;
+  set_spline(P, sp);
+  P->q = est->q; P->r = est->r; P->p0 = est->p0; P->y = a.y; P->x_proj = a.x_proj; P->u_prev = a.u_prev; P->u_stride = a.u_stride;
+  P->finished = a.finished; P->est_x = a.est_x; P->est_P = a.est_P; P->est_count = a.est_count; P->x0_est = a.x0_est; P->innov = a.innov;
+  P->nis = a.nis; P->F_out = a.F_out; P->x_prior = a.x_prior; P->H_out = a.H_out;
+  return 0;
+}
+
+int fsaempc_cl_estimate_cart_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                          const fsaempc_cl_estimator* est, const double* y, const double* x_proj, const double* u_prev,
+                                          long long u_stride, const int* finished, double* est_x, double* est_P, int* est_count, double* x0_est,
+                                          double* innov, double* nis, double* F_out, double* x_prior, double* H_out, void* stream) {
   ClEstimateCartParams P;
-  P.nx = (int)nx; P.batch = desc->batch; P.integ = ltv_integ(desc); P.q_per_instance = est->q_per_instance ? 1 : 0;
-  P.r_per_instance = est->r_per_instance ? 1 : 0; P.dt = desc->dt; P.L = est->L;
-  set_spline(&P, sp);
-  P.q = est->q; P.r = est->r; P.p0 = est->p0; P.y = y; P.x_proj = x_proj; P.u_prev = u_prev; P.u_stride = u_stride; P.finished = finished;
-  P.est_x = est_x; P.est_P = est_P; P.est_count = est_count; P.x0_est = x0_est; P.innov = innov; P.nis = nis; P.F_out = F_out; P.x_prior = x_prior;
-  P.H_out = H_out;
+  ByteRange out[CL_CART_OUT], in[CL_CART_IN];
+  const CartArgs a{y, x_proj, u_prev, u_stride, finished, est_x, est_P, est_count, x0_est, innov, nis, F_out, x_prior, H_out};
+  if (int rc = cl_cart_check(desc, sp, est, a, &P, out, in)) return rc;
+  if (int rc = ranges_check(out, CL_CART_OUT, in, CL_CART_IN)) return rc;
+  if (desc->batch == 0) return 0;
   return launched(cl_estimate_cart_launch(P, (hipStream_t)stream, par_values(par), par_stride(par)), "cl_estimate_cart_launch");
+}
+
+/* ---- closed loop: cone-based localisation ---- */
+// a cone map as both entries read it: `who` names the argument in the message
+static int cl_cone_map_check(const fsaempc_cones* m, const char* who, ClConeMap* out) {
+  if (!m) return fail(FSAEMPC_ERR_ARG, "null argument (%s)", who);
+  if (m->n_left < 0 || m->n_right < 0) return fail(FSAEMPC_ERR_ARG, "%s: a negative cone count", who);
+  if (m->n_left > FSAEMPC_CONES_MAX || m->n_right > FSAEMPC_CONES_MAX) return fail(FSAEMPC_ERR_DIM, "%s: more than FSAEMPC_CONES_MAX cones on a side", who);
+  if (m->n_left + m->n_right == 0) return fail(FSAEMPC_ERR_ARG, "%s: a map with no cones", who);
+  if ((m->n_left > 0 && !m->left) || (m->n_right > 0 && !m->right)) return fail(FSAEMPC_ERR_ARG, "null argument (%s: a side with cones and no pointer)", who);
+  out->left = m->left; out->right = m->right; out->n_left = m->n_left; out->n_right = m->n_right; out->per_car = m->per_corridor ? 1 : 0;
+  return 0;
+}
+
+static int cl_k_max_check(int k_max) {
+  return k_max >= 1 && k_max <= FSAEMPC_CONE_OBS_MAX ? 0 : fail(FSAEMPC_ERR_ARG, "k_max must be 1 .. FSAEMPC_CONE_OBS_MAX");
+}
+
+int fsaempc_cl_cone_sense_batch_device(int batch, const fsaempc_cl_cone_sensor* sensor, long long step, const double* cart, const int* finished,
+                                       int* cone_n, int* cone_seen, int* cone_id, double* cone_z, void* stream) {
+  if (batch < 0) return fail(FSAEMPC_ERR_ARG, "bad dimensions (batch)");
+  if (!sensor) return fail(FSAEMPC_ERR_ARG, "null argument (sensor)");
+  ClConeSenseParams P;
+  if (int rc = cl_cone_map_check(sensor->truth, "sensor->truth", &P.truth)) return rc;
+  if (int rc = cl_k_max_check(sensor->k_max)) return rc;
+  if (!(sensor->r_max < INFINITY) || !(sensor->r_min > 0) || !(sensor->r_min < sensor->r_max))
+    return fail(FSAEMPC_ERR_ARG, "r_min must be > 0 and below a finite r_max");
+  if (!(sensor->fov > 0 && sensor->fov <= 2 * M_PI)) return fail(FSAEMPC_ERR_ARG, "fov must be in (0, 2 pi]");
+  if (!(sensor->sigma_range >= 0)) return fail(FSAEMPC_ERR_ARG, "sigma_range must be >= 0");
+  if (!(sensor->sigma_bearing >= 0)) return fail(FSAEMPC_ERR_ARG, "sigma_bearing must be >= 0");
+  if (!(sensor->p_detect >= 0 && sensor->p_detect <= 1)) return fail(FSAEMPC_ERR_ARG, "p_detect must be in [0, 1]");
+  if (int rc = cl_draw_check(sensor->id0, step)) return rc;
+  const struct { const char* name; const void* p; } need[] = {{"cart", cart}, {"cone_n", cone_n}, {"cone_seen", cone_seen}, {"cone_id", cone_id},
+                                                               {"cone_z", cone_z}};
+  for (const auto& n : need)
+    if (!n.p) return fail(FSAEMPC_ERR_ARG, "null argument (%s)", n.name);
+  const size_t B = (size_t)batch, K = (size_t)sensor->k_max, d = sizeof(double), maps = P.truth.per_car ? B : 1;
+  const ByteRange out[] = {{"cone_n", cone_n, B * sizeof(int)}, {"cone_seen", cone_seen, B * sizeof(int)}, {"cone_id", cone_id, B * K * sizeof(int)},
+                           {"cone_z", cone_z, B * K * 2 * d}};
+  const ByteRange in[] = {{"cart", cart, B * 7 * d}, {"finished", finished, B * sizeof(int)},
+                          {"left", P.truth.left, maps * (size_t)P.truth.n_left * 2 * d}, {"right", P.truth.right, maps * (size_t)P.truth.n_right * 2 * d}};
+  if (int rc = ranges_check(out, (int)(sizeof(out) / sizeof(out[0])), in, (int)(sizeof(in) / sizeof(in[0])))) return rc;
+  if (batch == 0) return 0;
+  P.batch = batch; P.k_max = sensor->k_max; P.r_min = sensor->r_min; P.r_max = sensor->r_max; P.fov = sensor->fov;
+  P.sigma_rho = sensor->sigma_range; P.sigma_beta = sensor->sigma_bearing; P.p_detect = sensor->p_detect;
+  P.seed = sensor->seed; P.id0 = (unsigned long long)sensor->id0; P.step = (unsigned long long)step;
+  P.cart = cart; P.finished = finished; P.cone_n = cone_n; P.cone_seen = cone_seen; P.cone_id = cone_id; P.cone_z = cone_z;
+  return launched(cl_cone_sense_launch(P, (hipStream_t)stream), "cl_cone_sense_launch");
+}
+
+int fsaempc_cl_estimate_cones_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                           const fsaempc_cl_estimator* est, const double* y, const double* x_proj, const double* u_prev,
+                                           long long u_stride, const int* finished, double* est_x, double* est_P, int* est_count, double* x0_est,
+                                           double* innov, double* nis, double* F_out, double* x_prior, double* H_out, const fsaempc_cones* map,
+                                           int k_max, const double* r_cone, const int* cone_n, const int* cone_id, const double* cone_z,
+                                           double* cone_innov, int* rows_used, double* G_out, void* stream) {
+  ClEstimateConesParams P;
+  constexpr int N_OUT = CL_CART_OUT + 3, N_IN = CL_CART_IN + 5;
+  ByteRange out[N_OUT], in[N_IN];
+  const CartArgs a{y, x_proj, u_prev, u_stride, finished, est_x, est_P, est_count, x0_est, innov, nis, F_out, x_prior, H_out};
+  if (int rc = cl_cart_check(desc, sp, est, a, &P.E, out, in)) return rc;
+  if (int rc = cl_cone_map_check(map, "map", &P.map)) return rc;
+  if (int rc = cl_k_max_check(k_max)) return rc;
+  const struct { const char* name; const void* p; } need[] = {{"r_cone", r_cone}, {"cone_n", cone_n}, {"cone_id", cone_id}, {"cone_z", cone_z},
+                                                               {"cone_innov", cone_innov}, {"rows_used", rows_used}};
+  for (const auto& n : need)
+    if (!n.p) return fail(FSAEMPC_ERR_ARG, "null argument (%s)", n.name);
+  const size_t B = (size_t)desc->batch, K = (size_t)k_max, d = sizeof(double), maps = P.map.per_car ? B : 1;
+  out[CL_CART_OUT] = {"cone_innov", cone_innov, B * K * 2 * d};
+  out[CL_CART_OUT + 1] = {"rows_used", rows_used, B * sizeof(int)};
+  out[CL_CART_OUT + 2] = {"G_out", G_out, B * K * 6 * d};
+  in[CL_CART_IN] = {"cone_n", cone_n, B * sizeof(int)};
+  in[CL_CART_IN + 1] = {"cone_id", cone_id, B * K * sizeof(int)};
+  in[CL_CART_IN + 2] = {"cone_z", cone_z, B * K * 2 * d};
+  in[CL_CART_IN + 3] = {"left", P.map.left, maps * (size_t)P.map.n_left * 2 * d};
+  in[CL_CART_IN + 4] = {"right", P.map.right, maps * (size_t)P.map.n_right * 2 * d};
+  if (int rc = ranges_check(out, N_OUT, in, N_IN)) return rc;
+  if (desc->batch == 0) return 0;
+  P.k_max = k_max; P.r_cone[0] = r_cone[0]; P.r_cone[1] = r_cone[1];
+  P.cone_n = cone_n; P.cone_id = cone_id; P.cone_z = cone_z; P.cone_innov = cone_innov; P.rows_used = rows_used; P.G_out = G_out;
+  return launched(cl_estimate_cones_launch(P, (hipStream_t)stream, par_values(par), par_stride(par)), "cl_estimate_cones_launch");
 }
 
 /* ---- closed loop: the batched SQP as the controller ---- */

@@ -1120,6 +1120,80 @@ int fsaempc_cl_estimate_cart_batch_device(const fsaempc_ltv_desc* desc, const fs
                                           double* F_out /* optional, batch x nx x nx */, double* x_prior /* optional, batch x nx */,
                                           double* H_out /* optional, batch x nx x nx */, void* stream);
 
+/* ---- closed loop: cone-based localisation ----------------------------------------------
+ * The pose inferred from detections of the track's cones against a known map, as a lidar or a camera gives it: a cone sensor, and the
+ * filter above with the rows of its observations behind the car's own.  Opt-in like the entries above.  A cone map is an
+ * fsaempc_cones with at most FSAEMPC_CONES_MAX cones per side (per_corridor = 1: one map per car, car-major); cones are indexed
+ * g = 0 .. n_left - 1 on the left side and n_left .. n_left + n_right - 1 on the right.  Data association is known: an observation
+ * carries the index of its cone.
+ *
+ * fsaempc_cl_cone_sense_batch_device: one call per MPC period next to fsaempc_cl_sense_batch_device, on the same stream.  One
+ * wavefront per car.  With (X, Y, psi) = cart[b][0 .. 2] and cone g of the truth map at (cx, cy):
+ *   observation   dx = cx - X, dy = cy - Y, rho = sqrt(dx dx + dy dy), beta = angdiff(psi, atan2(dy, dx)) (MATLAB's angdiff: the bearing
+ *                 in the car's frame, wrapped to [-pi, pi]).  The cone is in view iff r_min <= rho <= r_max and |beta| <= fov / 2.
+ *   draws         the words (w0, w1, w2, w3) of the generator of fsaempc_cl_observe_batch_device with the counter (step, 2 + g, id lo,
+ *                 id hi), id = id0 + b (calls 0 and 1 of that layout are the state draws: cone draws never collide with them under one
+ *                 seed), and the normals (z0, z1) of (w0, w1).  The cone is detected iff (w2 + 0.5) 2^-32 < p_detect;
+ *                 rho_m = rho + sigma_range z0, beta_m = angdiff(0, beta + sigma_bearing z1) (a sigma of 0 copies).  A cone's draw
+ *                 depends on the seed, the car's id, the period and the cone's index only.
+ *   selection     of the cones in view and detected (cone_seen[b] counts them) the min(cone_seen, k_max) smallest by the key
+ *                 (rho, g) -- the true range, ties broken by the index -- in that order: cone_n[b] their number, cone_id[b][k] the
+ *                 index (-1 past the count), cone_z[b][k] = (rho_m, beta_m) (0 past the count).
+ *   finished      finished[b] != 0: cone_n = cone_seen = 0, every cone_id -1, every cone_z 0.
+ * No atomics: the result does not depend on the batch or the launch geometry, bit for bit.
+ * FSAEMPC_ERR_ARG before any launch, with the argument named: sensor, sensor->truth, cart, cone_n, cone_seen, cone_id or cone_z NULL; a
+ * side's pointer NULL with a count > 0; batch < 0; k_max outside 1 .. FSAEMPC_CONE_OBS_MAX; r_min not > 0 or not < a finite r_max; fov
+ * outside (0, 2 pi]; a negative or NaN sigma; p_detect outside [0, 1]; id0 < 0; step < 0 or >= 2^32; a negative count or a map with
+ * no cones; an output that overlaps another output or an input.  FSAEMPC_ERR_DIM: more than FSAEMPC_CONES_MAX cones on a side.
+ * batch == 0 succeeds without a launch. */
+#define FSAEMPC_CONE_OBS_MAX 16   /* observations per car and period */
+typedef struct {
+  const fsaempc_cones* truth;   /* where the cones are */
+  double r_min, r_max;          /* m */
+  double fov;                   /* rad, the whole opening angle, centred on the heading */
+  double sigma_range, sigma_bearing;
+  double p_detect;
+  int k_max;
+  unsigned long long seed;
+  long long id0;                /* id of instance 0 (a shard's first global id) */
+} fsaempc_cl_cone_sensor;
+
+int fsaempc_cl_cone_sense_batch_device(int batch, const fsaempc_cl_cone_sensor* sensor, long long step, const double* cart /* batch x 7 */,
+                                       const int* finished /* optional */, int* cone_n /* batch */, int* cone_seen /* batch */,
+                                       int* cone_id /* batch x k_max */, double* cone_z /* batch x k_max x 2 */, void* stream);
+
+/* fsaempc_cl_estimate_cones_batch_device: fsaempc_cl_estimate_cart_batch_device with the cone rows.  Steps 1 .. 8 of that entry hold;
+ * the update (step 6, and its second run of step 7, then linearised at x_proj) processes the nx own rows as there and then, per
+ * observation k < cone_n[b] in order, its range row and its bearing row, linearised once at the same prior x-.  With
+ * (h0, h1, h2) = h(x-)[0 .. 2], Hr the rows and columns 0 .. 2 of H = dh/dx(x-), id = cone_id[b][k], (mx, my) cone id of `map` (which may
+ * differ from the truth the sensor read: same counts and indexing; per_corridor = 1: one map per car) and (rho_m, beta_m) = cone_z[b][k]:
+ *   dx = mx - h0, dy = my - h1, q2 = dx dx + dy dy, rho^ = sqrt(q2), beta^ = angdiff(h2, atan2(dy, dx)),
+ *   g_rho = (-dx / rho^, -dy / rho^, 0), g_beta = (dy / q2, -dx / q2, -1), G_i[c] = sum_k g_i[k] Hr[k][c] (k = 0, 1, 2 in this order; the
+ *   state columns >= 3 are zero), nu0_rho = rho_m - rho^, nu0_beta = angdiff(beta^, beta_m).
+ * A row with variance r (r_cone[0] for range, r_cone[1] for bearing, shared by the batch; +Inf switches the channel off):
+ *   nu = nu0 - sum_c G[c] (x[c] - x-[c]), c = P G', s = G c + r; applied iff 0 <= id < n_left + n_right, rho^ > 0, r is finite and
+ *   >= 0 and s > 0: x_a += c_a nu / s, P_ab -= (c_a c_b) / s (exactly symmetric).  A row that is not applied changes nothing and its
+ *   innovation is 0.  A non-finite cone_z of an applied row spoils the update, which step 7 answers.
+ * cone_innov[b][k] = the innovations of the two rows (0 for k >= cone_n[b]); rows_used[b] = the rows applied, own and cone rows; nis
+ * sums over all of them; G_out (optional) = the two composed rows of every observation of the applied update (0 where not applied).
+ * A finished car: cone_innov = 0, rows_used = 0, G_out = 0.  cone_n[b] is clamped to 0 .. k_max.  With cone_n = 0 everywhere, or both
+ * variances +Inf, every common output equals fsaempc_cl_estimate_cart_batch_device's bit for bit.
+ * FSAEMPC_ERR_ARG before any launch, with the argument named: what fsaempc_cl_estimate_cart_batch_device refuses; map, r_cone, cone_n,
+ * cone_id, cone_z, cone_innov or rows_used NULL; a side's pointer NULL with a count > 0; k_max outside 1 .. FSAEMPC_CONE_OBS_MAX; a
+ * negative count or a map with no cones; an output that overlaps another output or an input.  FSAEMPC_ERR_DIM: more than
+ * FSAEMPC_CONES_MAX cones on a side.  desc->batch == 0 succeeds without a launch. */
+int fsaempc_cl_estimate_cones_batch_device(const fsaempc_ltv_desc* desc, const fsaempc_spline* sp, const fsaempc_ltv_params* par,
+                                           const fsaempc_cl_estimator* est, const double* y /* batch x nx */, const double* x_proj /* batch x nx */,
+                                           const double* u_prev, long long u_stride /* doubles between cars */, const int* finished /* optional */,
+                                           double* est_x, double* est_P, int* est_count /* batch x 2, zeroed by the caller */,
+                                           double* x0_est, double* innov, double* nis /* batch */,
+                                           double* F_out /* optional, batch x nx x nx */, double* x_prior /* optional, batch x nx */,
+                                           double* H_out /* optional, batch x nx x nx */,
+                                           const fsaempc_cones* map, int k_max, const double* r_cone /* host, 2 */,
+                                           const int* cone_n /* batch */, const int* cone_id /* batch x k_max */,
+                                           const double* cone_z /* batch x k_max x 2 */, double* cone_innov /* batch x k_max x 2 */,
+                                           int* rows_used /* batch */, double* G_out /* optional, batch x k_max x 2 x 3 */, void* stream);
+
 /* ---- closed loop: the batched SQP (nonlinear MPC) as the controller (main.m:118-160, MODE = "MS-NMPC") ----------
  * Between the pre-step (and lap gate, observation, estimator) and the plant, in place of the LTV step and
  * fsaempc_cl_accept_batch_device: shift -> fsaempc_sqp_batch_device_m -> accept.  Both entries return FSAEMPC_ERR_ARG, with a text

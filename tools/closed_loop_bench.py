@@ -32,6 +32,11 @@ driving cars' periods.
 [X, Y, psi, v, delta] (kinematic) or [X, Y, psi, x_d, y_d, theta_d, delta] (dynamic) with these standard deviations; without --estimator the
 loop drives on the projection of the measurement, with it the filter reads the measurement through h(x) (--meas-var is then in the
 sensor layout and defaults to the squares of --sensors).  Excludes --noise.  Echoed as "sensors", with the projections that lost the track.
+--cone-sensor r_max,fov_deg,s_rho,s_beta[,p_detect] [--cone-k K] [--cone-map FILE.npz] [--unmeasured-pose]: cone-based localisation
+(fsaempc.ConeSensor) next to --sensors and --estimator: every period each car observes range and bearing of its K nearest
+detected cones within r_max m and fov_deg degrees, and the filter processes them as rows behind its own; the cone draws share
+--sensor-seed.  --unmeasured-pose switches the rows of X, Y and psi off (a GPS outage).  Echoed as "cone_sensor", with the mean numbers
+of rows applied, cones kept and cones seen per car and period.
 --nmpc K [--nmpc-trials T] [--nmpc-timing]: the batched SQP of the nonlinear problem as the controller (fsaempc.Nmpc), K sweeps
 per period, warm-started from the previous period's plan shifted by one stage.  "value" then counts the periods of driving cars that
 ended with status 0 or 1; "nmpc" joins the JSON line: the status shares over the driving cars' periods, mean sweeps and QP iterations per
@@ -42,6 +47,7 @@ usage: tools/closed_loop_bench.py [--model dynamic|kinematic] [--batch 2048] [--
                                   [--delay D [--compensate]] [--noise s1,...,snx [--noise-seed S]]
                                   [--estimator q1,...,qnx [--meas-var r1,...,rnx] [--unmeasured i,j]]
                                   [--sensors s1,...,snx [--sensor-seed S]]
+                                  [--cone-sensor r_max,fov_deg,s_rho,s_beta[,p_detect] [--cone-k K] [--cone-map FILE.npz] [--unmeasured-pose]]
                                   [--nmpc K [--nmpc-trials T] [--nmpc-timing]]"""
 import argparse, json, os, sys, time
 import numpy as np
@@ -87,6 +93,11 @@ def main():
     ap.add_argument("--unmeasured", default=None, metavar="i,j", help="with --estimator: state components that are not measured (variance +inf)")
     ap.add_argument("--sensors", default=None, metavar="s1,...,snx", help="Cartesian sensor models: standard deviations in the sensor layout (CartesianSensors); excludes --noise")
     ap.add_argument("--sensor-seed", type=int, default=0, metavar="S", help="with --sensors: seed of the counter-based generator")
+    ap.add_argument("--cone-sensor", default=None, metavar="r_max,fov_deg,s_rho,s_beta[,p_detect]",
+                    help="cone-based localisation (ConeSensor): range m, opening angle deg, noise of range m and bearing rad, detection probability; needs --sensors and --estimator")
+    ap.add_argument("--cone-k", type=int, default=16, metavar="K", help="with --cone-sensor: observations per car and period (k_max)")
+    ap.add_argument("--cone-map", default=None, metavar="FILE.npz", help="with --cone-sensor: the cones, left / right or <track>_left / <track>_right (default: tests/golden/tracks/cones.npz)")
+    ap.add_argument("--unmeasured-pose", action="store_true", help="with --estimator and --sensors: X, Y and psi are not measured (variance +inf): a GPS outage")
     ap.add_argument("--nmpc", type=int, default=None, metavar="K", help="the batched SQP as the controller, K sweeps per period (Nmpc); excludes --corridor, --cones and --warm")
     ap.add_argument("--nmpc-trials", type=int, default=None, metavar="T", help="with --nmpc: step lengths the line search tries at once (default 8)")
     ap.add_argument("--nmpc-timing", action="store_true", help="with --nmpc: the SQP's phase sums by device events (fsaempc_qp_set_timing: one more synchronisation per sweep)")
@@ -140,6 +151,10 @@ def main():
             ap.error("--estimator needs --meas-var, --noise or --sensors")
         if len(r) != nx_ or any(not 0 <= i < nx_ for i in skip):
             ap.error("--meas-var takes %d values, --unmeasured indices 0 .. %d" % (nx_, nx_ - 1))
+        if a.unmeasured_pose:
+            if sens is None:
+                ap.error("--unmeasured-pose needs --sensors (the pose is a component of the sensor layout)")
+            skip = sorted(set(skip) | {0, 1, 2})
         for i in skip:
             r[i] = float("inf")
         try:
@@ -147,6 +162,33 @@ def main():
             est.resolve(lat, nx_, a.batch, a.laps, sens)
         except ValueError as e:
             ap.error(str(e))
+    elif a.unmeasured_pose:
+        ap.error("--unmeasured-pose needs --estimator")
+    cone_sensor = cone_cfg = None
+    if a.cone_sensor is not None:
+        if sens is None or est is None:
+            ap.error("--cone-sensor needs --sensors and --estimator")
+        try:
+            cv = [float(v) for v in a.cone_sensor.split(",")]
+        except ValueError:
+            ap.error("--cone-sensor takes comma-separated numbers")
+        if len(cv) not in (4, 5):
+            ap.error("--cone-sensor takes r_max,fov_deg,s_rho,s_beta[,p_detect]")
+        path = a.cone_map if a.cone_map is not None else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "tracks", "cones.npz")
+        with np.load(path) as z:
+            if "left" in z.files:
+                c_left, c_right = z["left"], z["right"]
+            elif a.track + "_left" in z.files:
+                c_left, c_right = z[a.track + "_left"], z[a.track + "_right"]
+            else:
+                ap.error("%s holds neither left / right nor %s_left / %s_right" % (path, a.track, a.track))
+        try:
+            cone_sensor = fm.ConeSensor(c_left, c_right, r_max=cv[0], fov=np.deg2rad(cv[1]), sigma=(cv[2], cv[3]), p_detect=cv[4] if len(cv) == 5 else 1.0,
+                                        k_max=a.cone_k, seed=a.sensor_seed)
+        except ValueError as e:
+            ap.error(str(e))
+        cone_cfg = {"r_max": cv[0], "fov_deg": cv[1], "sigma": [cv[2], cv[3]], "p_detect": cone_sensor.p_detect, "k_max": a.cone_k, "map": path,
+                    "cones": [int(len(c_left)), int(len(c_right))]}
     if a.corridor is not None and a.cones is not None:
         ap.error("--cones and --corridor exclude each other")
     if a.line_rows == "cells" and not (a.raceline and (a.corridor is not None or a.cones is not None)):
@@ -184,7 +226,7 @@ def main():
         plan = fm.Plan.raceline(model, tr, N_s=a.cells, N_c=a.points, margin=a.margin, grip=a.grip, corridor=cor, rows=a.line_rows)
     if a.minlap is not None:
         plan = fm.Plan.minlap(model, tr, N_s=a.cells, N_c=a.points, iters=a.minlap, margin=a.margin, grip=a.grip, corridor=cor)
-    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor, latency=lat, estimator=est, controller=ctl, sensors=sens)          # warm-up (allocations, code load)
+    fm.monte_carlo(model, a.horizon, tr, min(a.batch, 64), 2, a.seed, warm_start=a.warm, reference=plan, corridor=cor, latency=lat, estimator=est, controller=ctl, sensors=sens, cones=cone_sensor)          # warm-up (allocations, code load)
     n_max = float(fm.default_params(model)[fm.PARAM_INDEX["N_MAX"]])
     opts = fm.default_opts(max_iter=a.max_iter)
     t0 = time.perf_counter()
@@ -192,7 +234,7 @@ def main():
     # every car while it drives
     cart0, s_init = fm.monte_carlo_carts(tr, a.batch, a.seed, lap=a.lap)
     cl = fm.ClosedLoop(model, a.horizon, 0.05, tr, cart0, options=opts, warm_start=a.warm, launch_hint=not a.no_launch_hint, reference=plan,
-                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps, latency=lat, estimator=est, controller=ctl, sensors=sens)
+                       metrics=a.report, slack_tol=a.slack_tol, corridor=cor, laps=a.laps, latency=lat, estimator=est, controller=ctl, sensors=sens, cones=cone_sensor)
     cl.x_opt[:, :, 0] += torch.from_numpy(s_init).to(cl.device)[:, None]
     cl.x_opt[:, :, 3] += torch.from_numpy(cart0[:, 3]).to(cl.device)[:, None]
     fl_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
@@ -201,6 +243,9 @@ def main():
     off = torch.zeros((), dtype=torch.int64, device=cl.device)
     nis_sum = torch.zeros((), dtype=torch.float64, device=cl.device)
     nis_cnt = torch.zeros((), dtype=torch.int64, device=cl.device)
+    rows_sum = torch.zeros((), dtype=torch.int64, device=cl.device)      # with --cone-sensor: rows applied, cones kept and seen, over the same periods
+    kept_sum = torch.zeros((), dtype=torch.int64, device=cl.device)
+    seen_sum = torch.zeros((), dtype=torch.int64, device=cl.device)
     s_first = s_last = None
     if ctl is not None:   # the SQP's verbatim status and sweep count per (period, car), and its phase sums by device events
         st_d = torch.zeros((a.steps, a.batch), dtype=torch.int32, device=cl.device)
@@ -223,6 +268,8 @@ def main():
         s_last = torch.where(drv, cl.x0[:, 0], s_last)
         if est is not None:   # (a car that stopped driving in this very period still had its filter run)
             nis_sum += cl.est_nis.sum(); nis_cnt += (cl.est_nis != 0).sum()
+            if cone_sensor is not None:
+                rows_sum += cl.est_rows.sum(); kept_sum += cl.cone_n.sum(); seen_sum += cl.cone_seen.sum()
     torch.cuda.synchronize(cl.device)
     fl, it, ac = fl_d.cpu().numpy(), it_d.cpu().numpy(), ac_d.cpu().numpy()
     dt_wall = time.perf_counter() - t0
@@ -264,6 +311,9 @@ def main():
                                      "measured_components": nx_ - len(skip)}} if est is not None else {}),
                    **({"sensors": {"sigma": sens_sigma, "seed": a.sensor_seed, "filter": est is not None, "projections_lost": int(cl.proj_lost.sum().item()),
                                    "cars_with_a_lost_projection": int((cl.proj_lost > 0).sum().item())}} if sens is not None else {}),
+                   **({"cone_sensor": dict(cone_cfg, rows_mean=float(rows_sum.item()) / max(1, int(nis_cnt.item())),
+                                           cones_kept_mean=float(kept_sum.item()) / max(1, int(nis_cnt.item())),
+                                           cones_seen_mean=float(seen_sum.item()) / max(1, int(nis_cnt.item())))} if cone_sensor is not None else {}),
                    "controller": "LTV-MPC" if ctl is None else "MS-NMPC (batched SQP)", **({"nmpc": nmpc} if nmpc is not None else {}),
                    **({"cones": cone_info} if cone_info is not None else {}), "start": "s = 0 at rest (--lap)" if a.lap else "random s, speed U[0, 15]",
                    # (a mean over an empty set is NaN in the report: null in the JSON line)
