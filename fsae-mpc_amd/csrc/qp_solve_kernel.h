@@ -18,10 +18,10 @@
 #ifndef QP_DIAG_FLAT
 #define QP_DIAG_FLAT 1
 #endif
-// 1: pass 1 forms the scaled operands of both k-steps of a pair ahead of the pair's MFMAs and asks the scheduler to place the
-// VALU work of a k-step between its MFMAs (A/B builds; profiles/chol_panels/README.md)
-#ifndef QP_SYRK_INTERLEAVE
-#define QP_SYRK_INTERLEAVE 0
+// 1: pass 1 keeps the accumulator tiles of M in AGPRs across the trips of a phase where SyrkPin<T, NB> allows it; 0: the former
+// code in every instantiation (A/B builds; profiles/syrk_agpr/README.md)
+#ifndef QP_SYRK_PIN
+#define QP_SYRK_PIN 1
 #endif
 // 1: the former start-up, v = G x and A~'w of the initial multipliers as two passes (A/B and stamp builds: profiles/startup/README.md)
 #ifndef QP_STARTUP_ATW
@@ -243,6 +243,25 @@ template <int NA> struct CoefStage {
   }
 };
 
+// Where the accumulator tiles of M live during pass 1.  The MFMAs take them in AGPRs, the rest of the iteration reads them from
+// VGPRs, and left alone the register allocator moves the tiles a phase accumulates into VGPR -> AGPR at the top of every trip and
+// back behind the trip's last MFMA (4 C (C+1) moves each way in phase C; the way back waits for that MFMA, so the matrix pipe
+// drains once per trip).  An empty asm statement with the tile as an "a" operand in front of a phase's trip loop, at the head of
+// the trip body and behind the loop makes the AGPR copy the loop-carried one: it emits no instruction and changes no operand of an
+// MFMA or FMA, and every tile goes to the AGPRs once per pass, in front of the first phase that reaches it.  At the head of the
+// body alone the moves stay (tiles of the phase) or gather in the first phase's loop (every tile of M): profiles/syrk_agpr/README.md.
+// An instantiation that this costs scratch, spilled vector registers or its second wave per SIMD keeps the former code: <3,4>, which
+// would go from 0 to 8 spilled vector registers; the others are level or better (profiles/syrk_agpr/resource_usage.txt).
+template <int T, int NB> struct SyrkPin { static constexpr bool on = QP_SYRK_PIN && !(T == 3 && NB == 4); };
+template <int T, int NB, int C> DEVINL void syrk_pin_tiles(v4d* acc) {   // the tiles phase C reaches: (I, J), I <= J < C
+  if constexpr (SyrkPin<T, NB>::on) {
+#pragma unroll
+    for (int I = 0; I < C; ++I)
+#pragma unroll
+      for (int Jt = I; Jt < C; ++Jt) asm volatile("" : "+a"(acc[Tri<T>::idx(I, Jt)]));
+  }
+}
+
 // pass 1: acc += A~' D A~ on the matrix cores; p1 = A~'w1, p2 = A~'w2, p3 = A~'w3 on the VALU beside them.
 // The stream is walked trip by trip (4 k-steps); a trip with tc column tiles only touches the tc(tc+1)/2 accumulator
 // tiles it can reach.  Trips are sorted by tc, so the pass is T phases with compile-time tile counts (phase C: all
@@ -274,7 +293,9 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, Stream<T>& st, v4d*
   auto phase = [&](auto Cc) __attribute__((always_inline)) {
     constexpr int C = decltype(Cc)::value;
     const int tr_end = st.tend[C];
+    syrk_pin_tiles<T, NB, C>(acc);
     for (; tr < tr_end; ++tr) {
+      syrk_pin_tiles<T, NB, C>(acc);
       if ((tr & 3) == 0) { cs.commit(k); cs.load(k, arr, (tr >> 2) + 1); }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -282,13 +303,6 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, Stream<T>& st, v4d*
         st.template next_pair<C>(k, b);
         cs.read_pair(k, 4 * tr + 2 * u, cf);
         asm volatile("" ::: "memory");
-#if QP_SYRK_INTERLEAVE
-        double a2[2][C];   // the scaled operands of both k-steps of the pair, formed ahead of the first MFMA
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int t = 0; t < C; ++t) a2[h][t] = cf[0][h] * b[t][h];
-#endif
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           double a[C], ab[NBB];
@@ -296,11 +310,7 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, Stream<T>& st, v4d*
 #pragma unroll
           for (int e = 0; e < NB; ++e) ab[e] = cf[4 + e][h];
 #pragma unroll
-#if QP_SYRK_INTERLEAVE
-          for (int t = 0; t < C; ++t) a[t] = a2[h][t];
-#else
           for (int t = 0; t < C; ++t) a[t] = dd * b[t][h];
-#endif
 #pragma unroll
           for (int I = 0; I < C; ++I)
 #pragma unroll
@@ -319,17 +329,10 @@ template <int T, int NB> DEVINL void pass_syrk(const Ctx& k, Stream<T>& st, v4d*
             for (int f = e; f < NB; ++f) sbb[e][f] = fma(dab, ab[f], sbb[e][f]);
             pwb[0][e] = fma(w1, ab[e], pwb[0][e]); pwb[1][e] = fma(w2, ab[e], pwb[1][e]); pwb[2][e] = fma(w3, ab[e], pwb[2][e]);
           }
-#if QP_SYRK_INTERLEAVE
-          // the k-step's VALU work (p1..p3, the border) goes between its MFMAs instead of behind them: 1 MFMA, then up to 2 VALU
-#pragma unroll
-          for (int i = 0; i < C * (C + 1) / 2; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-          }
-#endif
         }
       }
     }
+    syrk_pin_tiles<T, NB, C>(acc);
   };
   if constexpr (T >= 1) phase(IC<1>{});
   if constexpr (T >= 2) phase(IC<2>{});
